@@ -7,12 +7,16 @@
 
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM:
     Morton sort + cell scan (CSR radius graph)  ->  edge geometry  ->  SEGNN forward (L layers)
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line: `value` (particles/s over all ranks), `ms_per_step` (wall time of one timed step), `metric`,
+`unit`, `higher_is_better`, `dtype`.  A plain run does only what that line needs: set-up, warm-up, the timed steps and, with
+`--dump-outputs DIR`, the last timed step's outputs.  With `--full` the line also carries the figures that cost runs or
+instrumentation of their own:
   roofline     : the dominant kernel (largest total time among the timed launches: the fused message kernel), timed
                  live with HIP events on the launch stream; achieved = algorithmic flops (x3 for the fp16 split) or bytes
                  / avg launch time; traffic = HBM bytes per launch from committed rocprofv3 --pmc passes (traffic_source)
   cpu_baseline : the CPU oracle pipeline (reference op pattern for every TP) on a bounded sample after a warm-up,
                  all host cores, rank 0, N=1 only; cpu_baseline_best_effort: the best CPU formulation we know.
+  bf16_storage : a second timed leg of the same workload in bf16 storage (l_max = 2, fp32 runs only).
 """
 import argparse
 import json
@@ -31,6 +35,7 @@ METRIC = "particles/sec (octree build + SEGNN fwd), 1M pts l_max=2, 1/2/4/8 MI35
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_F32_PEAK_TF = 157.3   # MI355X_MICROARCH.md: fp32-input MFMA (v_mfma_f32_32x32x2_f32) dense peak
 MFMA_BF16_PEAK_TF = 2500.0  # MI355X_MICROARCH.md: bf16 MFMA dense peak (~2.5 PF)
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
 
 
 def cutoff(n, k=24.0):
@@ -139,6 +144,26 @@ def roofline_of(dom_tag, dom, traffic_file):
     return roof
 
 
+def dump_outputs(outdir, g, out):
+    """The last timed step's outputs as a caller of the step receives them (the graph and the node features, both in the
+    graph's Morton order) -> ``outdir/<name>.npy``: features as float32, indices as float64 (exact).  Each of the four
+    arrays gets a quarter of DUMP_BYTES; a larger one is cut to a fixed seeded sample of its rows, whose row indices are
+    written beside it as ``<name>_rows.npy``."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"out": out.float(), "perm": g.perm, "rowptr": g.rowptr, "src": g.src}
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+        row_bytes = a.itemsize * (a.size // max(1, a.shape[0]))
+        if a.nbytes > share:
+            k = share // (row_bytes + 8)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(outdir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -151,11 +176,21 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=None, help="particles in the CPU-baseline sample")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="storage type of features / weights (bf16 = BASELINE config 3; l_max=2 only)")
-    ap.add_argument("--timing-json", type=str, default=None, help="also dump per-TP timings here")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-launch HIP events in the timed steps for "
+                         "`roofline`, the bf16-storage leg and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--timing-json", type=str, default=None, help="also dump per-TP timings here (with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-bf16-leg", action="store_true",
-                    help="skip the extra timed leg in bf16 storage (BASELINE.json configs[2]) reported as `bf16_storage`")
+                    help="with --full: skip the extra timed leg in bf16 storage (BASELINE.json configs[2]) reported as "
+                         "`bf16_storage`")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.timing_json and not args.full:
+        raise SystemExit("--timing-json needs --full (the per-launch timings come from its instrumented steps)")
 
     import models  # noqa: F401
     from scalable_e3_gnn_amd import ops, profiling
@@ -258,10 +293,12 @@ def main():
         assert torch.isfinite(out.float()).all()
         return dt, g, out, prof
 
-    dt, g, out, prof = timed(make_step(model, x), args.warmup, args.steps, True)
+    dt, g, out, prof = timed(make_step(model, x), args.warmup, args.steps, args.full)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, g, out)
     # second leg, same workload in bf16 storage (BASELINE.json configs[2]); reported beside the fp32 value, never as it
     bf16_leg = None
-    if args.dtype == "f32" and args.lmax == 2 and not args.no_bf16_leg:
+    if args.full and args.dtype == "f32" and args.lmax == 2 and not args.no_bf16_leg:
         m16 = SEGNN("1x0e+1x1o", args.hidden, "1x1o", args.layers, lmax=args.lmax).to(dev)
         m16.load_state_dict(model.state_dict())
         m16 = m16.bfloat16()
@@ -280,11 +317,13 @@ def main():
     if rank == 0:
         ms = dt / args.steps * 1e3
         total_particles = n * world
-        dom_tag, dom = max(prof.items(), key=lambda kv: kv[1]["total_ms"])
-        roof = roofline_of(dom_tag, dom, os.path.join(REPO, "profiles", f"r03_traffic_lmax{args.lmax}.json"))
-        roof["tp_share_of_step"] = sum(v["total_ms"] for v in prof.values()) / (dt * 1e3)
-        if args.timing_json:
-            json.dump(prof, open(args.timing_json, "w"), indent=1)
+        roof = None
+        if args.full:
+            dom_tag, dom = max(prof.items(), key=lambda kv: kv[1]["total_ms"])
+            roof = roofline_of(dom_tag, dom, os.path.join(REPO, "profiles", f"r03_traffic_lmax{args.lmax}.json"))
+            roof["tp_share_of_step"] = sum(v["total_ms"] for v in prof.values()) / (dt * 1e3)
+            if args.timing_json:
+                json.dump(prof, open(args.timing_json, "w"), indent=1)
         line = {
             "metric": METRIC, "value": total_particles / (dt / args.steps), "unit": "particles/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
@@ -303,11 +342,12 @@ def main():
                        "layers": args.layers, "lmax": args.lmax,
                        "parallelism": (f"spatial slabs x{world}, ghost halo width r, 1 position + {args.layers} feature "
                                        f"p2p exchanges/step over RCCL") if world > 1 else "single GPU"},
-            "roofline": roof,
         }
+        if roof is not None:
+            line["roofline"] = roof
         if bf16_leg is not None:
             line["bf16_storage"] = bf16_leg
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], line["cpu_baseline_best_effort"] = cpu_baseline(args, model.state_dict())
         print(json.dumps(line), flush=True)
     if dist is not None:
