@@ -155,6 +155,24 @@ int e3_rg_sort_count(const float* pos, int64_t N, const e3_rg_params* prm,
 int e3_rg_fill(int64_t N, const e3_rg_params* prm, const float* sorted_pos4, const int32_t* rowptr,
                int32_t* src, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Orthorhombic periodic box, chosen per axis: `periodic` bit a (0..2) = axis a periodic, the other axes open as above.
+ * Same grid, workspace, call sequence and outputs as e3_rg_sort_count / e3_rg_fill; on a periodic axis a, with
+ * L = fl32(hi_a - lo_a), invL = fl32(1 / L), hL = fl32(0.5 * L):
+ *   wrap   : w = fl32(p - fl32(L * floorf(fl32(fl32(p - lo_a) * invL)))); then one correction step:
+ *            w >= hi_a -> w = fl32(w - L), else w < lo_a -> w = fl32(w + L).  Cell and key are taken from w, and
+ *            sorted_pos4 holds w (open axes: p unchanged).
+ *   cells  : the 27 neighbour cells are taken modulo n_a (a cell named twice, n_a <= 2, is scanned once).
+ *   edge   : dx = fl32(x_i - x_j); dx > hL -> dx = fl32(dx - L), else dx < -hL -> dx = fl32(dx + L)  (x_i, x_j wrapped);
+ *            then d2 and the test d2 <= fl32(r*r) exactly as in the open box.
+ * Requires 0 < L and 2 r < L on every periodic axis (the minimum image is then unique: no pair has two edges, no
+ * particle is its own neighbour); otherwise, or periodic outside [0, 7], E3_ERR_INVALID_ARG before any launch.
+ * `periodic` must be the same in both calls. */
+int e3_rg_sort_count_pbc(const float* pos, int64_t N, const e3_rg_params* prm, int32_t periodic,
+                         int32_t* perm, float* sorted_pos4, int32_t* rowptr,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int e3_rg_fill_pbc(int64_t N, const e3_rg_params* prm, int32_t periodic, const float* sorted_pos4,
+                   const int32_t* rowptr, int32_t* src, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =================================================================================================
  * Edge / node stages of the SEGNN forward around the tensor product (builder-defined, SURVEY.md
  * §8a-N2, N3; fp32).  Graph = CSR by dst from e3_rg_* (rowptr [N+1], src [E], positions pos4 [N,4]).
@@ -165,6 +183,13 @@ int e3_rg_fill(int64_t N, const e3_rg_params* prm, const float* sorted_pos4, con
 /* edge_y [E,4], edge_d [E] (may be NULL), node_a [N,4] (may be NULL) */
 int e3_edge_geometry(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N,
                      float* edge_y, float* edge_d, float* node_a, void* stream);
+/* Periodic box (the *_pbc entries of the geometry, its backward and e3_msg_forward): box[3] (host) = L_a per axis, 0 = open
+ * axis.  rel_e is the minimum image of x[src_e] - x[dst_e], per periodic axis
+ *   d = fl32(x_src - x_dst);  rel = fl32(d - fl32(L * rintf(fl32(d * invL)))),   invL = fl32(1 / L)
+ * which holds for wrapped and for unwrapped coordinates (positions shifted by whole periods).  The shift is constant, so
+ * the backward is the open-box backward at the shifted vector.  A negative or non-finite L is E3_ERR_INVALID_ARG. */
+int e3_edge_geometry_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float box[3],
+                         float* edge_y, float* edge_d, float* node_a, void* stream);
 /* out[e] = [ h[dst_e] (D) | h[src_e] (D) | extra[e] (n_extra, may be 0) ]   row strides in elements */
 int e3_gather_concat(const float* h, int64_t ld_h, int D, const int32_t* rowptr, const int32_t* src, int64_t N,
                      const float* extra, int n_extra, float* out, int64_t ld_out, void* stream);
@@ -364,6 +389,11 @@ int e3_msg_forward(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, co
                    const int32_t* src, const int32_t* dst, int64_t E, const void* packed, const float* in_scale,
                    const float* premix, float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block,
                    void* stream);
+/* e3_msg_forward with Y_e, d_e of the minimum-image edge vector (box[3] as in e3_edge_geometry_pbc) */
+int e3_msg_forward_pbc(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const float* pos4,
+                       const int32_t* src, const int32_t* dst, int64_t E, const void* packed, const float* in_scale,
+                       const float* premix, float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block,
+                       const float box[3], void* stream);
 /*
  * bf16 storage (dtype E3_BF16, BASELINE config 3): segments / in1 / out / weights / norms are bf16, in2 (the
  * spherical harmonics) stays fp32, products run once on v_mfma_f32_16x16x32_bf16 with fp32 accumulation and one
@@ -374,6 +404,9 @@ int e3_segment_sum_bf16(const void* msg, int64_t ld_msg, const int32_t* rowptr, 
 /* SH / geometry for lmax 2: edge_y [E,9], node_a [N,9] (same definitions as e3_edge_geometry, Y2 = sqrt5 b(r^)) */
 int e3_edge_geometry_l2(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N,
                         float* edge_y, float* edge_d, float* node_a, void* stream);
+/* periodic box: as e3_edge_geometry_pbc */
+int e3_edge_geometry_l2_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float box[3],
+                            float* edge_y, float* edge_d, float* node_a, void* stream);
 /* general gate: in = [ns scalars | g gate scalars | gated blocks], block i = mul_i x (2 l_i + 1) with one gate per
  * channel, gates consumed in block order; out = [silu(s) | sigmoid(gate) * block].  ls/muls: host int arrays. */
 int e3_gate_blocks(const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t B, int ns,
@@ -394,6 +427,10 @@ int e3_gate_blocks(const float* in, int64_t ld_in, float* out, int64_t ld_out, i
 int e3_edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                               const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
                               void* stream);
+/* periodic box: as e3_edge_geometry_pbc */
+int e3_edge_geometry_backward_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float box[3], const float* g_edge_y, const float* g_edge_d,
+                                  const float* g_node_a, float* g_pos, void* stream);
 int e3_gather_concat_backward(const float* g_out, int64_t ld_gout, int D, const int32_t* rowptr, const int32_t* src,
                               int64_t N, int n_extra, float* g_h, int64_t ld_gh, float* g_extra, void* stream);
 int e3_gate_blocks_backward(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, float* g_in,

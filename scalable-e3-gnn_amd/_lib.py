@@ -21,6 +21,7 @@ CLS_NAMES = ("l0e", "l0o", "l1e", "l1o")
 _lib = None
 
 VoidP4 = c_void_p * 4
+Float3 = ctypes.c_float * 3  # a host float[3] argument (periodic box lengths)
 
 # name -> (restype, argtypes); mirrors include/e3gnn.h one to one
 SIGNATURES = {
@@ -77,6 +78,19 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "e3_edge_geometry_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    # periodic boxes (box = float[3] of L per axis, 0 = open; periodic = axis bit mask)
+    "e3_rg_sort_count_pbc": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_void_p]),
+    "e3_rg_fill_pbc": (c_int, [c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_edge_geometry_pbc": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, Float3, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "e3_edge_geometry_l2_pbc": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, Float3, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "e3_edge_geometry_backward_pbc": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float3, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
+    "e3_msg_forward_pbc": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, Float3,
+                                   c_void_p]),
     "e3_gather_concat_backward": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
                                           c_void_p, c_void_p]),
     "e3_gate_blocks_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,

@@ -65,6 +65,47 @@ struct PlanDev {
 
 struct Mfma;
 
+// orthorhombic periodic box of the periodic edge kernels (the *_pbc entries): per axis the box length L and 1 / L, both 0 on
+// an open axis (the minimum image below is then the identity)
+struct PbcBox {
+  float L[3], invL[3];
+};
+// minimum image of one component d = x_src - x_dst: d - L rint(d / L), explicitly rounded (include/e3gnn.h); d for L = 0
+__device__ __forceinline__ float min_image(const float d, const float L, const float invL) {
+  return __fsub_rn(d, __fmul_rn(L, rintf(__fmul_rn(d, invL))));
+}
+// edge vector x_src - x_dst of the geometry kernels; PBC: its minimum image (the rint form, so unwrapped coordinates work too)
+template <bool PBC>
+__device__ __forceinline__ void edge_rel(const float4 pj, const float4 pi, const PbcBox& box, float& rx, float& ry,
+                                         float& rz) {
+  if constexpr (PBC) {
+    rx = min_image(__fsub_rn(pj.x, pi.x), box.L[0], box.invL[0]);
+    ry = min_image(__fsub_rn(pj.y, pi.y), box.L[1], box.invL[1]);
+    rz = min_image(__fsub_rn(pj.z, pi.z), box.L[2], box.invL[2]);
+  } else {
+    rx = pj.x - pi.x; ry = pj.y - pi.y; rz = pj.z - pi.z;
+  }
+}
+
+// host: box[3] of a *_pbc entry (L per axis, 0 = open): finite, no negative length, and 2 r < L on every periodic axis
+inline bool box_valid(const float* box, float r) {
+  if (!box) return false;
+  for (int a = 0; a < 3; ++a) {
+    const float L = box[a];
+    if (!(L >= 0.0f) || !(L < 3.0e38f)) return false;
+    if (L > 0.0f && !(2.0f * r < L)) return false;
+  }
+  return true;
+}
+inline PbcBox make_box(const float* box) {
+  PbcBox b = {};
+  for (int a = 0; a < 3 && box; ++a) {
+    b.L[a] = box[a];
+    b.invL[a] = box[a] > 0.0f ? 1.0f / box[a] : 0.0f;
+  }
+  return b;
+}
+
 }  // namespace e3
 
 struct e3_l1tp_plan {

@@ -16,12 +16,14 @@ constexpr float kS3 = 1.7320508075688772f, kS5 = 2.2360679774997896f;
 //   g_u      = sqrt3 gY1 + sqrt5 (db/du)^T gY2
 //   g_r      = (g_u - u (u . g_u)) / d + gd u          (0 for d = 0: the forward uses u = 0 there)
 //   gpos[src] += g_r   (atomics),   gpos[dst] -= sum_e g_r   (wave reduction, one atomic per row and component)
-template <int LMAX>
+// PBC: r is the minimum image of x_src - x_dst; the shift is piecewise constant, so dr/dx is that of the open box.
+template <int LMAX, bool PBC>
 __global__ __launch_bounds__(256) void edge_geometry_bwd_kernel(const float4* __restrict__ pos4,
                                                                 const int32_t* __restrict__ rowptr,
                                                                 const int32_t* __restrict__ src, int64_t N,
                                                                 const float* __restrict__ gY, const float* __restrict__ gd,
-                                                                const float* __restrict__ gA, float* __restrict__ gpos) {
+                                                                const float* __restrict__ gA, float* __restrict__ gpos,
+                                                                const PbcBox box) {
   constexpr int NY = (LMAX + 1) * (LMAX + 1);
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
@@ -38,7 +40,8 @@ __global__ __launch_bounds__(256) void edge_geometry_bwd_kernel(const float4* __
     for (int q = b + lane; q < e; q += 64) {
       const int j = src[q];
       const float4 pj = pos4[j];
-      const float rx = pj.x - pi.x, ry = pj.y - pi.y, rz = pj.z - pi.z;
+      float rx, ry, rz;
+      edge_rel<PBC>(pj, pi, box, rx, ry, rz);
       const float d = sqrtf(rx * rx + ry * ry + rz * rz);
       if (!(d > 0.f)) continue;
       const float inv = 1.0f / d;
@@ -169,24 +172,37 @@ static inline int wave_grid_b(int64_t N) { return (int)std::max<int64_t>(1, std:
 
 using namespace e3;
 
-extern "C" {
-
-int e3_edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
-                              const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
-                              void* stream) {
+// box: NULL = open, else validated by the caller
+static int edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
+                                  const float* box, void* stream) {
   if (N < 0 || (lmax != 1 && lmax != 2)) return E3_ERR_INVALID_ARG;
   if (N == 0) return E3_OK;
   if (!pos4 || !rowptr || !src || !g_pos) return E3_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   E3_HIP_CHECK(hipMemsetAsync(g_pos, 0, (size_t)N * 3 * sizeof(float), s));
-  if (lmax == 1)
-    hipLaunchKernelGGL(edge_geometry_bwd_kernel<1>, dim3(wave_grid_b(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src,
-                       N, g_edge_y, g_edge_d, g_node_a, g_pos);
-  else
-    hipLaunchKernelGGL(edge_geometry_bwd_kernel<2>, dim3(wave_grid_b(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src,
-                       N, g_edge_y, g_edge_d, g_node_a, g_pos);
+  const PbcBox b = make_box(box);
+  auto kern = lmax == 1 ? (box ? edge_geometry_bwd_kernel<1, true> : edge_geometry_bwd_kernel<1, false>)
+                        : (box ? edge_geometry_bwd_kernel<2, true> : edge_geometry_bwd_kernel<2, false>);
+  hipLaunchKernelGGL(kern, dim3(wave_grid_b(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
+                     g_node_a, g_pos, b);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
+}
+
+extern "C" {
+
+int e3_edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                              const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
+                              void* stream) {
+  return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, nullptr, stream);
+}
+
+int e3_edge_geometry_backward_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float box[3], const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
+                                  float* g_pos, void* stream) {
+  if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, box, stream);
 }
 
 int e3_gather_concat_backward(const float* g_out, int64_t ld_gout, int D, const int32_t* rowptr, const int32_t* src,

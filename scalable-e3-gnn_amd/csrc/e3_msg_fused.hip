@@ -530,14 +530,14 @@ constexpr int msg_waves_per_simd(int lmax, int tt) {
   return (lmax == 2 ? 44 : 20) * tt <= 96 ? ((lmax == 2 && tt == 2) ? E3_MSG_WPS : 2) : 1;
 }
 
-template <int LMAX, int TT, bool IO16>
+template <int LMAX, int TT, bool IO16, bool PBC>
 // (waves per SIMD fixed from both sides: with the minimum alone the scheduler of a small instantiation -- l_max = 1 needs ~120
 // registers -- trades its load / compute overlap for an occupancy the launch does not use: 6.7 -> 8.7 ms)
 __global__ __launch_bounds__(256, msg_waves_per_simd(LMAX, TT))
 __attribute__((amdgpu_waves_per_eu(msg_waves_per_simd(LMAX, TT), msg_waves_per_simd(LMAX, TT)))) void msg_fused_kernel(
     const void* __restrict__ hv, int64_t ldh, const float4* __restrict__ pos4, const int32_t* __restrict__ src,
     const int32_t* __restrict__ dst, int64_t E, const float* __restrict__ packed, const float* __restrict__ U,
-    const float* __restrict__ in_scale, float* __restrict__ out, int64_t ldo, int blk) {
+    const float* __restrict__ in_scale, float* __restrict__ out, int64_t ldo, int blk, const PbcBox box) {
   using G = MsgGeom<LMAX, TT>;
   constexpr int H = G::H, D = G::D, T0 = G::T(0), NS = G::NS;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -709,7 +709,7 @@ __attribute__((amdgpu_waves_per_eu(msg_waves_per_simd(LMAX, TT), msg_waves_per_s
       float y[9], dist;
       {
         const float4 ps = pos4[sid], pd = pos4[did];
-        if constexpr (LMAX == 2) edge_sh(ps, pd, y, dist); else edge_sh1(ps, pd, y, dist);
+        if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, box); else edge_sh1<PBC>(ps, pd, y, dist, box);
       }
       f32x4 a0[T0], a1[TT][3], a2[LMAX == 2 ? TT : 1][5];
       const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -965,6 +965,7 @@ __attribute__((amdgpu_waves_per_eu(msg_waves_per_simd(LMAX, TT), msg_waves_per_s
 struct MsgKernels {
   int lmax, tt;
   const void* fused[2];   // [0] fp32 storage, [1] bf16 storage (nullptr: not instantiated)
+  const void* fused_pbc[2];  // the same with the periodic minimum image (e3_msg_forward_pbc)
   const void* premix[2];
   int64_t total_floats;
   int UD, D, lds_tab, lds_wave, nblk, NS, WD, o_norm1, o_norm2, o_wd, o_w, waves_per_simd;
@@ -972,12 +973,14 @@ struct MsgKernels {
 template <int LMAX, int TT>
 static MsgKernels make_entry() {
   using G = MsgGeom<LMAX, TT>;
-  MsgKernels k = {LMAX, TT, {(const void*)msg_fused_kernel<LMAX, TT, false>, nullptr},
+  MsgKernels k = {LMAX, TT, {(const void*)msg_fused_kernel<LMAX, TT, false, false>, nullptr},
+                  {(const void*)msg_fused_kernel<LMAX, TT, false, true>, nullptr},
                   {(const void*)msg_premix_kernel<LMAX, TT, false>, nullptr}, G::total_floats,
                   G::UD, G::D, G::lds_tab, G::lds_wave, G::nblk(), G::NS, G::WD, G::o_norm1, G::o_norm2, G::o_wd, G::o_w,
                   msg_waves_per_simd(LMAX, TT)};
   if constexpr (TT >= 2) {  // bf16 storage: the [0e] region of a staged row must be at least 4 units of 16 bytes (H >= 32)
-    k.fused[1] = (const void*)msg_fused_kernel<LMAX, TT, true>;
+    k.fused[1] = (const void*)msg_fused_kernel<LMAX, TT, true, false>;
+    k.fused_pbc[1] = (const void*)msg_fused_kernel<LMAX, TT, true, true>;
     k.premix[1] = (const void*)msg_premix_kernel<LMAX, TT, true>;
   }
   return k;
@@ -1001,6 +1004,7 @@ struct e3_msg_plan {
   MsgPackDesc* d_desc = nullptr;
   int device = -1;
   int grid[2] = {0, 0};  // workgroups of a full launch per storage type: CUs x resident workgroups per CU (occupancy query)
+  int grid_pbc[2] = {0, 0};  // the same for the periodic instantiations
   std::mutex mu;
 };
 
@@ -1022,13 +1026,16 @@ static int msg_ensure_device(e3_msg_plan* P) {
     if (!P->k->fused[io]) continue;
     // The grid fills the chip exactly once: what the registers the compiler ended up with and the LDS image allow per CU
     // (2 workgroups for H = 32, l_max = 2; the small instantiations fit 3-4), not a number assumed at compile time.
-    int per_cu = 0;
-    if (hipFuncSetAttribute(P->k->fused[io], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, P->k->fused[io], 256, lds) != hipSuccess || per_cu < 1) {
-      (void)hipFree(d);
-      return E3_ERR_HIP;
+    for (int pb = 0; pb < 2; ++pb) {
+      const void* kern = pb ? P->k->fused_pbc[io] : P->k->fused[io];
+      int per_cu = 0;
+      if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu < 1) {
+        (void)hipFree(d);
+        return E3_ERR_HIP;
+      }
+      (pb ? P->grid_pbc : P->grid)[io] = cus * (per_cu < 4 ? per_cu : 4);
     }
-    P->grid[io] = cus * (per_cu < 4 ? per_cu : 4);
   }
   P->device = cur;
   P->d_desc = d;
@@ -1162,9 +1169,13 @@ int e3_msg_premix(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const 
   return E3_OK;
 }
 
-int e3_msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
-                   const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
-                   float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block, void* stream) {
+}  // extern "C"
+
+// box: NULL = the open kernels; else L per axis (0 = open axis), already validated
+static int msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
+                       const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
+                       float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block, void* stream,
+                       const float* box) {
   if (!P || N < 0 || E < 0 || E > 0x7fffffffLL - 16) return E3_ERR_INVALID_ARG;  // edge ids are int32
   if (!e3_msg_supports(P, dtype)) return E3_ERR_UNSUPPORTED;
   const MsgKernels& k = *P->k;
@@ -1183,20 +1194,40 @@ int e3_msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const
   // tiles_per_block < 0 asks for this file's one-wave-per-tile kernel with |tiles_per_block| tiles per wave block.
   if (tiles_per_block >= 0 && msg_ws_supported(P->lmax, P->H, dtype)) {
     st = msg_ws_launch(P->lmax, P->H, dtype, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out,
-                       tiles_per_block > (1 << 20) ? (1 << 24) : tiles_per_block * 16, s);
+                       tiles_per_block > (1 << 20) ? (1 << 24) : tiles_per_block * 16, s, box);
     if (st != E3_ERR_UNSUPPORTED) return st;
   }
   if (tiles_per_block < 0) tiles_per_block = -tiles_per_block;
   const int64_t ntiles = (E + 15) / 16;
-  int nwg = P->grid[io];  // 4 waves per workgroup, every CU filled once
+  int nwg = (box ? P->grid_pbc : P->grid)[io];  // 4 waves per workgroup, every CU filled once
   nwg = (int)std::min<int64_t>(nwg, (ntiles + 3) / 4);
   nwg = std::max(8, (nwg + 7) / 8 * 8);
   int blk = tiles_per_block > 0 ? tiles_per_block : 4;  // default: 64 edges (2-3 dst nodes) per wave block
   if (blk > (1 << 16)) blk = 1 << 16;
   const size_t lds = (size_t)(k.lds_tab + 4 * k.lds_wave) * 4 + 4 * 256;
-  void* args[] = {&h, &ld_h, &pos4, &src, &dst, &E, &packed, &premix, &in_scale, &out, &ld_out, &blk};
-  if (hipLaunchKernel(k.fused[io], dim3(nwg), dim3(256), args, lds, s) != hipSuccess) return E3_ERR_HIP;
+  PbcBox pbox = make_box(box);
+  void* args[] = {&h, &ld_h, &pos4, &src, &dst, &E, &packed, &premix, &in_scale, &out, &ld_out, &blk, &pbox};
+  if (hipLaunchKernel(box ? k.fused_pbc[io] : k.fused[io], dim3(nwg), dim3(256), args, lds, s) != hipSuccess)
+    return E3_ERR_HIP;
   return E3_OK;
+}
+
+extern "C" {
+
+int e3_msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
+                   const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
+                   float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block, void* stream) {
+  return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, accumulate,
+                     tiles_per_block, stream, nullptr);
+}
+
+int e3_msg_forward_pbc(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
+                       const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
+                       float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block, const float box[3],
+                       void* stream) {
+  if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
+  return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, accumulate,
+                     tiles_per_block, stream, box);
 }
 
 #if E3_MSG_STAMP

@@ -490,9 +490,10 @@ struct WsArgs {
   const float4* pos4; const int32_t* src; const int32_t* dst; int64_t E;
   const float* packed; const float* U; const float* hmax; const float* in_scale; float* out; int64_t ldo;
   int chunk;  // edges per chunk (multiple of 16)
+  PbcBox box;  // periodic instantiations only (the open kernel never reads it)
 };
 
-template <int LMAX, int TT, bool IO16, int W>
+template <int LMAX, int TT, bool IO16, int W, bool PBC>
 __device__ __forceinline__ void ws_run(const WsArgs& A, unsigned char* smem) {
   using G = MsgGeom<LMAX, TT>;
   using L = Ws<LMAX, TT, IO16>;
@@ -759,7 +760,7 @@ __device__ __forceinline__ void ws_run(const WsArgs& A, unsigned char* smem) {
         }
         __builtin_amdgcn_sched_barrier(0);
         float y[9], dist;
-        if constexpr (LMAX == 2) edge_sh(ps, pd, y, dist); else edge_sh1(ps, pd, y, dist);
+        if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, A.box); else edge_sh1<PBC>(ps, pd, y, dist, A.box);
         auto put4 = [&](const int fr, const float (&f)[4]) { ws_put4<IO16>(b1 + fr * L::FRB, f, xs); };  // (operand scale in the split)
         auto degree = [&](auto ltag, float* q) {  // q[r * D1 + a]: channel r of the piece, component a
           constexpr int L1 = decltype(ltag)::value, D1 = 2 * L1 + 1;
@@ -796,7 +797,7 @@ __device__ __forceinline__ void ws_run(const WsArgs& A, unsigned char* smem) {
         const float* urow = reinterpret_cast<const float*>(smem + L::o_u + slot * L::U_ROW) + 4 * g;
         constexpr int T0 = G::T(0);
         float y[9], dist;
-        if constexpr (LMAX == 2) edge_sh(ps, pd, y, dist); else edge_sh1(ps, pd, y, dist);
+        if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, A.box); else edge_sh1<PBC>(ps, pd, y, dist, A.box);
         const float dsc = dist * xs;
         float z110[3][1], z220[5][1];
         make_z<1, 1, 0>(y, z110);
@@ -1061,7 +1062,7 @@ __device__ __forceinline__ void ws_run(const WsArgs& A, unsigned char* smem) {
 #undef WS_STAMP
 }
 
-template <int LMAX, int TT, bool IO16>
+template <int LMAX, int TT, bool IO16, bool PBC>
 // (waves per SIMD fixed from both sides: the LDS image admits one workgroup per CU = 2 waves per SIMD; with the minimum alone
 // hipcc schedules for a third wave -- it held the kernel at 167 registers by issuing every LDS read right in front of its use)
 __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void msg_ws_kernel(const WsArgs A) {
@@ -1082,14 +1083,14 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   __syncthreads();
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   switch (wave) {
-    case 0: ws_run<LMAX, TT, IO16, 0>(A, ws_smem); break;
-    case 1: ws_run<LMAX, TT, IO16, 1>(A, ws_smem); break;
-    case 2: ws_run<LMAX, TT, IO16, 2>(A, ws_smem); break;
-    case 3: ws_run<LMAX, TT, IO16, 3>(A, ws_smem); break;
-    case 4: ws_run<LMAX, TT, IO16, 4>(A, ws_smem); break;
-    case 5: ws_run<LMAX, TT, IO16, 5>(A, ws_smem); break;
-    case 6: ws_run<LMAX, TT, IO16, 6>(A, ws_smem); break;
-    default: ws_run<LMAX, TT, IO16, 7>(A, ws_smem); break;
+    case 0: ws_run<LMAX, TT, IO16, 0, PBC>(A, ws_smem); break;
+    case 1: ws_run<LMAX, TT, IO16, 1, PBC>(A, ws_smem); break;
+    case 2: ws_run<LMAX, TT, IO16, 2, PBC>(A, ws_smem); break;
+    case 3: ws_run<LMAX, TT, IO16, 3, PBC>(A, ws_smem); break;
+    case 4: ws_run<LMAX, TT, IO16, 4, PBC>(A, ws_smem); break;
+    case 5: ws_run<LMAX, TT, IO16, 5, PBC>(A, ws_smem); break;
+    case 6: ws_run<LMAX, TT, IO16, 6, PBC>(A, ws_smem); break;
+    default: ws_run<LMAX, TT, IO16, 7, PBC>(A, ws_smem); break;
   }
 }
 
@@ -1102,36 +1103,41 @@ bool msg_ws_supported(int lmax, int hidden, int dtype) {
 
 int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, int64_t N, const float* pos4, const int32_t* src,
                   const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix, float* out,
-                  int64_t ldo, int chunk_edges, hipStream_t stream) {
+                  int64_t ldo, int chunk_edges, hipStream_t stream, const float* box) {
   if (!msg_ws_supported(lmax, hidden, dtype)) return E3_ERR_UNSUPPORTED;
+  const int pb = box ? 1 : 0;
   if (E > 0x7fffffffLL - 65536) return E3_ERR_UNSUPPORTED;  // 32-bit edge arithmetic with chunk head room
   const int io = dtype == E3_BF16 ? 1 : 0;
   const int li = lmax == 2 ? 1 : 0;
 #if WS_LMAX1
-  const void* kern = li ? (io ? (const void*)msg_ws_kernel<2, 2, true> : (const void*)msg_ws_kernel<2, 2, false>)
-                        : (io ? (const void*)msg_ws_kernel<1, 2, true> : (const void*)msg_ws_kernel<1, 2, false>);
+  const void* kern =
+      pb ? (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, true> : (const void*)msg_ws_kernel<2, 2, false, true>)
+               : (io ? (const void*)msg_ws_kernel<1, 2, true, true> : (const void*)msg_ws_kernel<1, 2, false, true>))
+         : (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, false> : (const void*)msg_ws_kernel<2, 2, false, false>)
+               : (io ? (const void*)msg_ws_kernel<1, 2, true, false> : (const void*)msg_ws_kernel<1, 2, false, false>));
   const int lds = li ? (io ? Ws<2, 2, true>::total : Ws<2, 2, false>::total) : (io ? Ws<1, 2, true>::total : Ws<1, 2, false>::total);
   const int ud = li ? MsgGeom<2, 2>::UD : MsgGeom<1, 2>::UD;
 #else
-  const void* kern = io ? (const void*)msg_ws_kernel<2, 2, true> : (const void*)msg_ws_kernel<2, 2, false>;
+  const void* kern = pb ? (io ? (const void*)msg_ws_kernel<2, 2, true, true> : (const void*)msg_ws_kernel<2, 2, false, true>)
+                        : (io ? (const void*)msg_ws_kernel<2, 2, true, false> : (const void*)msg_ws_kernel<2, 2, false, false>);
   const int lds = io ? Ws<2, 2, true>::total : Ws<2, 2, false>::total;
   const int ud = MsgGeom<2, 2>::UD;
 #endif
   int dev = 0;
   E3_HIP_CHECK(hipGetDevice(&dev));
   static std::mutex mu;
-  static int cus_of[64][2][2];
+  static int cus_of[64][2][2][2];
   int cus = 0;
   {
     std::lock_guard<std::mutex> lock(mu);
     if (dev < 0 || dev >= 64) return E3_ERR_INVALID_ARG;
-    if (cus_of[dev][io][li] == 0) {  // once per device and storage type: the kernel needs its LDS image admitted
+    if (cus_of[dev][io][li][pb] == 0) {  // once per device, storage type and box kind: the kernel needs its LDS image admitted
       E3_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       int n = 0;
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      cus_of[dev][io][li] = n;
+      cus_of[dev][io][li][pb] = n;
     }
-    cus = cus_of[dev][io][li];
+    cus = cus_of[dev][io][li][pb];
   }
   int chunk = chunk_edges > 0 ? (chunk_edges + 15) / 16 * 16 : 256;
   const int64_t nchunks = (E + chunk - 1) / chunk;
@@ -1139,7 +1145,7 @@ int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, i
   nwg = std::max(8, (nwg + 7) / 8 * 8);
   const float* hmax = premix + (size_t)N * ud;  // per-node row maxima behind the table (e3_msg_premix)
   WsArgs a = {h, ldh, reinterpret_cast<const float4*>(pos4), src, dst, E, static_cast<const float*>(packed), premix, hmax,
-              in_scale, out, ldo, chunk};
+              in_scale, out, ldo, chunk, make_box(box)};
   void* args[] = {&a};
   if (hipLaunchKernel(kern, dim3(nwg), dim3(512), args, lds, stream) != hipSuccess) return E3_ERR_HIP;
   return E3_OK;

@@ -40,32 +40,65 @@ struct RgDev {
   int bits;
 };
 
+// periodic axes (the *_pbc entries; include/e3gnn.h): box length L = hi - lo, 1 / L, hL = L / 2 (+inf on an open axis: the
+// edge-test shift never fires there), bit a of `periodic` = axis a
+struct RgPbc {
+  float hi[3], L[3], invL[3], hL[3];
+  int periodic;
+};
+
+// a coordinate of a periodic axis wrapped into [lo, hi): w = p - L floor((p - lo) / L), then one correction step
+__device__ __forceinline__ float wrap_coord(const float p, const float lo, const float hi, const float L, const float invL) {
+  float w = __fsub_rn(p, __fmul_rn(L, floorf(__fmul_rn(__fsub_rn(p, lo), invL))));
+  if (w >= hi) w = __fsub_rn(w, L);
+  else if (w < lo) w = __fadd_rn(w, L);
+  return w;
+}
+template <bool PBC>
+__device__ __forceinline__ float3 load_pos(const float* __restrict__ pos, const int64_t o, const RgDev& g, const RgPbc& pb) {
+  float3 p = make_float3(pos[3 * o + 0], pos[3 * o + 1], pos[3 * o + 2]);
+  if constexpr (PBC) {
+    if (pb.periodic & 1) p.x = wrap_coord(p.x, g.lo[0], pb.hi[0], pb.L[0], pb.invL[0]);
+    if (pb.periodic & 2) p.y = wrap_coord(p.y, g.lo[1], pb.hi[1], pb.L[1], pb.invL[1]);
+    if (pb.periodic & 4) p.z = wrap_coord(p.z, g.lo[2], pb.hi[2], pb.L[2], pb.invL[2]);
+  }
+  return p;
+}
+
 __device__ __forceinline__ int cell_of(float p, float lo, float inv, int n) {
   float t = __fmul_rn(__fsub_rn(p, lo), inv);
   int c = (int)floorf(t);
   return c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
 }
 
+template <bool PBC>
 __global__ void rg_keys_kernel(const float* __restrict__ pos, int64_t N, RgDev g, uint32_t* __restrict__ keys,
-                               int32_t* __restrict__ idx) {
+                               int32_t* __restrict__ idx, const RgPbc pb) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
-  int cx = cell_of(pos[3 * i + 0], g.lo[0], g.inv[0], g.n[0]);
-  int cy = cell_of(pos[3 * i + 1], g.lo[1], g.inv[1], g.n[1]);
-  int cz = cell_of(pos[3 * i + 2], g.lo[2], g.inv[2], g.n[2]);
+  const float3 p = load_pos<PBC>(pos, i, g, pb);
+  int cx = cell_of(p.x, g.lo[0], g.inv[0], g.n[0]);
+  int cy = cell_of(p.y, g.lo[1], g.inv[1], g.n[1]);
+  int cz = cell_of(p.z, g.lo[2], g.inv[2], g.n[2]);
   keys[i] = morton3(cx, cy, cz);
   idx[i] = (int32_t)i;
 }
 
-// sorted positions (x,y,z,0), cell table [begin,end) per Morton code, list of non-empty cells
+// sorted positions (x,y,z,0; PBC: wrapped), cell table [begin,end) per Morton code, list of non-empty cells
+template <bool PBC>
 __global__ void rg_cells_kernel(const float* __restrict__ pos, int64_t N, const uint32_t* __restrict__ skeys,
                                 const int32_t* __restrict__ perm, float4* __restrict__ spos,
                                 int32_t* __restrict__ cbegin, int32_t* __restrict__ cend,
-                                int32_t* __restrict__ heads, int32_t* __restrict__ nheads) {
+                                int32_t* __restrict__ heads, int32_t* __restrict__ nheads, const RgDev g, const RgPbc pb) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
   const int32_t o = perm[i];
-  spos[i] = make_float4(pos[3 * (int64_t)o], pos[3 * (int64_t)o + 1], pos[3 * (int64_t)o + 2], 0.0f);
+  if constexpr (PBC) {
+    const float3 p = load_pos<PBC>(pos, o, g, pb);
+    spos[i] = make_float4(p.x, p.y, p.z, 0.0f);
+  } else {
+    spos[i] = make_float4(pos[3 * (int64_t)o], pos[3 * (int64_t)o + 1], pos[3 * (int64_t)o + 2], 0.0f);
+  }
   const uint32_t k = skeys[i];
   if (i == 0 || skeys[i - 1] != k) {
     cbegin[k] = (int32_t)i;
@@ -75,14 +108,16 @@ __global__ void rg_cells_kernel(const float* __restrict__ pos, int64_t N, const 
 }
 
 // One wave per non-empty cell.  FILL=false: deg[i] = #neighbours.  FILL=true: src[rowptr[i]..] = ids.
-template <bool FILL>
+// PBC: neighbour cells modulo n on periodic axes (duplicates dropped: n <= 2 names a cell more than once) and the one-step
+// minimum image in the edge test -- skipped by the cells whose 3x3x3 neighbourhood stays inside the box (wave-uniform).
+template <bool FILL, bool PBC>
 __global__ __launch_bounds__(64) void rg_scan_kernel(const float4* __restrict__ spos, const uint32_t* __restrict__ skeys,
                                                      const int32_t* __restrict__ cbegin,
                                                      const int32_t* __restrict__ cend,
                                                      const int32_t* __restrict__ heads,
                                                      const int32_t* __restrict__ nheads_p, RgDev g,
                                                      int32_t* __restrict__ deg, const int32_t* __restrict__ rowptr,
-                                                     int32_t* __restrict__ src) {
+                                                     int32_t* __restrict__ src, const RgPbc pb) {
   __shared__ float4 cand[kCandCap];   // x,y,z, id (bit pattern)
   __shared__ int rb[28], re[28], pre[29];
   const int lane = threadIdx.x;
@@ -98,12 +133,27 @@ __global__ __launch_bounds__(64) void rg_scan_kernel(const float4* __restrict__ 
     if (lane < 27) {
       int dx = lane % 3 - 1, dy = (lane / 3) % 3 - 1, dz = lane / 9 - 1;
       int x = cx + dx, y = cy + dy, z = cz + dz;
+      if constexpr (PBC) {
+        if (pb.periodic & 1) x = x < 0 ? x + g.n[0] : (x >= g.n[0] ? x - g.n[0] : x);
+        if (pb.periodic & 2) y = y < 0 ? y + g.n[1] : (y >= g.n[1] ? y - g.n[1] : y);
+        if (pb.periodic & 4) z = z < 0 ? z + g.n[2] : (z >= g.n[2] ? z - g.n[2] : z);
+      }
       if (x >= 0 && x < g.n[0] && y >= 0 && y < g.n[1] && z >= 0 && z < g.n[2]) {
         ncode = morton3(x, y, z);
         b = cbegin[ncode];
         e = cend[ncode];
         if (e <= b) ncode = 0xFFFFFFFFu;  // empty
       }
+    }
+    bool shift = false;  // some candidate may sit across a periodic face
+    if constexpr (PBC) {
+      bool dup = false;  // the same cell under a lower offset (n <= 2 on a periodic axis)
+      for (int m = 0; m < 27; ++m) dup |= (__shfl(ncode, m) == ncode) && (m < lane);
+      if (dup) ncode = 0xFFFFFFFFu;
+      // n >= 5 and a cell away from both faces: |x_i - x_j| < 2 cell widths + rounding < L / 2, the shift never fires
+      const int c[3] = {cx, cy, cz};
+      for (int a = 0; a < 3; ++a)
+        if ((pb.periodic >> a) & 1) shift |= g.n[a] < 5 || c[a] < 1 || c[a] > g.n[a] - 2;
     }
     int rank = 0;
     for (int m = 0; m < 27; ++m) {
@@ -148,7 +198,12 @@ __global__ __launch_bounds__(64) void rg_scan_kernel(const float4* __restrict__ 
           if (c < nc) {
             const float4 pc = cand[c];
             id = __float_as_int(pc.w);
-            const float dx = __fsub_rn(pi.x, pc.x), dy = __fsub_rn(pi.y, pc.y), dz = __fsub_rn(pi.z, pc.z);
+            float dx = __fsub_rn(pi.x, pc.x), dy = __fsub_rn(pi.y, pc.y), dz = __fsub_rn(pi.z, pc.z);
+            if (PBC && shift) {
+              dx = dx > pb.hL[0] ? __fsub_rn(dx, pb.L[0]) : (dx < -pb.hL[0] ? __fadd_rn(dx, pb.L[0]) : dx);
+              dy = dy > pb.hL[1] ? __fsub_rn(dy, pb.L[1]) : (dy < -pb.hL[1] ? __fadd_rn(dy, pb.L[1]) : dy);
+              dz = dz > pb.hL[2] ? __fsub_rn(dz, pb.L[2]) : (dz < -pb.hL[2] ? __fadd_rn(dz, pb.L[2]) : dz);
+            }
             const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
             ok = (id != i) && (d2 <= g.r2);
           }
@@ -222,8 +277,27 @@ int64_t e3_rg_workspace_bytes(int64_t N, const e3_rg_params* p) {
   return (int64_t)rg_ws(N, p->bits).total;
 }
 
-int e3_rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, int32_t* perm, float* sorted_pos4,
-                     int32_t* rowptr, void* workspace, int64_t workspace_bytes, void* stream) {
+}  // extern "C"
+
+// host: the device box of a periodic mask (validated: 2 r < L = hi - lo on every periodic axis)
+static int rg_pbc(const e3_rg_params* p, int periodic, RgPbc* pb) {
+  if (!p || periodic < 0 || periodic > 7) return E3_ERR_INVALID_ARG;
+  for (int a = 0; a < 3; ++a) {
+    const float L = p->hi[a] - p->lo[a];
+    const bool on = (periodic >> a) & 1;
+    if (on && !(L > 0.0f && 2.0f * p->r < L && L < 3.0e38f)) return E3_ERR_INVALID_ARG;
+    pb->hi[a] = p->hi[a];
+    pb->L[a] = on ? L : 0.0f;
+    pb->invL[a] = on ? 1.0f / L : 0.0f;
+    pb->hL[a] = on ? 0.5f * L : INFINITY;
+  }
+  pb->periodic = periodic;
+  return E3_OK;
+}
+
+template <bool PBC>
+static int rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, const RgPbc& pb, int32_t* perm,
+                         float* sorted_pos4, int32_t* rowptr, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!p || N < 0 || !rowptr || p->bits < 1 || p->bits > 8) return E3_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (N == 0) { E3_HIP_CHECK(hipMemsetAsync(rowptr, 0, 4, s)); return E3_OK; }
@@ -241,7 +315,7 @@ int e3_rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, int32_t
   int32_t* nheads = (int32_t*)(ws + w.nheads);
   int32_t* deg = (int32_t*)(ws + w.deg);
   const int nb = (int)((N + 255) / 256);
-  hipLaunchKernelGGL(rg_keys_kernel, dim3(nb), dim3(256), 0, s, pos, N, g, keys, idx);
+  hipLaunchKernelGGL(rg_keys_kernel<PBC>, dim3(nb), dim3(256), 0, s, pos, N, g, keys, idx, pb);
   size_t cb = w.cub_bytes;
   (void)hipGetLastError();
   E3_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(ws + w.cub, cb, keys, skeys, idx, perm, (int)N, 0, 3 * p->bits, s));
@@ -249,11 +323,11 @@ int e3_rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, int32_t
   E3_HIP_CHECK(hipMemsetAsync(cbegin, 0, ncode * 4, s));
   E3_HIP_CHECK(hipMemsetAsync(cend, 0, ncode * 4, s));
   E3_HIP_CHECK(hipMemsetAsync(nheads, 0, 4, s));
-  hipLaunchKernelGGL(rg_cells_kernel, dim3(nb), dim3(256), 0, s, pos, N, skeys, perm, (float4*)sorted_pos4, cbegin,
-                     cend, heads, nheads);
+  hipLaunchKernelGGL(rg_cells_kernel<PBC>, dim3(nb), dim3(256), 0, s, pos, N, skeys, perm, (float4*)sorted_pos4, cbegin,
+                     cend, heads, nheads, g, pb);
   const int grid = (int)std::min<int64_t>(N, 256 * 40);
-  hipLaunchKernelGGL(rg_scan_kernel<false>, dim3(grid), dim3(64), 0, s, (const float4*)sorted_pos4, skeys, cbegin,
-                     cend, heads, nheads, g, deg, (const int32_t*)nullptr, (int32_t*)nullptr);
+  hipLaunchKernelGGL((rg_scan_kernel<false, PBC>), dim3(grid), dim3(64), 0, s, (const float4*)sorted_pos4, skeys, cbegin,
+                     cend, heads, nheads, g, deg, (const int32_t*)nullptr, (int32_t*)nullptr, pb);
   E3_HIP_CHECK(hipMemsetAsync(deg + N, 0, 4, s));
   cb = w.cub_bytes;
   E3_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws + w.cub, cb, deg, rowptr, (int)(N + 1), s));
@@ -261,8 +335,9 @@ int e3_rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, int32_t
   return E3_OK;
 }
 
-int e3_rg_fill(int64_t N, const e3_rg_params* p, const float* sorted_pos4, const int32_t* rowptr, int32_t* src,
-               void* workspace, int64_t workspace_bytes, void* stream) {
+template <bool PBC>
+static int rg_fill(int64_t N, const e3_rg_params* p, const RgPbc& pb, const float* sorted_pos4, const int32_t* rowptr,
+                   int32_t* src, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!p || N < 0 || p->bits < 1 || p->bits > 8) return E3_ERR_INVALID_ARG;
   if (N == 0) return E3_OK;
   if (!sorted_pos4 || !rowptr || !workspace) return E3_ERR_INVALID_ARG;
@@ -273,11 +348,39 @@ int e3_rg_fill(int64_t N, const e3_rg_params* p, const float* sorted_pos4, const
   RgDev g = rg_dev(p);
   int32_t* deg = (int32_t*)(ws + w.deg);  // reused as the per-row fill cursor between chunks
   const int grid = (int)std::min<int64_t>(N, 256 * 40);
-  hipLaunchKernelGGL(rg_scan_kernel<true>, dim3(grid), dim3(64), 0, s, (const float4*)sorted_pos4,
+  hipLaunchKernelGGL((rg_scan_kernel<true, PBC>), dim3(grid), dim3(64), 0, s, (const float4*)sorted_pos4,
                      (const uint32_t*)(ws + w.skeys), (const int32_t*)(ws + w.cbegin), (const int32_t*)(ws + w.cend),
-                     (const int32_t*)(ws + w.heads), (const int32_t*)(ws + w.nheads), g, deg, rowptr, src);
+                     (const int32_t*)(ws + w.heads), (const int32_t*)(ws + w.nheads), g, deg, rowptr, src, pb);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
+}
+
+extern "C" {
+
+int e3_rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, int32_t* perm, float* sorted_pos4,
+                     int32_t* rowptr, void* workspace, int64_t workspace_bytes, void* stream) {
+  return rg_sort_count<false>(pos, N, p, RgPbc{}, perm, sorted_pos4, rowptr, workspace, workspace_bytes, stream);
+}
+
+int e3_rg_fill(int64_t N, const e3_rg_params* p, const float* sorted_pos4, const int32_t* rowptr, int32_t* src,
+               void* workspace, int64_t workspace_bytes, void* stream) {
+  return rg_fill<false>(N, p, RgPbc{}, sorted_pos4, rowptr, src, workspace, workspace_bytes, stream);
+}
+
+int e3_rg_sort_count_pbc(const float* pos, int64_t N, const e3_rg_params* p, int32_t periodic, int32_t* perm,
+                         float* sorted_pos4, int32_t* rowptr, void* workspace, int64_t workspace_bytes, void* stream) {
+  RgPbc pb;
+  const int st = rg_pbc(p, periodic, &pb);
+  if (st != E3_OK) return st;
+  return rg_sort_count<true>(pos, N, p, pb, perm, sorted_pos4, rowptr, workspace, workspace_bytes, stream);
+}
+
+int e3_rg_fill_pbc(int64_t N, const e3_rg_params* p, int32_t periodic, const float* sorted_pos4, const int32_t* rowptr,
+                   int32_t* src, void* workspace, int64_t workspace_bytes, void* stream) {
+  RgPbc pb;
+  const int st = rg_pbc(p, periodic, &pb);
+  if (st != E3_OK) return st;
+  return rg_fill<true>(N, p, pb, sorted_pos4, rowptr, src, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

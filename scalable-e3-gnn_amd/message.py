@@ -184,10 +184,13 @@ class FusedMessage:
                     profiling.end(f"msg_premix lmax={self.lmax} H={self.hidden} N={N} {io}", N, N * (esz * W + 4 * ud), t0,
                                   flops=2 * self.hidden * ud * N, kernel="e3::msg_premix_kernel" + mode)
             t0 = profiling.begin() if profiling.enabled() else None
-            _lib.check(lib.e3_msg_forward(hd, h.data_ptr(), h.stride(0), N, g.pos4.data_ptr(), src.data_ptr(),
-                                          dst.data_ptr(), E, packed.data_ptr(), sc, premix.data_ptr(),
-                                          out.data_ptr(), out.stride(0), code, 0 if cont is None else 1,
-                                          int(self.tiles_per_block), stream), "e3_msg_forward")
+            args = (hd, h.data_ptr(), h.stride(0), N, g.pos4.data_ptr(), src.data_ptr(), dst.data_ptr(), E,
+                    packed.data_ptr(), sc, premix.data_ptr(), out.data_ptr(), out.stride(0), code,
+                    0 if cont is None else 1, int(self.tiles_per_block))
+            if g.box is not None:  # periodic box: harmonics of the minimum-image edge vectors
+                _lib.check(lib.e3_msg_forward_pbc(*args, g.box_arg, stream), "e3_msg_forward_pbc")
+            else:
+                _lib.check(lib.e3_msg_forward(*args, stream), "e3_msg_forward")
             if t0 is not None:
                 # algorithmic bytes: h read once, positions, the two index columns, aggregated rows written once
                 nb = esz * N * W + 16 * N + 8 * E + 4 * N * W

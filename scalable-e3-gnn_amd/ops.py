@@ -32,12 +32,15 @@ def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True)
     d = torch.empty(E, dtype=torch.float32, device=dev) if (want_dist and want_edge) else None
     A = torch.empty((N, ny), dtype=torch.float32, device=dev) if want_node_attr else None
     fn = {1: "e3_edge_geometry", 2: "e3_edge_geometry_l2"}[lmax]
+    outs = (Y.data_ptr() if Y is not None else None, d.data_ptr() if d is not None else None,
+            A.data_ptr() if A is not None else None, _stream(pos4))
     with torch.cuda.device(dev):
-        _lib.check(getattr(_lib.load(), fn)(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
-                                                Y.data_ptr() if Y is not None else None,
-                                                d.data_ptr() if d is not None else None,
-                                                A.data_ptr() if A is not None else None, _stream(pos4)),
-                   "e3_edge_geometry")
+        if g.box is not None:  # periodic box: minimum-image edge vectors
+            _lib.check(getattr(_lib.load(), fn + "_pbc")(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
+                                                         g.box_arg, *outs), fn + "_pbc")
+        else:
+            _lib.check(getattr(_lib.load(), fn)(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, *outs),
+                       "e3_edge_geometry")
     return Y, d, A
 
 
@@ -63,9 +66,14 @@ class _EdgeGeometryFn(torch.autograd.Function):
         gY, gd, gA = c(gY), c(gd), c(gA)
         p = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(pos4.device):
-            _lib.check(_lib.load().e3_edge_geometry_backward(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
-                                                             ctx.lmax, p(gY), p(gd), p(gA), gpos.data_ptr(),
-                                                             _stream(pos4)), "e3_edge_geometry_backward")
+            if g.box is not None:
+                _lib.check(_lib.load().e3_edge_geometry_backward_pbc(
+                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.box_arg, p(gY), p(gd), p(gA),
+                    gpos.data_ptr(), _stream(pos4)), "e3_edge_geometry_backward_pbc")
+            else:
+                _lib.check(_lib.load().e3_edge_geometry_backward(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(),
+                                                                 N, ctx.lmax, p(gY), p(gd), p(gA), gpos.data_ptr(),
+                                                                 _stream(pos4)), "e3_edge_geometry_backward")
         return gpos, None, None
 
 
@@ -75,7 +83,8 @@ def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int
     (the fused message kernel computes the spherical harmonics of its edges itself).
 
     ``pos`` [N,3] (graph order, i.e. ``original_pos[g.perm]``): when given and it requires grad, the three outputs are
-    differentiable w.r.t. it (forces = -dE/dpos); otherwise the graph's own ``pos4`` is used."""
+    differentiable w.r.t. it (forces = -dE/dpos); otherwise the graph's own ``pos4`` is used.  A periodic graph
+    (``g.box``) takes the minimum image of every edge vector, so ``pos`` may be the unwrapped coordinates."""
     _check(g.pos4, "pos4")
     if pos is not None and _wants_grad(pos):
         _check(pos, "pos")

@@ -3,6 +3,10 @@
 Builder-defined stage (no reference code in the mount): particles are renumbered by
 a stable Morton sort, edges ``(src=j -> dst=i)`` exist iff ``i != j`` and ``|x_i-x_j|^2 <= r^2`` in
 explicitly rounded fp32, and the result is CSR-by-dst with ascending ``src``.
+
+Periodic boxes (``periodic=``, per axis): coordinates are wrapped into ``[lo, hi)`` and the edge test takes the minimum
+image (definitions in include/e3gnn.h, ``e3_rg_sort_count_pbc``); the graph then carries ``box`` and every edge stage
+downstream (geometry, message kernels, forces) uses the minimum-image edge vector.
 """
 from __future__ import annotations
 
@@ -27,6 +31,12 @@ class RadiusGraph:
     src: torch.Tensor       # [E] int32   ascending inside each row
     num_edges: int
     grid: tuple
+    box: tuple | None = None  # (L_x, L_y, L_z), 0.0 on an open axis; None = open box
+
+    @property
+    def box_arg(self):
+        """The ``box`` as the ``float[3]`` argument of the ``*_pbc`` entries (None for an open box)."""
+        return None if self.box is None else _lib.Float3(*self.box)
 
     @property
     def dst(self) -> torch.Tensor:
@@ -50,8 +60,37 @@ def grid_params(lo, hi, r) -> RgParams:
     return p
 
 
-def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None) -> RadiusGraph:
-    """pos [N,3] fp32 on a ROCm device.  ``lo``/``hi``: bounding box (computed from pos when omitted)."""
+def periodic_mask(periodic, r, lo, hi) -> int:
+    """Axis bit mask of ``periodic`` (bool or 3 bools), checked against the box: ``ValueError`` for a wrong-length mask, a
+    missing ``lo`` / ``hi`` or ``2 r >= L`` on a periodic axis (L = hi - lo in fp32)."""
+    if isinstance(periodic, (bool, int)) or periodic is None:
+        axes = [bool(periodic)] * 3
+    else:
+        axes = [bool(a) for a in periodic]
+        if len(axes) != 3:
+            raise ValueError(f"periodic must be a bool or 3 bools, got {len(axes)}")
+    mask = sum(1 << a for a in range(3) if axes[a])
+    if mask == 0:
+        return 0
+    if lo is None or hi is None:
+        raise ValueError("a periodic radius graph needs lo and hi: the box cannot be inferred from the points")
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("lo and hi must have 3 entries")
+    r32 = ctypes.c_float(r).value
+    for a in range(3):
+        if axes[a]:
+            L = ctypes.c_float(ctypes.c_float(hi[a]).value - ctypes.c_float(lo[a]).value).value
+            if not L > 0.0 or not 2.0 * r32 < L:
+                raise ValueError(f"periodic axis {a}: need 0 < 2 r < L = hi - lo, got r = {r}, L = {L}")
+    return mask
+
+
+def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False) -> RadiusGraph:
+    """pos [N,3] fp32 on a ROCm device.  ``lo``/``hi``: bounding box (computed from pos when omitted).
+
+    ``periodic``: bool or 3 bools; periodic axes wrap at ``[lo, hi)`` (then ``lo`` / ``hi`` are required and
+    ``2 r < hi - lo``).  Positions may lie outside the box on those axes; ``pos4`` holds them wrapped."""
+    mask = periodic_mask(periodic, r, lo, hi)
     if not pos.is_cuda:
         raise RuntimeError("radius_graph runs on ROCm tensors only; there is no CPU path")
     if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
@@ -64,6 +103,7 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None) -> RadiusGraph:
         hi = [h if h > l else l + 1.0 for l, h in zip(lo, hi)]
     lib = _lib.load()
     p = grid_params(lo, hi, r)
+    box = tuple(ctypes.c_float(p.hi[a] - p.lo[a]).value if (mask >> a) & 1 else 0.0 for a in range(3)) if mask else None
     dev = pos.device
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -74,8 +114,13 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None) -> RadiusGraph:
         perm = torch.empty(N, dtype=torch.int32, device=dev)
         pos4 = torch.empty((N, 4), dtype=torch.float32, device=dev)
         rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        _lib.check(lib.e3_rg_sort_count(pos.data_ptr(), N, ctypes.byref(p), perm.data_ptr(), pos4.data_ptr(),
-                                        rowptr.data_ptr(), ws.data_ptr(), wbytes, stream), "e3_rg_sort_count")
+        if mask:
+            _lib.check(lib.e3_rg_sort_count_pbc(pos.data_ptr(), N, ctypes.byref(p), mask, perm.data_ptr(),
+                                                pos4.data_ptr(), rowptr.data_ptr(), ws.data_ptr(), wbytes, stream),
+                       "e3_rg_sort_count_pbc")
+        else:
+            _lib.check(lib.e3_rg_sort_count(pos.data_ptr(), N, ctypes.byref(p), perm.data_ptr(), pos4.data_ptr(),
+                                            rowptr.data_ptr(), ws.data_ptr(), wbytes, stream), "e3_rg_sort_count")
         # the count / scan run in int32 (indices are int32 end to end): a graph with >= 2^31 edges wraps the running sum,
         # which shows as a negative or decreasing rowptr -- checked here with the same host read that fetches E
         if N > 0:
@@ -87,6 +132,10 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None) -> RadiusGraph:
                                "(sharding.SlabHalo) or reduce the cutoff")
         E = int(E)
         src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.e3_rg_fill(N, ctypes.byref(p), pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
-                                  ws.data_ptr(), wbytes, stream), "e3_rg_fill")
-    return RadiusGraph(perm, pos4, rowptr, src[:E], E, (tuple(p.n), p.bits))
+        if mask:
+            _lib.check(lib.e3_rg_fill_pbc(N, ctypes.byref(p), mask, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
+                                          ws.data_ptr(), wbytes, stream), "e3_rg_fill_pbc")
+        else:
+            _lib.check(lib.e3_rg_fill(N, ctypes.byref(p), pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
+                                      ws.data_ptr(), wbytes, stream), "e3_rg_fill")
+    return RadiusGraph(perm, pos4, rowptr, src[:E], E, (tuple(p.n), p.bits), box)
