@@ -211,6 +211,31 @@ int e3_split_edges(const int32_t* rowptr, const int32_t* src, const uint8_t* is_
                    int32_t* rowptr_kept, int32_t* src_kept, int32_t* dst_kept, int32_t* src_interior, int32_t* dst_interior,
                    int32_t* src_boundary, int32_t* dst_boundary, int32_t* counts, void* workspace, void* stream);
 
+/* Periodic halo (sharding.GridHalo with `periodic`): wrap the owned positions and pick the particles each ghost image
+ * needs -- a two-call pair in the style of e3_rg_sort_count / e3_rg_fill.
+ *   wrap   : on the axes of `periodic` (bits 0..2) with the domain lo[3] / hi[3] (host fp32): exactly the wrap of
+ *            e3_rg_sort_count_pbc (L = fl32(hi_a - lo_a), invL = fl32(1 / L)); open axes unchanged -> pos_wrapped [n,3].
+ *   entry  : entries[e] (host, n_entries <= 26) = {lo[3], hi[3], shift[3]} fp32; particle i is in entry e iff
+ *            lo[a] <= w_i[a] < hi[a] on every axis (fp32 compares of the wrapped position).
+ *   output : idx [total] int32 and ghost_pos [total,3] = fl32(pos_wrapped[idx] + shift), grouped by entry, ascending particle
+ *            ids inside a group (the order of nonzero() on an entry-major [n_entries, n] mask); counts[e] (device) = the
+ *            size of group e, total = sum of counts.
+ * Call sequence: e3_halo_select_workspace_bytes -> e3_halo_select_count (pos_wrapped, counts) -> read counts
+ *   -> e3_halo_select_fill (idx, ghost_pos; the same workspace, entries and wrap arguments, `total` = the capacity of idx).
+ * E3_ERR_INVALID_ARG before any launch for n_entries outside [0, 26], a non-finite or empty lo / hi, periodic outside [0, 7],
+ * 2 r >= L on a periodic axis, a NaN entry bound or a non-finite shift, or n * n_entries >= 2^31 - 1. */
+#define E3_HALO_MAX_ENTRIES 26
+typedef struct e3_halo_entry {
+  float lo[3], hi[3], shift[3];
+} e3_halo_entry;
+int64_t e3_halo_select_workspace_bytes(int64_t n, int n_entries);
+int e3_halo_select_count(const float* pos, int64_t n, const float lo[3], const float hi[3], int32_t periodic, float r,
+                         const e3_halo_entry* entries, int n_entries, float* pos_wrapped, int32_t* counts, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+int e3_halo_select_fill(const float* pos_wrapped, int64_t n, const float lo[3], const float hi[3], int32_t periodic, float r,
+                        const e3_halo_entry* entries, int n_entries, int64_t total, int32_t* idx, float* ghost_pos,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =================================================================================================
  * General SH tensor product, l <= 2 (builder-defined generalisation of the reference operator, which
  * hard-asserts lmax == 1, l1_tensor_prod.py:13-14).

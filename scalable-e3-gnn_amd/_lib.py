@@ -23,6 +23,12 @@ _lib = None
 VoidP4 = c_void_p * 4
 Float3 = ctypes.c_float * 3  # a host float[3] argument (periodic box lengths)
 
+
+class HaloEntry(ctypes.Structure):
+    """``e3_halo_entry`` of include/e3gnn.h: one ghost image's selection bounds and shift (fp32)."""
+    _fields_ = [("lo", ctypes.c_float * 3), ("hi", ctypes.c_float * 3), ("shift", ctypes.c_float * 3)]
+
+
 # name -> (restype, argtypes); mirrors include/e3gnn.h one to one
 SIGNATURES = {
     "e3_abi_version": (c_int, []),
@@ -52,6 +58,11 @@ SIGNATURES = {
     "e3_split_edges_workspace_bytes": (c_int64, [c_int64]),
     "e3_split_edges": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e3_halo_select_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "e3_halo_select_count": (c_int, [c_void_p, c_int64, Float3, Float3, c_int32, ctypes.c_float, c_void_p, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_halo_select_fill": (c_int, [c_void_p, c_int64, Float3, Float3, c_int32, ctypes.c_float, c_void_p, c_int, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "e3_tp_plan_create": (c_int, [POINTER(c_int32), c_int, c_int, POINTER(c_int32), c_int, POINTER(c_void_p)]),
     "e3_tp_plan_destroy": (c_int, [c_void_p]),
     "e3_tp_in1_dim": (c_int, [c_void_p]),

@@ -74,6 +74,14 @@ struct PbcBox {
 __device__ __forceinline__ float min_image(const float d, const float L, const float invL) {
   return __fsub_rn(d, __fmul_rn(L, rintf(__fmul_rn(d, invL))));
 }
+// a coordinate of a periodic axis wrapped into [lo, hi): w = p - L floor((p - lo) / L), then one correction step
+// (include/e3gnn.h above e3_rg_sort_count_pbc; shared by the graph builder and the halo's image selection)
+__device__ __forceinline__ float wrap_coord(const float p, const float lo, const float hi, const float L, const float invL) {
+  float w = __fsub_rn(p, __fmul_rn(L, floorf(__fmul_rn(__fsub_rn(p, lo), invL))));
+  if (w >= hi) w = __fsub_rn(w, L);
+  else if (w < lo) w = __fadd_rn(w, L);
+  return w;
+}
 // edge vector x_src - x_dst of the geometry kernels; PBC: its minimum image (the rint form, so unwrapped coordinates work too)
 template <bool PBC>
 __device__ __forceinline__ void edge_rel(const float4 pj, const float4 pi, const PbcBox& box, float& rx, float& ry,

@@ -47,13 +47,6 @@ struct RgPbc {
   int periodic;
 };
 
-// a coordinate of a periodic axis wrapped into [lo, hi): w = p - L floor((p - lo) / L), then one correction step
-__device__ __forceinline__ float wrap_coord(const float p, const float lo, const float hi, const float L, const float invL) {
-  float w = __fsub_rn(p, __fmul_rn(L, floorf(__fmul_rn(__fsub_rn(p, lo), invL))));
-  if (w >= hi) w = __fsub_rn(w, L);
-  else if (w < lo) w = __fadd_rn(w, L);
-  return w;
-}
 template <bool PBC>
 __device__ __forceinline__ float3 load_pos(const float* __restrict__ pos, const int64_t o, const RgDev& g, const RgPbc& pb) {
   float3 p = make_float3(pos[3 * o + 0], pos[3 * o + 1], pos[3 * o + 2]);

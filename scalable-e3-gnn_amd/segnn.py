@@ -88,7 +88,8 @@ class SEGNNLayer(nn.Module):
         """-> (h_next, operand scale of h_next | None).  ``halo`` / ``split`` (sharding.GridHalo / SplitGraph): the layer
         refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges."""
         if (halo is not None or split is not None) and g.box is not None:
-            raise NotImplementedError("a periodic graph cannot be sharded (halo / split): periodic halos are not built")
+            raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
+                                      "ghost images of GridHalo(..., periodic=...)")
         inference = not (torch.is_grad_enabled() and _needs_grad(self, h))
         if not inference and self.fused and not SEGNNLayer._warned_unfused:
             # the switch is visible: the fused MFMA kernels are inference kernels (no backward); a call that needs a gradient
@@ -199,7 +200,8 @@ class SEGNN(nn.Module):
         are meaningful.  ``split`` (``halo.split_graph(g)``): edges into ghost rows dropped and the rest split into
         interior / boundary lists so that the refresh overlaps the interior edges."""
         if (halo is not None or split is not None) and g.box is not None:
-            raise NotImplementedError("a periodic graph cannot be sharded (halo / split): periodic halos are not built")
+            raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
+                                      "ghost images of GridHalo(..., periodic=...)")
         if split is not None:
             g = split.graph
         if geometry is not None:
