@@ -2,10 +2,13 @@
 
 Builder-defined (the reference has no distributed code).  The domain is cut into a grid of axis-aligned
 boxes, one per rank (``GridHalo``); a node's messages need neighbours within the cutoff ``r``, so each rank also holds
-*ghost* copies of the particles of the (up to 26) adjacent boxes that lie within ``r`` of its own box:
+*ghost* copies of the particles of the (up to 26) adjacent boxes that lie within ``r`` of its own box.  The halo is a list of
+*entries* ``(peer q, offset d, translation t)`` (``image_entries``), one per adjacent box: ``coords(me) + d`` is the adjacent
+box, wrapped modulo ``dims`` on periodic axes, and ``t`` (whole box lengths per axis) moves q's box next to mine at offset
+``d``.  In an open box every entry has ``t = 0`` and its own peer, in ascending rank order.
 
-  * ``setup``      — once per graph build: boundary particles (positions + input features) go to the adjacent boxes; the
-                     local cloud is ``[owned | ghosts from neighbour 0 | ghosts from neighbour 1 | ...]``.
+  * ``setup``      — once per graph build: the owner of a boundary particle sends it (position + input features) to every
+                     entry whose box + r holds it; the local cloud is ``[owned | ghosts of entry 0 | of entry 1 | ...]``.
   * ``split_graph``— once per graph build: edges INTO ghost rows are dropped (their sums would be thrown away), the rest is
                      split into *interior* edges (owned src: computable before the layer's exchange has landed) and
                      *boundary* edges (ghost src).  On a GPU one HIP launch pair classifies and compacts (``e3_split_edges``).
@@ -23,23 +26,25 @@ Two layouts are built on it:
                      for slabs of width 1/8; tests/test_sharding_gloo.py prints both.  (Equal-COUNT Morton ranges for a
                      non-uniform cloud are not implemented: boxes are equal-volume.)
 
-Periodic boxes (``GridHalo(..., periodic=)``, per axis, as ``radius_graph(periodic=)``): the halo is made of *ghost
-images*.  An entry ``(peer q, offset d)`` replaces a neighbour: ``coords(me) + d`` is wrapped modulo ``dims`` on the periodic
-axes, and the entry's translation ``t`` (whole box lengths per axis) moves q's box next to mine at offset ``d``.  The owner of
-a particle sends it, shifted by ``-t``, to every image box whose r-neighbourhood holds it, so the same peer can appear several
-times with different shifts, and with one or two boxes along an axis a rank is its own neighbour (self entries are served
-by local copies, never by ``torch.distributed``).  ``setup`` wraps the owned positions (the graph builder's formula) and
-the local graph is an OPEN graph over ``[wrapped owned | ghost images]``: its edge vectors are the minimum images, and
-``split_graph`` / ``start`` / ``finish`` work unchanged.  Rounding contract: the sharded periodic graph has exactly the edges
-of ``radius_graph(periodic=True)`` over the whole cloud when the image shifts are exact in fp32 (e.g. dyadic coordinates
-with a dyadic box length); otherwise a pair within about 1 ulp of the cutoff may differ, and edge vectors agree to fp32
-rounding.  On ROCm tensors the selection is one HIP launch pair (``csrc/e3_halo.hip``); on CPU tensors (gloo rehearsal) a
-torch restatement of the same predicate and order (``select_images_torch``).
+Open box: an entry's ghosts are the owned particles in ``[blo - r, bhi + r)`` of the peer's box, bounds in the positions'
+dtype, one torch mask and ONE ``nonzero`` over all entries; positions and features keep their dtypes.
 
-Only point-to-point traffic between adjacent boxes (``batch_isend_irecv`` = grouped ncclSend/ncclRecv on RCCL: every pair
-talks over its own xGMI link; no ring, no collective over all ranks).  Host syncs: two per graph build (one ``nonzero`` over
-all neighbours at once -- periodic: one read of the selection's counts --, one read of the incoming counts), one per graph in
-``split_graph`` (three edge counts), none per layer.
+Periodic boxes (``GridHalo(..., periodic=)``, per axis, as ``radius_graph(periodic=)``): an offset never leaves the grid on
+a periodic axis, so with one or two boxes along it the same peer appears in several entries with different shifts, and a
+rank can be its own peer.  The owner sends a particle, shifted by ``-t``, to every image box whose r-neighbourhood holds it.
+``setup`` wraps the owned positions (the graph builder's formula) and the local graph is an OPEN graph over
+``[wrapped owned | ghost images]``: its edge vectors are the minimum images, and ``split_graph`` / ``start`` / ``finish``
+work unchanged.  Rounding contract: the sharded periodic graph has exactly the edges of ``radius_graph(periodic=True)`` over
+the whole cloud when the image shifts are exact in fp32 (e.g. dyadic coordinates with a dyadic box length); otherwise a pair
+within about 1 ulp of the cutoff may differ, and edge vectors agree to fp32 rounding.  On ROCm tensors the selection is one
+HIP launch pair (``csrc/e3_halo.hip``); on CPU tensors (gloo rehearsal) a torch restatement of the same predicate and order
+(``select_images_torch``).
+
+Self entries are served by local copies, never by ``torch.distributed`` (world 1 needs no process group).  The others are
+point-to-point traffic between adjacent boxes (``batch_isend_irecv`` = grouped ncclSend/ncclRecv on RCCL: every pair talks
+over its own xGMI link; no ring, no collective over all ranks), posted per peer in tag order.  Host syncs: two per graph
+build (the selection -- open: the ``nonzero``; periodic: one read of the counts --, one read of the outgoing and incoming
+counts), one per graph in ``split_graph`` (three edge counts), none per layer.
 """
 from __future__ import annotations
 
@@ -53,8 +58,8 @@ import torch.distributed as dist
 
 from .radius_graph import periodic_mask
 
-# neighbour offsets; the index of the RECEIVER-side offset is the P2POp tag of a periodic entry's messages (gloo matches by
-# tag, RCCL by order: the ops with one peer are posted in tag order, so both pair the entries of a peer correctly)
+# neighbour offsets; the index of the RECEIVER-side offset is the P2POp tag of an entry's messages (gloo matches by tag, RCCL
+# by order: the ops with one peer are posted in tag order, so both pair the entries of a peer correctly)
 OFFSETS = list(itertools.product((-1, 0, 1), repeat=3))
 
 
@@ -115,6 +120,12 @@ def _wrap_torch(pos, lo, hi, mask):
     return out
 
 
+def _in_boxes(pos, elo, ehi):
+    """(entry, index) of every position inside ``[elo_e, ehi_e)`` on all three axes, entry-major, then by index."""
+    m = ((pos[None, :, :] >= elo[:, None, :]) & (pos[None, :, :] < ehi[:, None, :])).all(-1)   # [ne, n]
+    return m.nonzero(as_tuple=True)
+
+
 def select_images_torch(pos, lo, hi, periodic, r, entries):
     """Torch restatement of ``e3_halo_select_count`` / ``_fill`` (any device): -> (pos_wrapped [n,3] fp32, idx [total]
     int64, counts (list of int), ghost_pos [total,3] fp32).  ``entries``: ``[(lo3, hi3, shift3), ...]`` fp32 values."""
@@ -129,8 +140,7 @@ def select_images_torch(pos, lo, hi, periodic, r, entries):
     elo = torch.tensor([e[0] for e in entries], dtype=torch.float32, device=dev)
     ehi = torch.tensor([e[1] for e in entries], dtype=torch.float32, device=dev)
     esh = torch.tensor([e[2] for e in entries], dtype=torch.float32, device=dev)
-    m = ((pw[None, :, :] >= elo[:, None, :]) & (pw[None, :, :] < ehi[:, None, :])).all(-1)   # [ne, n], entry-major
-    ent, idx = m.nonzero(as_tuple=True)
+    ent, idx = _in_boxes(pw, elo, ehi)
     counts = [int(v) for v in torch.bincount(ent, minlength=ne).tolist()]
     return pw, idx, counts, pw[idx] + esh[ent]
 
@@ -184,11 +194,10 @@ class SplitGraph:
 class GridHalo:
     """Ghost-cell halo of a ``dims = (px, py, pz)`` grid of equal boxes covering ``[lo, hi)``; rank = (ix py + iy) pz + iz.
 
-    ``periodic`` (bool or 3 bools, validated by ``radius_graph.periodic_mask``): those axes wrap at ``[lo, hi)`` and the halo
-    is built from ghost images (module docstring).  ``images`` lists the entries ``(peer, d, t)``; in periodic mode
-    ``send_counts`` / ``recv_counts`` are per entry, ``neighbours`` stays the sorted distinct peers other than this rank.
-    Positions must then be fp32; ``setup`` returns the owned ones wrapped.  Works without a process group at world 1
-    (dims (1, 1, 1) with periodic axes: a pure self-halo)."""
+    ``images`` lists the halo's entries ``(peer, d, t)`` (module docstring); ``send_counts`` / ``recv_counts`` are per
+    entry and ``neighbours`` is the sorted distinct peers other than this rank.  ``periodic`` (bool or 3 bools, validated by
+    ``radius_graph.periodic_mask``): those axes wrap at ``[lo, hi)``; positions must then be fp32, and ``setup`` returns the
+    owned ones wrapped.  Works without a process group at world 1 (dims (1, 1, 1) with periodic axes: a pure self-halo)."""
 
     def __init__(self, dims, lo, hi, group=None, periodic=False):
         self.group = group
@@ -201,11 +210,17 @@ class GridHalo:
         self.hi = [float(v) for v in hi]
         self.n_owned = 0
         self.bytes_last_exchange = 0
-        self.neighbours = []       # adjacent ranks, ascending
-        self.periodic = periodic_mask(periodic, 0.0, self.lo, self.hi)   # axis bit mask; 0 = open box (the original path)
+        self.periodic = periodic_mask(periodic, 0.0, self.lo, self.hi)   # axis bit mask; 0 = open box
         self._axes = tuple(bool((self.periodic >> a) & 1) for a in range(3))
-        self.images = []           # entries (peer, d, t)
-        self._set_boxes()
+        ent = self.images = image_entries(self.dims, self.lo, self.hi, self._axes, self.rank)
+        self.neighbours = sorted({q for q, _, _ in ent if q != self.rank})
+        at = {d: e for e, (_, d, _) in enumerate(ent)}
+        # self entry e receives what this rank sends for its entry (me, -d)
+        self._self_pairs = [(e, at[tuple(-v for v in d)]) for e, (q, d, _) in enumerate(ent) if q == self.rank]
+        self._remote = [e for e, (q, _, _) in enumerate(ent) if q != self.rank]
+        # per peer, in tag order (the receiver-side offset: -d for what I send, d for what I receive)
+        self._send_ops = sorted((ent[e][0], OFFSETS.index(tuple(-v for v in ent[e][1])), e) for e in self._remote)
+        self._recv_ops = sorted((ent[e][0], OFFSETS.index(ent[e][1]), e) for e in self._remote)
 
     # -- geometry -------------------------------------------------------------------------------------
     def coords(self, rank):
@@ -228,27 +243,6 @@ class GridHalo:
             idx.append(((pos[:, a] - self.lo[a]) / w).floor().long().clamp_(0, self.dims[a] - 1))
         return (idx[0] * self.dims[1] + idx[1]) * self.dims[2] + idx[2]
 
-    def _set_boxes(self):
-        me = self.coords(self.rank)
-        nb = set()
-        for d in itertools.product((-1, 0, 1), repeat=3):
-            c = [me[a] + d[a] for a in range(3)]
-            if d != (0, 0, 0) and all(0 <= c[a] < self.dims[a] for a in range(3)):
-                nb.add((c[0] * self.dims[1] + c[1]) * self.dims[2] + c[2])
-        self.neighbours = sorted(nb)
-        self.images = image_entries(self.dims, self.lo, self.hi, self._axes, self.rank)
-        if self.periodic:
-            ent = self.images
-            self.neighbours = sorted({q for q, _, _ in ent if q != self.rank})
-            at = {d: e for e, (_, d, _) in enumerate(ent)}
-            # self entry e receives what this rank sends for its entry (me, -d)
-            self._self_pairs = [(e, at[tuple(-v for v in d)]) for e, (q, d, _) in enumerate(ent) if q == self.rank]
-            remote = [e for e, (q, _, _) in enumerate(ent) if q != self.rank]
-            self._remote = remote
-            # per peer, in tag order (the receiver-side offset: -d for what I send, d for what I receive)
-            self._send_ops = sorted((ent[e][0], OFFSETS.index(tuple(-v for v in ent[e][1])), e) for e in remote)
-            self._recv_ops = sorted((ent[e][0], OFFSETS.index(ent[e][1]), e) for e in remote)
-
     def _selection(self, r):
         """fp32 selection bounds and shift of every entry, sender side: the owned particles in ``[blo + t - r, bhi + t + r)``
         of the peer's box go to it, at ``p - t``."""
@@ -259,136 +253,82 @@ class GridHalo:
                         [-t[a] if t[a] else 0.0 for a in range(3)]))
         return out
 
+    def _select(self, pos, r):
+        """-> (owned positions as the local cloud holds them, indices sent [total], per-entry counts, positions sent), the
+        particles grouped by entry, ascending within an entry."""
+        if self.periodic:
+            return select_images(pos, self.lo, self.hi, self._axes, r, self._selection(r))
+        if not self.images:
+            return pos, torch.empty(0, dtype=torch.long, device=pos.device), [], pos[:0]
+        # bounds in pos.dtype: per axis a superset of the r-ball
+        blo = torch.tensor([self.box(q)[0] for q, _, _ in self.images], dtype=pos.dtype, device=pos.device)
+        bhi = torch.tensor([self.box(q)[1] for q, _, _ in self.images], dtype=pos.dtype, device=pos.device)
+        ent, idx = _in_boxes(pos, blo - r, bhi + r)
+        return pos, idx, torch.bincount(ent, minlength=len(self.images)), pos[idx]
+
     # -- p2p helpers ----------------------------------------------------------------------------------
-    def _post_images(self, sends, recvs):
-        """Periodic mode: grouped send / recv of the remote entries (``sends[e]`` / ``recvs[e]`` by entry index), per peer
-        in tag order; empty messages are skipped on both ends."""
-        ops = []
-        for q, tag, e in self._send_ops:
-            if sends[e].numel():
-                ops.append(dist.P2POp(dist.isend, sends[e], q, self.group, tag=tag))
-        for q, tag, e in self._recv_ops:
-            if recvs[e].numel():
-                ops.append(dist.P2POp(dist.irecv, recvs[e], q, self.group, tag=tag))
+    def _post(self, sends, recvs):
+        """Grouped send / recv of the remote entries (``sends[e]`` / ``recvs[e]`` by entry index), per peer in tag order;
+        empty messages are skipped on both ends (the sizes were agreed on in ``setup``)."""
+        ops = [dist.P2POp(dist.isend, sends[e], q, self.group, tag=tag) for q, tag, e in self._send_ops if sends[e].numel()]
+        ops += [dist.P2POp(dist.irecv, recvs[e], q, self.group, tag=tag) for q, tag, e in self._recv_ops if recvs[e].numel()]
         return dist.batch_isend_irecv(ops) if ops else []
 
-    def _start_images(self, sends, recvs):
-        """Periodic mode: serve the self entries by local copies, post the others -> (kind, works, (host recvs, recvs))."""
+    def _gloo(self):
+        return dist.get_backend(self.group) == "gloo"
+
+    def _start(self, sends, recvs):
+        """Serve the self entries by local copies and post the remote ones -> ``(works, staged, posted)`` for ``_wait``.
+        gloo has no device transport: device tensors are staged through host memory (rehearsal mode only); ``staged`` lists
+        the (device recv, host recv) pairs and ``posted`` keeps the send buffers referenced until the wait."""
         for e, m in self._self_pairs:
             recvs[e].copy_(sends[m])
-        if self._remote and self._staged(sends[self._remote[0]]):
-            hs = {e: sends[e].cpu() for e in self._remote}
-            hr = {e: torch.empty(recvs[e].shape, dtype=recvs[e].dtype) for e in self._remote}
-            return "staged", self._post_images(hs, hr), ([hr[e] for e in self._remote], [recvs[e] for e in self._remote])
-        return "direct", (self._post_images(sends, recvs) if self._remote else []), ([], [])
+        if not self._remote:
+            return [], [], sends
+        staged = []
+        if sends[0].is_cuda and self._gloo():
+            sends = {e: sends[e].cpu() for e in self._remote}
+            host = {e: torch.empty(recvs[e].shape, dtype=recvs[e].dtype) for e in self._remote}
+            staged = [(recvs[e], host[e]) for e in self._remote]
+            recvs = host
+        return self._post(sends, recvs), staged, sends
 
-    def _sendrecv_images(self, sends, recvs):
-        kind, works, (hr, rr) = self._start_images(sends, recvs)
+    @staticmethod
+    def _wait(works, staged, posted):
         for w in works:
             w.wait()
-        for d, s in zip(rr, hr):
+        for d, s in staged:
             d.copy_(s)
-
-    def _staged(self, t):
-        """gloo has no device transport: device tensors are staged through host memory (rehearsal mode only)."""
-        return t.is_cuda and dist.get_backend(self.group) == "gloo"
-
-    def _post(self, sends, recvs):
-        """Grouped send / recv with every neighbour (empty messages are skipped on both ends: the sizes were agreed on in
-        ``setup``)."""
-        ops = []
-        for q, s, r in zip(self.neighbours, sends, recvs):
-            if s.numel():
-                ops.append(dist.P2POp(dist.isend, s, q, self.group))
-            if r.numel():
-                ops.append(dist.P2POp(dist.irecv, r, q, self.group))
-        return dist.batch_isend_irecv(ops) if ops else []
-
-    def _sendrecv(self, sends, recvs):
-        if sends and self._staged(sends[0]):
-            hs, hr = [t.cpu() for t in sends], [t.cpu() for t in recvs]
-            for w in self._post(hs, hr):
-                w.wait()
-            for d, s in zip(recvs, hr):
-                d.copy_(s)
-            return
-        for w in self._post(sends, recvs):
-            w.wait()
 
     # -- once per graph build -------------------------------------------------------------------------
     def setup(self, pos: torch.Tensor, feats: torch.Tensor, r: float):
-        """pos [n,3], feats [n,F] of the owned particles -> (local_pos, local_feats) with the ghosts of every adjacent box
-        appended in neighbour order.  Positions and features travel in their own dtypes.
-        Periodic mode: ``[wrapped owned | ghost images]``, the images in entry order (``images``)."""
-        if self.periodic:
-            return self._setup_images(pos, feats, r)
-        dev = pos.device
-        n = pos.shape[0]
-        self.n_owned = n
-        nn = len(self.neighbours)
-        w = min((self.hi[a] - self.lo[a]) / self.dims[a] for a in range(3) if self.dims[a] > 1) if nn else float("inf")
-        if nn and r > w:
-            raise ValueError(f"cutoff {r} exceeds the box width {w}: ghosts would come from beyond the adjacent boxes")
-        if nn:
-            # my particles within r (per axis: a superset of the r-ball) of each adjacent box -- one mask, ONE nonzero
-            blo = torch.tensor([self.box(q)[0] for q in self.neighbours], dtype=pos.dtype, device=dev)   # [nn, 3]
-            bhi = torch.tensor([self.box(q)[1] for q in self.neighbours], dtype=pos.dtype, device=dev)
-            m = ((pos[None, :, :] >= blo[:, None, :] - r) & (pos[None, :, :] < bhi[:, None, :] + r)).all(-1)   # [nn, n]
-            nbr, idx = m.nonzero(as_tuple=True)                     # sorted by neighbour, then particle  (host sync #1)
-            cnt_out = torch.bincount(nbr, minlength=nn)
-        else:
-            idx = torch.empty(0, dtype=torch.long, device=dev)
-            cnt_out = torch.zeros(0, dtype=torch.int64, device=dev)
-        cnt_in = torch.zeros_like(cnt_out)
-        self._sendrecv([cnt_out[i:i + 1] for i in range(nn)], [cnt_in[i:i + 1] for i in range(nn)])
-        both = torch.stack([cnt_out, cnt_in]).tolist() if nn else [[], []]                               # host sync #2
-        self.send_counts, self.recv_counts = [int(v) for v in both[0]], [int(v) for v in both[1]]
-        self.sel = idx                                   # original indices of the particles sent, grouped by neighbour
-        self._send_idx = idx
-        out = []
-        ng = sum(self.recv_counts)
-        for t in (pos, feats):
-            sends = list(t[idx].contiguous().split(self.send_counts)) if nn else []
-            ghosts = torch.empty((ng, t.shape[1]), dtype=t.dtype, device=dev)
-            self._sendrecv(sends, list(ghosts.split(self.recv_counts)) if nn else [])
-            out.append(torch.cat([t, ghosts], 0))
-        self.n_ghost = ng
-        self._recv_idx = torch.arange(n, n + ng, device=dev)
-        return out[0], out[1]
-
-    def _setup_images(self, pos, feats, r):
+        """pos [n,3], feats [n,F] of the owned particles -> (local_pos, local_feats) = ``[owned | ghosts]``, the ghosts in
+        entry order (``images``).  Positions and features travel in their own dtypes (periodic: positions fp32, the owned
+        ones wrapped)."""
         check_cutoff(self.dims, self.lo, self.hi, self._axes, r)        # ValueError before any transfer
         dev = pos.device
         n = pos.shape[0]
-        self.n_owned = n
+        pos, idx, cnt, gpos = self._select(pos, r)                        # host sync #1
+        # the counts: on the CPU for gloo, else on the device; self entries are local copies; ONE read of [out | in]
+        cdev = dev if self._remote and not self._gloo() else torch.device("cpu")
+        co = torch.as_tensor(cnt, dtype=torch.int64).to(cdev)
+        ci = torch.zeros_like(co)
+        for w in self._post(co[:, None], ci[:, None]):
+            w.wait()
+        both = torch.cat([co, ci]).tolist()                                # host sync #2
         ne = len(self.images)
-        pw, idx, cnt_out, gpos = select_images(pos, self.lo, self.hi, self._axes, r, self._selection(r))  # host sync #1
-        cnt_in = [0] * ne
+        self.send_counts, self.recv_counts = both[:ne], both[ne:]
         for e, m in self._self_pairs:
-            cnt_in[e] = cnt_out[m]
-        if self._remote:
-            cdev = torch.device("cpu") if dist.get_backend(self.group) == "gloo" else dev
-            co = torch.tensor(cnt_out, dtype=torch.int64, device=cdev)
-            ci = torch.zeros(ne, dtype=torch.int64, device=cdev)
-            works = self._post_images(list(co.split(1)), list(ci.split(1)))
-            for w in works:
-                w.wait()
-            got = ci.tolist()                                                                   # host sync #2
-            for e in self._remote:
-                cnt_in[e] = int(got[e])
-        self.send_counts, self.recv_counts = cnt_out, cnt_in
+            self.recv_counts[e] = self.send_counts[m]
+        self.n_owned, self.n_ghost = n, sum(self.recv_counts)
         self.sel = idx                         # original indices of the particles sent, grouped by entry
         self._send_idx = idx
-        ng = sum(cnt_in)
         out = []
-        for t, send in ((pw, gpos), (feats, None)):
-            if send is None:
-                send = t[idx]
-            ghosts = torch.empty((ng, t.shape[1]), dtype=t.dtype, device=dev)
-            self._sendrecv_images(list(send.split(cnt_out)), list(ghosts.split(cnt_in)))
+        for t, send in ((pos, gpos), (feats, feats[idx])):
+            ghosts = torch.empty((self.n_ghost, t.shape[1]), dtype=t.dtype, device=dev)
+            self._wait(*self._start(list(send.split(self.send_counts)), list(ghosts.split(self.recv_counts))))
             out.append(torch.cat([t, ghosts], 0))
-        self.n_ghost = ng
-        self._recv_idx = torch.arange(n, n + ng, device=dev)
+        self._recv_idx = torch.arange(n, n + self.n_ghost, device=dev)
         return out[0], out[1]
 
     def renumber(self, perm: torch.Tensor):
@@ -450,29 +390,17 @@ class GridHalo:
         D = h.shape[1]
         recv = torch.empty((self.n_ghost, D), dtype=h.dtype, device=h.device)
         send = h[self._send_idx].contiguous()
-        sends, recvs = list(send.split(self.send_counts)), list(recv.split(self.recv_counts))
-        if self.periodic:
-            # self entries: local copies (not counted as exchanged bytes); the rest over torch.distributed
-            self.bytes_last_exchange = sum(self.send_counts[e] for e in self._remote) * D * h.element_size()
-            kind, works, (hr, rr) = self._start_images(sends, recvs)
-            return (kind, works, recv, (send, hr, rr))
-        self.bytes_last_exchange = send.numel() * h.element_size()
-        if self._staged(h):
-            hs, hr = [t.cpu() for t in sends], [t.cpu() for t in recvs]
-            return ("staged", self._post(hs, hr), recv, (hs, hr, recvs))
-        return ("direct", self._post(sends, recvs), recv, (send,))
+        # self entries are local copies, not exchanged bytes
+        self.bytes_last_exchange = sum(self.send_counts[e] for e in self._remote) * D * h.element_size()
+        return recv, self._start(list(send.split(self.send_counts)), list(recv.split(self.recv_counts)))
 
     def finish(self, h: torch.Tensor, token) -> torch.Tensor:
         """Wait for the transfer and write the ghost rows of ``h`` in place (one indexed copy, no clone of ``h``).
         Inference only: a tensor autograd has saved for backward must not be overwritten."""
         if torch.is_grad_enabled() and h.requires_grad:
             raise RuntimeError("the halo refresh writes ghost rows in place: not differentiable (run under torch.no_grad())")
-        kind, works, recv, keep = token
-        for w in works:
-            w.wait()
-        if kind == "staged":
-            for d, s in zip(keep[2], keep[1]):
-                d.copy_(s)
+        recv, pending = token
+        self._wait(*pending)
         if recv.shape[0]:
             h.index_copy_(0, self._recv_idx, recv)
         return h
@@ -500,7 +428,6 @@ class SlabHalo(GridHalo):
         self.lo[0] = float(slab_lo) - self.rank * w
         self.hi[0] = self.lo[0] + self.world * w
         out = super().setup(pos, feats, r)
-        by = dict(zip(self.neighbours, self.recv_counts))
-        self.n_ghost_left = by.get(self.left, 0) if self.left is not None else 0
-        self.n_ghost_right = by.get(self.right, 0) if self.right is not None else 0
+        by = {d: c for (_, d, _), c in zip(self.images, self.recv_counts)}
+        self.n_ghost_left, self.n_ghost_right = by.get((-1, 0, 0), 0), by.get((1, 0, 0), 0)
         return out

@@ -4,15 +4,12 @@ whole cloud, and two ranks sharing cuda:0 over gloo against the single-process p
 tiled cloud.  Tolerances: 2e-5 between fp32 forwards (different summation order per row), 1e-5 against the fp64 oracle
 (as tests/test_periodic_gpu.py), 2e-2 between bf16-storage forwards (one bf16 rounding of differently ordered sums)."""
 import itertools
-import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
+import gloo_ranks
 import models  # noqa: F401  (registers scalable_e3_gnn_amd -- also in the spawned ranks, which import this module)
 import pbc_reference as P
 from scalable_e3_gnn_amd import _lib
@@ -20,7 +17,6 @@ from scalable_e3_gnn_amd.sharding import GridHalo, select_images, select_images_
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OFFS = list(itertools.product((-1, 0, 1), repeat=3))
 
 
@@ -190,63 +186,45 @@ def test_world1_self_halo_vs_27_image_oracle():
 # ---------------------------------------------------------------------------------------------------------------------
 # 6. two ranks on cuda:0 over gloo, dims (2, 1, 1)
 # ---------------------------------------------------------------------------------------------------------------------
-def _worker(rank, world, port, periodic, M, H, layers, q):
-    sys.path.insert(0, REPO)
+def _worker(rank, world, periodic, M, H, layers, q):
     import torch.distributed as dist
     from scalable_e3_gnn_amd.radius_graph import radius_graph
     from scalable_e3_gnn_amd.segnn import SEGNN
 
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        r = 1.0 / (layers + 2.2)
-        pos = _dyadic(M, 41)
-        x = np.random.default_rng(42).standard_normal((M, 4)).astype(np.float32)
-        torch.manual_seed(43)
-        model = SEGNN("1x0e+1x1o", H, "1x1o", layers, lmax=2).to(DEV)
-        halo = GridHalo((2, 1, 1), (0, 0, 0), (1, 1, 1), periodic=periodic)
-        own = (halo.owner_of(torch.as_tensor(pos)) == rank).nonzero().flatten()
-        lpos, lx = halo.setup(torch.as_tensor(pos)[own].to(DEV), torch.as_tensor(x)[own].to(DEV), r)
-        blo, bhi = halo.box(rank)
-        g = radius_graph(lpos, r, [v - 2 * r for v in blo], [v + 2 * r for v in bhi])
-        halo.renumber(g.perm)
-        split = halo.split_graph(g)
+    r = 1.0 / (layers + 2.2)
+    pos = _dyadic(M, 41)
+    x = np.random.default_rng(42).standard_normal((M, 4)).astype(np.float32)
+    torch.manual_seed(43)
+    model = SEGNN("1x0e+1x1o", H, "1x1o", layers, lmax=2).to(DEV)
+    halo = GridHalo((2, 1, 1), (0, 0, 0), (1, 1, 1), periodic=periodic)
+    own = (halo.owner_of(torch.as_tensor(pos)) == rank).nonzero().flatten()
+    lpos, lx = halo.setup(torch.as_tensor(pos)[own].to(DEV), torch.as_tensor(x)[own].to(DEV), r)
+    blo, bhi = halo.box(rank)
+    g = radius_graph(lpos, r, [v - 2 * r for v in blo], [v + 2 * r for v in bhi])
+    halo.renumber(g.perm)
+    split = halo.split_graph(g)
+    with torch.no_grad():
+        o = model(lx[g.perm.long()], g, halo=halo, split=split)[halo.owned_new]
+        ob = model(lx[g.perm.long()], g, halo=halo)[halo.owned_new]
+    assert float((o - ob).abs().max() / ob.abs().max()) < 2e-5
+    q.put(("part", o.double().cpu().numpy(), own.numpy(), len(halo.neighbours), len(halo.images)))
+    if rank == 0:
+        gg = radius_graph(torch.as_tensor(pos).to(DEV), r, [0, 0, 0], [1, 1, 1], periodic=periodic)
         with torch.no_grad():
-            o = model(lx[g.perm.long()], g, halo=halo, split=split)[halo.owned_new]
-            ob = model(lx[g.perm.long()], g, halo=halo)[halo.owned_new]
-        assert float((o - ob).abs().max() / ob.abs().max()) < 2e-5
-        q.put(("part", o.double().cpu().numpy(), own.numpy(), len(halo.neighbours), len(halo.images)))
-        if rank == 0:
-            gg = radius_graph(torch.as_tensor(pos).to(DEV), r, [0, 0, 0], [1, 1, 1], periodic=periodic)
-            with torch.no_grad():
-                full = model(torch.as_tensor(x).to(DEV)[gg.perm.long()], gg)
-            ref = torch.empty_like(full)
-            ref[gg.perm.long()] = full
-            q.put(("ref", ref.double().cpu().numpy(), None, 0, 0))
-            params = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-            q.put(("oracle", _tiled_oracle(params, H, layers, pos, x, r, periodic), None, 0, 0))
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
+            full = model(torch.as_tensor(x).to(DEV)[gg.perm.long()], gg)
+        ref = torch.empty_like(full)
+        ref[gg.perm.long()] = full
+        q.put(("ref", ref.double().cpu().numpy(), None, 0, 0))
+        params = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+        q.put(("oracle", _tiled_oracle(params, H, layers, pos, x, r, periodic), None, 0, 0))
+    dist.barrier()
 
 
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("periodic", [True, (True, True, False)])
 def test_two_ranks_on_one_gpu(periodic):
     world, M, H, layers = 2, 300, 32, 2
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, periodic, M, H, layers, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=240) for _ in range(world + 2)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = gloo_ranks.run(_worker, world, (periodic, M, H, layers), world + 2, 240)
     ref = [g for g in got if g[0] == "ref"][0][1]
     oracle = [g for g in got if g[0] == "oracle"][0][1]
     merged = np.full_like(ref, np.nan)

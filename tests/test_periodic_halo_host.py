@@ -5,20 +5,16 @@ periodic images, and the local edge sets (ghosts mapped back to global ids throu
 ``radius_graph(periodic=True)``'s restatement (tests/pbc_reference.py) exactly.  Coordinates are dyadic (2^-16 grid, box
 length 1), so every image shift is exact in fp32."""
 import itertools
-import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
+import gloo_ranks
 import models  # noqa: F401  (registers scalable_e3_gnn_amd -- also in the spawned ranks, which import this module)
 import pbc_reference as P
 from scalable_e3_gnn_amd.sharding import GridHalo, check_cutoff, image_entries
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OFFS = list(itertools.product((-1, 0, 1), repeat=3))
 MASKS = [True, False, (True, False, True), (False, True, False)]
 
@@ -166,9 +162,7 @@ def _ref_edges(pos, r, periodic, rows):
     return set(map(tuple, np.stack([dst[m], s[m]], 1).tolist()))
 
 
-def _worker(rank, world, port, dims, periodic, N, H, layers, kind, q):
-    sys.path.insert(0, REPO)
-    sys.path.insert(0, os.path.join(REPO, "tests"))
+def _worker(rank, world, dims, periodic, N, H, layers, kind, q):
     import torch.distributed as dist
     import models  # noqa: F401
     from oracle import graph_oracle as G
@@ -176,47 +170,42 @@ def _worker(rank, world, port, dims, periodic, N, H, layers, kind, q):
     from scalable_e3_gnn_amd.radius_graph import RadiusGraph
     from scalable_e3_gnn_amd.segnn import SEGNN
 
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        pos, x = _cloud(N, kind, 5)
-        r = 1.0 / (layers + 2.2)
-        torch.manual_seed(0)
-        params = {k: v.detach().double().numpy() for k, v in SEGNN("1x0e+1x1o", H, "1x1o", layers).state_dict().items()}
-        halo = GridHalo(dims, (0, 0, 0), (1, 1, 1), periodic=periodic)
-        own = (halo.owner_of(torch.as_tensor(pos)) == rank).nonzero().flatten().numpy()
-        feats = torch.as_tensor(np.concatenate([x[own], own[:, None].astype(np.float64)], 1))   # last column: global id
-        lpos, lf = halo.setup(torch.as_tensor(pos[own]), feats, r)
-        assert lpos.dtype == torch.float32 and len(halo.send_counts) == len(halo.images) == len(halo.recv_counts)
-        blo, bhi = halo.box(rank)
-        nloc = lpos.shape[0]
-        if nloc:
-            perm, rowptr, src = G.graph(lpos.numpy(), [v - 2 * r for v in blo], [v + 2 * r for v in bhi], r)
-        else:
-            perm, rowptr, src = np.zeros(0, np.int32), np.zeros(1, np.int32), np.zeros(0, np.int32)
-        halo.renumber(torch.as_tensor(perm))
-        edges = _owned_edges(halo, perm, rowptr, src, lf[:, 4].numpy())
-        g = RadiusGraph(torch.as_tensor(perm), torch.zeros(nloc, 4), torch.as_tensor(rowptr), torch.as_tensor(src),
-                        len(src), ((1, 1, 1), 0))
-        sp = halo.split_graph(g)
+    pos, x = _cloud(N, kind, 5)
+    r = 1.0 / (layers + 2.2)
+    torch.manual_seed(0)
+    params = {k: v.detach().double().numpy() for k, v in SEGNN("1x0e+1x1o", H, "1x1o", layers).state_dict().items()}
+    halo = GridHalo(dims, (0, 0, 0), (1, 1, 1), periodic=periodic)
+    own = (halo.owner_of(torch.as_tensor(pos)) == rank).nonzero().flatten().numpy()
+    feats = torch.as_tensor(np.concatenate([x[own], own[:, None].astype(np.float64)], 1))   # last column: global id
+    lpos, lf = halo.setup(torch.as_tensor(pos[own]), feats, r)
+    assert lpos.dtype == torch.float32 and len(halo.send_counts) == len(halo.images) == len(halo.recv_counts)
+    blo, bhi = halo.box(rank)
+    nloc = lpos.shape[0]
+    if nloc:
+        perm, rowptr, src = G.graph(lpos.numpy(), [v - 2 * r for v in blo], [v + 2 * r for v in bhi], r)
+    else:
+        perm, rowptr, src = np.zeros(0, np.int32), np.zeros(1, np.int32), np.zeros(0, np.int32)
+    halo.renumber(torch.as_tensor(perm))
+    edges = _owned_edges(halo, perm, rowptr, src, lf[:, 4].numpy())
+    g = RadiusGraph(torch.as_tensor(perm), torch.zeros(nloc, 4), torch.as_tensor(rowptr), torch.as_tensor(src),
+                    len(src), ((1, 1, 1), 0))
+    sp = halo.split_graph(g)
 
-        def exchange(h):
-            t = torch.as_tensor(h)
-            return halo.finish(t, halo.start(t)).numpy()
+    def exchange(h):
+        t = torch.as_tensor(h)
+        return halo.finish(t, halo.start(t)).numpy()
 
-        if len(own):
-            out = S.forward(params, H, layers, "1x0e+1x1o", "1x1o", lf[:, :4].numpy()[perm],
-                            lpos.numpy().astype(np.float64)[perm], sp.graph.rowptr.numpy(), sp.graph.src.numpy(),
-                            exchange=exchange)
-            owned_out = out[halo.owned_new.numpy()]
-        else:
-            for _ in range(layers):
-                exchange(np.zeros((nloc, 4 * H)))   # an empty rank still takes part in every refresh
-            owned_out = np.zeros((0, 3))
-        q.put((rank, own, owned_out, sorted(edges), halo.n_ghost, len(halo.neighbours)))
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
+    if len(own):
+        out = S.forward(params, H, layers, "1x0e+1x1o", "1x1o", lf[:, :4].numpy()[perm],
+                        lpos.numpy().astype(np.float64)[perm], sp.graph.rowptr.numpy(), sp.graph.src.numpy(),
+                        exchange=exchange)
+        owned_out = out[halo.owned_new.numpy()]
+    else:
+        for _ in range(layers):
+            exchange(np.zeros((nloc, 4 * H)))   # an empty rank still takes part in every refresh
+        owned_out = np.zeros((0, 3))
+    q.put((rank, own, owned_out, sorted(edges), halo.n_ghost, len(halo.neighbours)))
+    dist.barrier()
 
 
 def _tiled_oracle(pos, x, r, periodic, H, layers):
@@ -241,19 +230,7 @@ def _tiled_oracle(pos, x, r, periodic, H, layers):
 
 def _run(dims, periodic, N, kind, H=4, layers=2):
     world = dims[0] * dims[1] * dims[2]
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, dims, periodic, N, H, layers, kind, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=280) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = gloo_ranks.run(_worker, world, (dims, periodic, N, H, layers, kind), world, 280)
     pos, x = _cloud(N, kind, 5)
     r = 1.0 / (layers + 2.2)
     want = _tiled_oracle(pos, x, r, periodic, H, layers)

@@ -2,86 +2,67 @@
 ghosts must match the single-process forward over the whole cloud and -- for the l_max = 2 cases -- the numpy fp64 oracle of
 the whole cloud.  `boost`: the features of rank 1's particles are multiplied by it, so that the refreshed ghost rows of rank 0
 are far larger than every row rank 0 held when the layer's operand scale was fixed (the stale-ghost scale)."""
-import os
-import socket
-import sys
-
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+import gloo_ranks
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _worker(rank, world, port, N, H, L, lmax, boost, q):
-    sys.path.insert(0, REPO)
+def _worker(rank, world, N, H, L, lmax, boost, q):
     import torch.distributed as dist
     import models  # noqa
     from scalable_e3_gnn_amd.radius_graph import radius_graph
     from scalable_e3_gnn_amd.segnn import SEGNN
     from scalable_e3_gnn_amd.sharding import SlabHalo
 
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        dev = "cuda:0"
-        g0 = torch.Generator().manual_seed(11)
-        pos = torch.rand(N, 3, generator=g0)
-        pos[:, 0] *= world
-        x = torch.randn(N, 4, generator=g0)
-        x[pos[:, 0] >= 1.0] *= boost
-        r = float((3 * 16.0 / (4 * np.pi * (N / world))) ** (1 / 3))
-        torch.manual_seed(0)
-        model = SEGNN("1x0e+1x1o", H, "1x1o", L, lmax=lmax).to(dev)
-        own = ((pos[:, 0] >= rank) & (pos[:, 0] < rank + 1)).nonzero().flatten()
-        halo = SlabHalo()
-        lpos, lx = halo.setup(pos[own].to(dev), x[own].to(dev), float(rank), float(rank + 1), r)
-        g = radius_graph(lpos, r, [rank - 2 * r, 0, 0], [rank + 1 + 2 * r, 1, 1])
-        halo.renumber(g.perm)
-        split = halo.split_graph(g)
+    dev = "cuda:0"
+    g0 = torch.Generator().manual_seed(11)
+    pos = torch.rand(N, 3, generator=g0)
+    pos[:, 0] *= world
+    x = torch.randn(N, 4, generator=g0)
+    x[pos[:, 0] >= 1.0] *= boost
+    r = float((3 * 16.0 / (4 * np.pi * (N / world))) ** (1 / 3))
+    torch.manual_seed(0)
+    model = SEGNN("1x0e+1x1o", H, "1x1o", L, lmax=lmax).to(dev)
+    own = ((pos[:, 0] >= rank) & (pos[:, 0] < rank + 1)).nonzero().flatten()
+    halo = SlabHalo()
+    lpos, lx = halo.setup(pos[own].to(dev), x[own].to(dev), float(rank), float(rank + 1), r)
+    g = radius_graph(lpos, r, [rank - 2 * r, 0, 0], [rank + 1 + 2 * r, 1, 1])
+    halo.renumber(g.perm)
+    split = halo.split_graph(g)
+    with torch.no_grad():
+        out = model(lx[g.perm.long()], g, halo=halo, split=split)   # overlapped refresh, interior / boundary edges
+        out_b = model(lx[g.perm.long()], g, halo=halo)              # blocking refresh on the unsplit graph
+    o, ob = out[halo.owned_new], out_b[halo.owned_new]
+    assert float((o - ob).abs().max() / ob.abs().max()) < 2e-5
+    q.put(("part", o.cpu().numpy(), own.numpy()))
+    if rank == 0:
+        gg = radius_graph(pos.to(dev), r, [0, 0, 0], [world, 1, 1])
         with torch.no_grad():
-            out = model(lx[g.perm.long()], g, halo=halo, split=split)   # overlapped refresh, interior / boundary edges
-            out_b = model(lx[g.perm.long()], g, halo=halo)              # blocking refresh on the unsplit graph
-        o, ob = out[halo.owned_new], out_b[halo.owned_new]
-        assert float((o - ob).abs().max() / ob.abs().max()) < 2e-5
-        q.put(("part", o.cpu().numpy(), own.numpy()))
-        if rank == 0:
-            gg = radius_graph(pos.to(dev), r, [0, 0, 0], [world, 1, 1])
-            with torch.no_grad():
-                full = model(x.to(dev)[gg.perm.long()], gg)
-            ref = torch.empty_like(full)
-            ref[gg.perm.long()] = full
-            q.put(("ref", ref.cpu().numpy(), None))
-            if lmax == 2 and N <= 8000:   # an independent reference too: the fp64 oracle of the unsharded cloud
-                from oracle import segnn_oracle as S
-                params = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-                perm = gg.perm.cpu().numpy()
-                want = S.forward_l2(params, H, L, "1x0e+1x1o", "1x1o", x.double().numpy()[perm], pos.numpy()[perm],
-                                    gg.rowptr.cpu().numpy(), gg.src.cpu().numpy())
-                o64 = np.empty_like(want)
-                o64[perm] = want
-                q.put(("oracle", o64, None))
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
+            full = model(x.to(dev)[gg.perm.long()], gg)
+        ref = torch.empty_like(full)
+        ref[gg.perm.long()] = full
+        q.put(("ref", ref.cpu().numpy(), None))
+        if lmax == 2 and N <= 8000:   # an independent reference too: the fp64 oracle of the unsharded cloud
+            from oracle import segnn_oracle as S
+            params = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+            perm = gg.perm.cpu().numpy()
+            want = S.forward_l2(params, H, L, "1x0e+1x1o", "1x1o", x.double().numpy()[perm], pos.numpy()[perm],
+                                gg.rowptr.cpu().numpy(), gg.src.cpu().numpy())
+            o64 = np.empty_like(want)
+            o64[perm] = want
+            q.put(("oracle", o64, None))
+    dist.barrier()
 
 
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("H,lmax,N,boost", [(16, 1, 20000, 1.0), (32, 2, 20000, 1.0), (32, 2, 6000, 1.0), (32, 2, 6000, 100.0)])
 def test_sharded_gpu_forward_equals_single_process(H, lmax, N, boost):
     world, L = 2, 3
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, N, H, L, lmax, boost, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=240) for _ in range(world + 1 + (1 if (lmax == 2 and N <= 8000) else 0))]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = gloo_ranks.run(_worker, world, (N, H, L, lmax, boost), world + 1 + (1 if (lmax == 2 and N <= 8000) else 0), 240)
     ref = [g for g in got if g[0] == "ref"][0][1]
     merged = np.full_like(ref, np.nan)
     for tag, val, idx in got:
