@@ -288,6 +288,12 @@ int e3_tp_forward(const e3_tp_plan* plan, const void* in1, int64_t ld_in1, const
  * ignored) and writes out4 = {s, 1/s, scratch, scratch} on the stream; no host synchronisation.  Exact powers of two:
  * scaling itself adds no rounding.  e3_add_pow2_scale: out = h + u (n elements, n % 4 == 0, 16-byte aligned) and the
  * scale of `out` in the same pass (the residual update of a layer yields the next layer's scale for free).
+ * The contract, shared by every producer of a scale (these two entries and out_scale4 of e3_tp_forward_fused_epilogue):
+ *   - m = max |x| over the FINITE elements only; NaN and +-inf are skipped per element and never hide a finite value
+ *     (a tensor with no finite nonzero element gives m = 0).  out4[2] holds the float bits of m.
+ *   - e = biased exponent of m.  e == 0 (m zero or denormal) gives s = 1.
+ *   - otherwise s = 2^(se - 127) with se = 127 + target_log2 - (e - 127) clamped to [1, 254], i.e. m s lies in
+ *     [2^target, 2^(target+1)) unless the clamp bites.  out4[1] = 1/s, exact.
  */
 int e3_pow2_scale(const e3_tp_segment* segs, const int64_t* nrows, int nseg, int target_log2, float* out4,
                   void* stream);

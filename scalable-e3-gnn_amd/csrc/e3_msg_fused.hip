@@ -79,14 +79,14 @@ __global__ void msg_absmax_kernel(MsgPackArgs a, uint32_t* hdr) {  // fp32 stora
   float m1 = 0.f, m2 = 0.f;
   for (int c = 0; c < 3; ++c) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.nw1[c]; i += (int64_t)gridDim.x * blockDim.x)
-      m1 = fmaxf(m1, fabsf(static_cast<const float*>(a.w1[c])[i]));
+      m1 = fmax_finite(m1, static_cast<const float*>(a.w1[c])[i]);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.nw2[c]; i += (int64_t)gridDim.x * blockDim.x)
-      m2 = fmaxf(m2, fabsf(static_cast<const float*>(a.w2[c])[i]));
+      m2 = fmax_finite(m2, static_cast<const float*>(a.w2[c])[i]);
   }
   for (int o = 32; o > 0; o >>= 1) { m1 = fmaxf(m1, __shfl_xor(m1, o)); m2 = fmaxf(m2, __shfl_xor(m2, o)); }
   if ((threadIdx.x & 63) == 0) {
-    if (m1 > 0.f && m1 < INFINITY) atomicMax(hdr + 0, __builtin_bit_cast(uint32_t, m1));
-    if (m2 > 0.f && m2 < INFINITY) atomicMax(hdr + 3, __builtin_bit_cast(uint32_t, m2));
+    if (m1 > 0.f) atomicMax(hdr + 0, __builtin_bit_cast(uint32_t, m1));
+    if (m2 > 0.f) atomicMax(hdr + 3, __builtin_bit_cast(uint32_t, m2));
   }
 }
 

@@ -19,7 +19,8 @@ struct ScaleArgs {
   int n;
 };
 
-// out4: [0] s, [1] 1/s, [2] float bits of the running max |x| (zeroed on the stream before this kernel), [3] unused
+// out4: [0] s, [1] 1/s, [2] float bits of the running max |x| over the finite elements (zeroed on the stream before this
+// kernel), [3] unused.  NaN / inf are filtered per element (fmax_finite), so they never hide a finite maximum.
 // A segment whose rows are whole float4s (cols and ld multiples of 4, 16-byte aligned base) is read 16 bytes per lane:
 // dense segments as one flat range, strided ones row by row (a workgroup per row step, no per-element division).
 __global__ __launch_bounds__(256) void absmax_kernel(ScaleArgs a, uint32_t* bits) {
@@ -33,26 +34,23 @@ __global__ __launch_bounds__(256) void absmax_kernel(ScaleArgs a, uint32_t* bits
       const float4* b4 = reinterpret_cast<const float4*>(base);
       const int64_t n4 = rows * cols / 4;
       for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const float4 v = b4[i];
-        m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+        m = fmax_finite4(m, b4[i]);
       }
     } else if (vec) {
       const int c4 = cols / 4;
       for (int64_t r = blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {  // a wave per row
         const float4* b4 = reinterpret_cast<const float4*>(base + r * ld);
         for (int c = threadIdx.x & 63; c < c4; c += 64) {
-          const float4 v = b4[c];
-          m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+          m = fmax_finite4(m, b4[c]);
         }
       }
     } else {
       for (int64_t r = blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4)
-        for (int c = threadIdx.x & 63; c < cols; c += 64) m = fmaxf(m, fabsf(base[r * ld + c]));
+        for (int c = threadIdx.x & 63; c < cols; c += 64) m = fmax_finite(m, base[r * ld + c]);
     }
   }
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  // NaN / inf inputs leave the scale at the finite maximum seen so far (the product then propagates them itself)
-  if ((threadIdx.x & 63) == 0 && m > 0.f && m < INFINITY) atomicMax(bits, __builtin_bit_cast(uint32_t, m));
+  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(bits, __builtin_bit_cast(uint32_t, m));
 }
 
 __global__ void scale_finalize_kernel(float* out4, int target) {
@@ -70,10 +68,10 @@ __global__ __launch_bounds__(256) void add_absmax_kernel(const float4* __restric
     const float4 a = h[i], b = u[i];
     const float4 r = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
     o[i] = r;
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
+    m = fmax_finite4(m, r);
   }
   for (int o2 = 32; o2 > 0; o2 >>= 1) m = fmaxf(m, __shfl_xor(m, o2));
-  if ((threadIdx.x & 63) == 0 && m > 0.f && m < INFINITY) atomicMax(bits, __builtin_bit_cast(uint32_t, m));
+  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(bits, __builtin_bit_cast(uint32_t, m));
 }
 
 int scale_finalize(float* out4, int target_log2, hipStream_t s) {

@@ -13,7 +13,7 @@ namespace e3 {
 
 #include "e3_tp_mfma_core.h"
 
-// max |w| over the three natural-parity class matrices -> header[0] (float bits, atomicMax; zeroed by the caller)
+// max |w| over the finite entries of the three natural-parity class matrices -> header[0] (float bits, atomicMax; zeroed by the caller)
 template <typename T>
 __global__ void fast_absmax_kernel(const T* w0, int64_t n0, const T* w1, int64_t n1, const T* w2, int64_t n2,
                                    uint32_t* hdr) {
@@ -22,9 +22,9 @@ __global__ void fast_absmax_kernel(const T* w0, int64_t n0, const T* w1, int64_t
   float m = 0.f;
   for (int c = 0; c < 3; ++c)
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n[c]; i += (int64_t)gridDim.x * blockDim.x)
-      m = fmaxf(m, fabsf(to_acc(w[c][i])));
+      m = fmax_finite(m, to_acc(w[c][i]));
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0 && m > 0.f && m < INFINITY) atomicMax(hdr, __builtin_bit_cast(uint32_t, m));
+  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(hdr, __builtin_bit_cast(uint32_t, m));
 }
 
 template <typename T>

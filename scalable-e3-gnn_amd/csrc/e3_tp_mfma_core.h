@@ -59,6 +59,17 @@ __host__ __device__ __forceinline__ float pow2_scale_from_bits(uint32_t amax_bit
   return f;
 }
 
+// Running max |v| over the FINITE values only (the operand-scale contract, include/e3gnn.h): each element is filtered
+// before the max, so a NaN / inf never discards the finite values it is reduced with (fabsf(NaN) < INF is false too).
+__device__ __forceinline__ float fmax_finite(float m, float v) {
+  const float a = fabsf(v);
+  return fmaxf(m, a < INFINITY ? a : 0.f);
+}
+__device__ __forceinline__ float fmax_finite4(float m, float4 v) {
+  return fmaxf(fmaxf(m, fmaxf(fmax_finite(0.f, v.x), fmax_finite(0.f, v.y))),
+               fmaxf(fmax_finite(0.f, v.z), fmax_finite(0.f, v.w)));
+}
+
 // Compile-time bookkeeping: which (l1, l2, l3) paths exist for natural-parity irreps with SH degree <= LSH and NT*
 // output tiles per degree.
 template <int LSH, int NT0, int NT1, int NT2>

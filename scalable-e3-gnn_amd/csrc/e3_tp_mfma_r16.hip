@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
                   v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
                 }
               }
-              amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+              amax = fmax_finite4(amax, v);
             }
             if (IO16) {
               uint2 pk;
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
               v += IO16 ? __builtin_bit_cast(float, (uint32_t)reinterpret_cast<const uint16_t*>(segs.residual)[ro] << 16)
                         : reinterpret_cast<const float*>(segs.residual)[ro];
             }
-            amax = fmaxf(amax, fabsf(v));
+            amax = fmax_finite(amax, v);
             if (IO16)
               reinterpret_cast<uint16_t*>(outv)[c0 + (int64_t)r * ldo] = __builtin_bit_cast(uint16_t, (__bf16)v);
             else
@@ -568,8 +568,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
     }
   }
   if constexpr (!SCAT) {
-    if (segs.amax) {  // NaN / inf leave the maximum at the largest finite value seen (as e3_pow2_scale does)
-      amax = amax < INFINITY ? amax : 0.f;
+    if (segs.amax) {  // max over the finite values only, filtered per element above (as e3_pow2_scale does)
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
       if (lane == 0 && amax > 0.f) atomicMax(segs.amax, __builtin_bit_cast(uint32_t, amax));

@@ -105,12 +105,18 @@ class FusedMessage:
     def refresh_row_max(self, state, h: torch.Tensor, rows: torch.Tensor, in_scale: torch.Tensor | None):
         """The pre-mix launch leaves max |h[n] in_scale| per node behind its table (the edge kernel bounds a row's messages
         with it).  After rows of ``h`` were overwritten (halo refresh of the ghost rows) their entries are recomputed here
-        -- device-side, no sync -- and the largest scaled value is returned (device scalar) for the caller's overflow guard."""
+        -- device-side, no sync -- and the largest scaled value is returned (device scalar) for the caller's overflow guard.
+        The maxima are over the finite entries (the operand-scale contract): a NaN / inf ghost row stays in the rows the
+        math sends it to and does not trip the guard."""
         premix = state[1]
         N = h.shape[0]
         ud = premix.numel() // N - 1
         hmax = premix[N * ud:]
-        m = h[rows].float().abs().amax(1) if rows.numel() else h.new_zeros(0, dtype=torch.float32)
+        if rows.numel():
+            a = h[rows].float().abs()
+            m = torch.where(a < float("inf"), a, 0.0).amax(1)   # NaN < inf is False: filtered too
+        else:
+            m = h.new_zeros(0, dtype=torch.float32)
         if in_scale is not None and h.dtype == torch.float32:
             m = m * in_scale[0]
         hmax[rows] = m
