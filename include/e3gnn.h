@@ -319,6 +319,17 @@ int e3_tp_forward_fused_epilogue(const e3_tp_plan* plan, const e3_tp_segment* se
                                  int64_t ld_in2, const void* packed, void* out, int64_t ld_out, int64_t B, int dtype,
                                  int gate, const float* in_scale, const void* residual, int64_t ld_residual,
                                  float* out_scale4, int target_log2, void* stream);
+/* Both products of a SEGNN node update in one launch:  u = gate(plan1([seg0 | seg1 ...] ; in2)),
+ * out = plan2(u ; in2) + residual, and out_scale4 (null = none) as in e3_tp_forward_fused_epilogue.  u never reaches HBM.
+ * fp32 storage: u's operand scale is a power of two per row (the two-launch path uses one for the whole tensor), so results
+ * agree with e3_tp_forward_fused + e3_tp_forward_fused_epilogue to the rounding of the fp16 split, not bit for bit; bf16
+ * storage: bit-identical.  E3_ERR_UNSUPPORTED (nothing launched) when the pair has no fused instantiation (plan1 gated with
+ * hidden 32 at l_max 2, plan2 = its gated irreps -> hidden irreps, segments without row_index, 16-byte aligned rows):
+ * callers then run the two launches. */
+int e3_tp_forward_update_pair(const e3_tp_plan* plan1, const e3_tp_plan* plan2, const e3_tp_segment* segs, int nseg,
+                              const void* in2, int64_t ld_in2, const void* packed1, const void* packed2,
+                              const float* in_scale, const void* residual, int64_t ld_residual, void* out,
+                              int64_t ld_out, int64_t B, int dtype, float* out_scale4, int target_log2, void* stream);
 /* Gradients of e3_tp_forward (fp32 / fp64; the reference operator relies on torch autograd, l1_tensor_prod.py:240-299).
  * `packed` = the buffer e3_tp_pack_weights wrote for this dtype.  Any of grad_in1 [B, in1_dim] (storage dtype),
  * grad_in2 [B, in2_dim] (ACCUMULATION dtype: fp32 for E3_F32, fp64 for E3_F64; with broadcast in2, ld_in2 == 0, pass

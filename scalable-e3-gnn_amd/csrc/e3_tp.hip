@@ -1204,6 +1204,30 @@ int e3_tp_forward_fused_epilogue(const e3_tp_plan* plan, const e3_tp_segment* se
   return out_scale4 ? scale_finalize(out_scale4, target_log2, s) : E3_OK;
 }
 
+int e3_tp_forward_update_pair(const e3_tp_plan* plan1, const e3_tp_plan* plan2, const e3_tp_segment* segs, int nseg,
+                              const void* in2, int64_t ld2, const void* packed1, const void* packed2,
+                              const float* in_scale, const void* residual, int64_t ld_residual, void* out, int64_t ldo,
+                              int64_t B, int dtype, float* out_scale4, int target_log2, void* stream) {
+  if (!plan1 || !plan2 || !segs || B < 0 || (residual && ld_residual <= 0)) return E3_ERR_INVALID_ARG;
+  if (out_scale4 && (target_log2 < -20 || target_log2 > 14)) return E3_ERR_INVALID_ARG;
+  if ((dtype != E3_F32 && dtype != E3_BF16) || ld2 == 0 || !e3::r16_pair_supported(&plan1->fast, &plan2->fast))
+    return E3_ERR_UNSUPPORTED;
+  if (!in2 || !packed1 || !packed2 || !out || ld2 < plan1->dev.Dy || ldo < plan2->dev.Dout) return E3_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  int st = tp_ensure_device(plan1);
+  if (st == E3_OK) st = tp_ensure_device(plan2);
+  if (st != E3_OK) return st;
+  if (out_scale4) E3_HIP_CHECK(hipMemsetAsync(out_scale4, 0, 16, s));
+  if (B > 0) {
+    st = fast_forward_pair(&plan1->fast, &plan2->fast, segs, nseg, plan1->dev.D1, in2, ld2,
+                           (const char*)packed1 + fast_section_offset(plan1), (const char*)packed2 + fast_section_offset(plan2),
+                           out, ldo, B, dtype, plan1->dev.ocol, plan2->dev.ocol, in_scale, residual, ld_residual,
+                           out_scale4 ? reinterpret_cast<uint32_t*>(out_scale4) + 2 : nullptr, s);
+    if (st != E3_OK) return st;
+  }
+  return out_scale4 ? scale_finalize(out_scale4, target_log2, s) : E3_OK;
+}
+
 int e3_tp_forward_fused_scatter(const e3_tp_plan* plan, const e3_tp_segment* segs, int nseg, const void* in2,
                                 int64_t ld2, const void* packed, const int32_t* row_node, void* out_nodes,
                                 int64_t ldo, int64_t B, int dtype, int gate, const float* in_scale, void* stream) {

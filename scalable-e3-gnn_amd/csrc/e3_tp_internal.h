@@ -69,5 +69,15 @@ bool r16_supported(const TpFast* F);
 int fast_forward_r16(const TpFast* F, const void* seg_args, const void* in2, int64_t ld2, const void* packed, void* out,
                      int64_t ldo, int64_t B, int gate, int io16, const int32_t* ocol_tab, const float* in_scale,
                      hipStream_t s);
+// fused node update (plan 1 gated, its output u the input of plan 2): is there an instantiation / launch it
+// (1 = launched, 0 = not applicable, < 0 = -status)
+bool r16_pair_supported(const TpFast* F1, const TpFast* F2);
+int fast_forward_pair_r16(const TpFast* F1, const TpFast* F2, const void* seg_args, const void* in2, int64_t ld2,
+                          const void* packed1, const void* packed2, void* out, int64_t ldo, int64_t B, int io16,
+                          const int32_t* ocol1, const int32_t* ocol2, const float* in_scale, hipStream_t s);
+int fast_forward_pair(const TpFast* F1, const TpFast* F2, const e3_tp_segment* segs, int nseg, int D1, const void* in2,
+                      int64_t ld2, const void* packed1, const void* packed2, void* out, int64_t ldo, int64_t B, int dtype,
+                      const int32_t* ocol1, const int32_t* ocol2, const float* in_scale, const void* residual,
+                      int64_t ldr, uint32_t* amax, hipStream_t s);
 
 }  // namespace e3

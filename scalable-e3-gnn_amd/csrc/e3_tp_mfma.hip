@@ -196,15 +196,10 @@ static thread_local const char* g_last_kernel = "";
 void fast_note_kernel(const char* name) { g_last_kernel = name; }
 const char* fast_last_kernel() { return g_last_kernel; }
 
-int fast_forward(const TpFast* F, const e3_tp_segment* segs, int nseg, int D1, const void* in2, int64_t ld2,
-                 const void* packed, void* out, int64_t ldo, int64_t B, int gate, int dtype, const int32_t* ocol_tab,
-                 const float* in_scale, hipStream_t s, const int32_t* scatter, const void* residual, int64_t ldr,
-                 uint32_t* amax) {
-  if (!F->usable) return E3_ERR_UNSUPPORTED;
-  const bool io16 = dtype == E3_BF16;
-  const FDev& d = F->dev;
+// the segments of in1 (and the epilogue extras) as the kernels take them
+static int fast_seg_args(const TpFast* F, const e3_tp_segment* segs, int nseg, int D1, int64_t ldo, const int32_t* scatter,
+                         const void* residual, int64_t ldr, uint32_t* amax, SegArgs& sa) {
   if (nseg < 1 || nseg > 4) return E3_ERR_INVALID_ARG;
-  SegArgs sa;
   int col = 0;
   if (ldo >= ((int64_t)1 << 24)) return E3_ERR_UNSUPPORTED;  // the store loop uses 24-bit multiplies for row * ldo
   for (int i = 0; i < 4; ++i) { sa.base[i] = nullptr; sa.ld[i] = 0; sa.index[i] = nullptr; }
@@ -230,8 +225,34 @@ int fast_forward(const TpFast* F, const e3_tp_segment* segs, int nseg, int D1, c
     while (sidx + 1 < nseg && ch.col >= sa.col0[sidx + 1]) ++sidx;
     if (ch.col + cw > sa.col0[sidx + 1]) return E3_ERR_INVALID_ARG;
   }
+  return E3_OK;
+}
+
+int fast_forward(const TpFast* F, const e3_tp_segment* segs, int nseg, int D1, const void* in2, int64_t ld2,
+                 const void* packed, void* out, int64_t ldo, int64_t B, int gate, int dtype, const int32_t* ocol_tab,
+                 const float* in_scale, hipStream_t s, const int32_t* scatter, const void* residual, int64_t ldr,
+                 uint32_t* amax) {
+  if (!F->usable) return E3_ERR_UNSUPPORTED;
+  const bool io16 = dtype == E3_BF16;
+  SegArgs sa;
+  const int st = fast_seg_args(F, segs, nseg, D1, ldo, scatter, residual, ldr, amax, sa);
+  if (st != E3_OK) return st;
   if (gate && !fast_gate_shape_ok(F)) return E3_ERR_UNSUPPORTED;
   const int r = fast_forward_r16(F, &sa, in2, ld2, packed, out, ldo, B, gate, io16 ? 1 : 0, ocol_tab, in_scale, s);
+  if (r == 1) return E3_OK;
+  return r < 0 ? -r : E3_ERR_UNSUPPORTED;
+}
+
+int fast_forward_pair(const TpFast* F1, const TpFast* F2, const e3_tp_segment* segs, int nseg, int D1, const void* in2,
+                      int64_t ld2, const void* packed1, const void* packed2, void* out, int64_t ldo, int64_t B, int dtype,
+                      const int32_t* ocol1, const int32_t* ocol2, const float* in_scale, const void* residual,
+                      int64_t ldr, uint32_t* amax, hipStream_t s) {
+  if (!F1->usable || !F2->usable || !r16_pair_supported(F1, F2)) return E3_ERR_UNSUPPORTED;
+  SegArgs sa;
+  const int st = fast_seg_args(F1, segs, nseg, D1, ldo, nullptr, residual, ldr, amax, sa);
+  if (st != E3_OK) return st;
+  const int r = fast_forward_pair_r16(F1, F2, &sa, in2, ld2, packed1, packed2, out, ldo, B, dtype == E3_BF16 ? 1 : 0,
+                                      ocol1, ocol2, in_scale, s);
   if (r == 1) return E3_OK;
   return r < 0 ? -r : E3_ERR_UNSUPPORTED;
 }

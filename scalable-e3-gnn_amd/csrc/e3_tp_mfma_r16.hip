@@ -577,6 +577,373 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Fused node update (e3_tp_forward_update_pair): update #1 (plan 1: [h | a] x A, gated) and update #2 (plan 2: u x A, plus the
+// residual h and the scale of the result) in one launch.  u never leaves the wave: after product #1 it is written one degree
+// at a time into the chunk buffer, laid out as a staged chunk of that degree, and product #2's chunk of that degree runs off
+// it.  fp32 storage: u gets a power-of-two operand scale PER ROW -- lane & 15 is the row both in the accumulators and in the
+// B operand, so a row's scale is one value per lane, with no pass over u and no agreement between waves -- and product #2's
+// accumulators are multiplied by its exact inverse.  bf16 storage: u is rounded to bf16 as the two-launch path stores it and
+// the chunks run in the same order, so the result is bit-identical.  Hidden 32: one 32-channel tile per degree of u.
+// Segments without a row index, 16-byte aligned rows (checked on the host).
+struct PairArgs {
+  const float* packed;       // plan 2's packed MFMA section
+  const FDev* dp;
+  const FChunk* chunks;      // plan 2: chunk l = degree l of u, 32 channels
+  const int32_t* ocol_tab;
+};
+constexpr int kPairTarget = 10;  // max |u| s of a row in [2^10, 2^11), as e3_pow2_scale's target for input features
+
+template <int LSH, int NT0, int NT1, int NT2, int MODE, int... L1S>
+__global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs, const float* __restrict__ in2, int64_t ld2,
+                                                                    const float* __restrict__ packed,
+                                                                    void* __restrict__ outv, int64_t ldo, int64_t B,
+                                                                    const FDev* __restrict__ dp,
+                                                                    const FChunk* __restrict__ chunks,
+                                                                    const int32_t* __restrict__ ocol_tab,
+                                                                    const float* __restrict__ in_scale, PairArgs pr) {
+  constexpr bool IO16 = MODE == 2;
+  constexpr int NL = (NT1 > 0 ? 1 : 0) + (NT2 > 0 ? 1 : 0);
+  static_assert(NT1 == 1 && NT2 <= 1 && NT0 == 1 + NL, "hidden 32: scalars and one gate block per degree, one tile each");
+  constexpr int CHUNK = r16_chunk(r16_max({L1S...}), NL);
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nwaves = blockDim.x >> 6;
+  const int j = lane & 15, g = lane >> 4;
+  const int Dout = dp->Dout, Dy = dp->Dy, nchunks = dp->nchunks, ntab = dp->ntab;
+  const int Dout2 = pr.dp->Dout, ntab2 = pr.dp->ntab;
+  int cMpad[3], cOoff[3], cBfoff[3], cM2[3], cMpad2[3], cOoff2[3], cBfoff2[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    cMpad[c] = dp->Mpad[c]; cOoff[c] = dp->ooff[c]; cBfoff[c] = dp->bfoff[c];
+    cM2[c] = pr.dp->M[c]; cMpad2[c] = pr.dp->Mpad[c]; cOoff2[c] = pr.dp->ooff[c]; cBfoff2[c] = pr.dp->bfoff[c];
+  }
+
+  // LDS: [normcol 1 | ocol 1 | normcol 2 | ocol 2 | per wave: chunk buffer | Y tile (16 x 9, padded to 160)]
+  float* nrm = lds;
+  int* ocl = reinterpret_cast<int*>(nrm + ((Dout + 15) & ~15));
+  float* nrm2 = reinterpret_cast<float*>(ocl + ((ntab + 15) & ~15));
+  int* ocl2 = reinterpret_cast<int*>(nrm2 + ((Dout2 + 15) & ~15));
+  float* cbuf = reinterpret_cast<float*>(ocl2 + ((ntab2 + 15) & ~15)) + (size_t)wave * (CHUNK + 160);
+  float* ybuf = cbuf + CHUNK;
+  // plan 1's operand scales as in tp_fwd_mfma_r16_kernel; plan 2's norms carry its weight scale only (u's scale is per row)
+  const float* hdr = packed + ((Dout + 3) & ~3);
+  const float* hdr2 = pr.packed + ((Dout2 + 3) & ~3);
+  const float xs = (!IO16 && in_scale) ? in_scale[0] : 1.0f;
+  const float unscale = IO16 ? 1.0f : hdr[2] * (in_scale ? in_scale[1] : 1.0f);
+  const float unscale2 = IO16 ? 1.0f : hdr2[2];
+  for (int i = tid; i < Dout; i += blockDim.x) nrm[i] = packed[i] * unscale;
+  for (int i = tid; i < ntab; i += blockDim.x) ocl[i] = ocol_tab[i];
+  for (int i = tid; i < Dout2; i += blockDim.x) nrm2[i] = pr.packed[i] * unscale2;
+  for (int i = tid; i < ntab2; i += blockDim.x) ocl2[i] = pr.ocol_tab[i];
+  __syncthreads();
+  const uint4* whi_base = reinterpret_cast<const uint4*>(hdr + 4);
+  const uint4* wlo_base = reinterpret_cast<const uint4*>(hdr + 4 + (dp->bftotal >> 1));
+  const uint4* whi2_base = reinterpret_cast<const uint4*>(hdr2 + 4);
+  const uint4* wlo2_base = reinterpret_cast<const uint4*>(hdr2 + 4 + (pr.dp->bftotal >> 1));
+
+  const int64_t ntiles = (B + 15) / 16;
+  const int64_t tstride = (int64_t)gridDim.x * nwaves;
+  const int inv_dy = (65536 + Dy - 1) / Dy;
+  using Slots = PathSlots<LSH, NT0, NT1, NT2>;
+  using Slots2 = PathSlots<LSH, 1, NT1, NT2>;
+  using Seq = IntSeq<L1S...>;
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+  using I3 = std::integral_constant<int, 3>;
+  using I5 = std::integral_constant<int, 5>;
+  // this lane's 8 channels of a 32-channel tile: q = 4 * (16-tile) + r  ->  channel 16 * (q >> 2) + 4 * g + (q & 3)
+  auto chan_of = [&](int q) { return 16 * (q >> 2) + 4 * g + (q & 3); };
+  const bool out_vec = !(ldo & 3) && ((reinterpret_cast<uintptr_t>(outv) & 15) == 0) &&
+                       (!segs.residual || (!(segs.ldr & 3) && (reinterpret_cast<uintptr_t>(segs.residual) & 15) == 0));
+  float amax = 0.f;  // running max |h'| of this lane's stores
+
+  for (int64_t tile = (int64_t)blockIdx.x * nwaves + wave; tile < ntiles; tile += tstride) {
+    const int64_t row0 = tile * 16;
+    const int nrows = (int)((B - row0) < 16 ? (B - row0) : 16);
+
+    // chunk ci of [h | a] -> chunk buffer: rows row0 .. row0 + 15 of its segment, one 16-byte LDS-DMA unit per lane (rows of
+    // S units, the odd pad unit unused), zeros for the tail rows
+    auto stage = [&](int ci) {
+      const FChunk ch = chunks[ci];
+      const int s = (segs.nseg > 1 && ch.col >= segs.col0[1]) + (segs.nseg > 2 && ch.col >= segs.col0[2]) +
+                    (segs.nseg > 3 && ch.col >= segs.col0[3]);
+      auto pick = [&](auto v0, auto v1, auto v2, auto v3) {
+        auto v = v0;
+        v = s == 1 ? v1 : v;
+        v = s == 2 ? v2 : v;
+        v = s == 3 ? v3 : v;
+        return v;
+      };
+      const int64_t ld = pick(segs.ld[0], segs.ld[1], segs.ld[2], segs.ld[3]);
+      const char* base = reinterpret_cast<const char*>(pick(segs.base[0], segs.base[1], segs.base[2], segs.base[3]));
+      const int segcol = ch.col - pick(segs.col0[0], segs.col0[1], segs.col0[2], segs.col0[3]);
+      constexpr int ESZ = IO16 ? 2 : 4, EPU = 16 / ESZ, MI = IO16 ? 1 : 0;
+      const int cw = ch.count * (2 * ch.l1 + 1);  // whole 32-channel chunks: no padding columns
+      const int S = ch.S[MI], rows_per = ch.rows_per[MI];
+      const int rl = (lane * ch.inv[MI]) >> 16, u = lane - rl * S;
+      const bool lane_ok = rl < rows_per && u < cw / EPU;
+      const char* lsrc = base + ((row0 + rl) * ld + segcol) * ESZ + u * 16;
+      for (int r0 = 0; r0 < 16; r0 += rows_per)
+        if (lane_ok && r0 + rl < nrows)
+          __builtin_amdgcn_global_load_lds((glb_void_t*)(lsrc + (int64_t)r0 * ld * ESZ), (lds_void_t*)(cbuf + r0 * S * 4), 16,
+                                           0, 0);
+      for (int e = nrows * S * 4 + lane; e < 16 * S * 4; e += 64) cbuf[e] = 0.f;
+    };
+
+    // Y tile [16][Dy]
+    for (int h = 0; h * 64 < 16 * Dy; ++h) {
+      const int e = h * 64 + lane;
+      const int yr = (e * inv_dy) >> 16, yc = e - yr * Dy;
+      if (e < 16 * Dy) {
+        if (yr < nrows)
+          __builtin_amdgcn_global_load_lds((glb_void_t*)(in2 + (row0 + yr) * ld2 + yc), (lds_void_t*)(ybuf + h * 64), 4,
+                                           0, 0);
+        else
+          ybuf[e] = 0.f;
+      }
+    }
+    stage(0);
+
+    // ---- product #1 ----
+    f32x4 a0[2 * NT0][1], a1[2][3], a2[NT2 > 0 ? 2 : 1][5];
+#pragma unroll
+    for (int t = 0; t < 2 * NT0; ++t) a0[t][0] = f32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) a1[t][c] = f32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < (NT2 > 0 ? 2 : 1); ++t)
+#pragma unroll
+      for (int c = 0; c < 5; ++c) a2[t][c] = f32x4{0, 0, 0, 0};
+    float y[9];
+    int ci = 0;
+    auto process = [&](auto itag) {
+      constexpr int L1 = Seq::at(decltype(itag)::value);
+      wait_vm0();
+      wave_sync_lds();
+      if (ci == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) y[q] = (q < Dy) ? ybuf[j * Dy + q] : 0.f;
+      }
+      const FChunk ch = chunks[ci];
+      float x[8][2 * L1 + 1];
+      load_x16<L1, IO16>(cbuf + j * (((32 * (2 * L1 + 1) / (IO16 ? 8 : 4)) | 1) * 4), g, xs, x);
+#define E3_RUN(L2v, L3v, ACC, NTv)                                                                             \
+  if constexpr (Slots::valid(L1, L2v, L3v)) {                                                                  \
+    const size_t o = (size_t)(cBfoff[L3v] >> 3) + (size_t)(2 * ch.wblk[L2v][L3v] + g) * cMpad[L3v] + j;        \
+    run16<L1, L2v, L3v, 2 * NTv, IO16>(x, true, whi_base + o, wlo_base + o, y, ACC);                            \
+  }
+      E3_RUN(0, 0, a0, NT0) E3_RUN(1, 0, a0, NT0) E3_RUN(2, 0, a0, NT0)
+      E3_RUN(0, 1, a1, NT1) E3_RUN(1, 1, a1, NT1) E3_RUN(2, 1, a1, NT1)
+      E3_RUN(0, 2, a2, NT2) E3_RUN(1, 2, a2, NT2) E3_RUN(2, 2, a2, NT2)
+#undef E3_RUN
+      wave_sync_lds();
+      if (ci + 1 < nchunks) stage(ci + 1);
+      ++ci;
+    };
+    for_each_index(process, std::make_index_sequence<sizeof...(L1S)>{});
+    wait_vm0();
+    wave_sync_lds();
+
+    // ---- u = gate(product #1) in place (the values the two-launch path stores), and the row scale ----
+    // out irreps of plan 1: [32 scalars | 32 gates per gated degree | 32 x1o (| 32 x2e)]; the gate of channel c of degree l
+    // is scalar channel 32 l + c: same lane and register of a0
+    {
+      const float* nrm0 = nrm + ocl[cOoff[0]];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float s = a0[q >> 2][0][q & 3] * nrm0[chan_of(q)];
+        a0[q >> 2][0][q & 3] = s * sigmoid_(s);
+      }
+      const float* nv1 = nrm + ocl[cOoff[1]];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float gq = sigmoid_(a0[2 + (q >> 2)][0][q & 3] * nrm0[32 + chan_of(q)]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a1[q >> 2][c][q & 3] = (gq * a1[q >> 2][c][q & 3]) * nv1[3 * chan_of(q) + c];
+      }
+      if constexpr (NT2 > 0) {
+        const float* nv2 = nrm + ocl[cOoff[2]];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const float gq = sigmoid_(a0[4 + (q >> 2)][0][q & 3] * nrm0[64 + chan_of(q)]);
+#pragma unroll
+          for (int c = 0; c < 5; ++c) a2[q >> 2][c][q & 3] = (gq * a2[q >> 2][c][q & 3]) * nv2[5 * chan_of(q) + c];
+        }
+      }
+    }
+    float srow = 1.0f, isrow = 1.0f;
+    if constexpr (!IO16) {
+      float m = 0.f;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        m = fmax_finite(m, a0[q >> 2][0][q & 3]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m = fmax_finite(m, a1[q >> 2][c][q & 3]);
+        if constexpr (NT2 > 0) {
+#pragma unroll
+          for (int c = 0; c < 5; ++c) m = fmax_finite(m, a2[q >> 2][c][q & 3]);
+        }
+      }
+      // the row's four k groups (lanes j, j + 16, j + 32, j + 48)
+      m = fmaxf(m, __shfl_xor(m, 16, 64));
+      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      srow = pow2_scale_from_bits(__builtin_bit_cast(uint32_t, m), kPairTarget);
+      isrow = 1.0f / srow;
+    }
+
+    // ---- product #2, one degree of u at a time ----
+    f32x4 b0[2][1], b1[2][3], b2[NT2 > 0 ? 2 : 1][5];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      b0[t][0] = f32x4{0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) b1[t][c] = f32x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int t = 0; t < (NT2 > 0 ? 2 : 1); ++t)
+#pragma unroll
+      for (int c = 0; c < 5; ++c) b2[t][c] = f32x4{0, 0, 0, 0};
+    // degree L of u into the chunk buffer in the layout of a staged chunk of that degree: row j, channel-major, the row
+    // stride load_x16 expects (fp32: 32 D + 4 floats; bf16: 8 ((32 D / 8) | 1) halves)
+    auto put = [&](auto dtag, auto val) {
+      constexpr int D = decltype(dtag)::value;
+      if constexpr (IO16) {
+        uint16_t* o16 = reinterpret_cast<uint16_t*>(cbuf) + j * (8 * (((32 * D) / 8) | 1));
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+          for (int c = 0; c < D; ++c) o16[D * chan_of(q) + c] = __builtin_bit_cast(uint16_t, (__bf16)val(q, c));
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+          for (int c = 0; c < D; ++c) cbuf[j * (32 * D + 4) + D * chan_of(q) + c] = val(q, c) * srow;
+      }
+      wave_sync_lds();
+    };
+    // plan 2's chunk of degree L1 (same path order as tp_fwd_mfma_r16_kernel: bit-identical sums in bf16)
+    auto mul2 = [&](auto ltag) {
+      constexpr int L1 = decltype(ltag)::value;
+      const FChunk ch = pr.chunks[L1];
+      float x[8][2 * L1 + 1];
+      load_x16<L1, IO16>(cbuf + j * (((32 * (2 * L1 + 1) / (IO16 ? 8 : 4)) | 1) * 4), g, 1.0f, x);
+#define E3_RUN2(L2v, L3v, ACC, NTv)                                                                            \
+  if constexpr (Slots2::valid(L1, L2v, L3v)) {                                                                 \
+    const size_t o = (size_t)(cBfoff2[L3v] >> 3) + (size_t)(2 * ch.wblk[L2v][L3v] + g) * cMpad2[L3v] + j;      \
+    run16<L1, L2v, L3v, 2 * NTv, IO16>(x, true, whi2_base + o, wlo2_base + o, y, ACC);                          \
+  }
+      E3_RUN2(0, 0, b0, 1) E3_RUN2(1, 0, b0, 1) E3_RUN2(2, 0, b0, 1)
+      E3_RUN2(0, 1, b1, NT1) E3_RUN2(1, 1, b1, NT1) E3_RUN2(2, 1, b1, NT1)
+      E3_RUN2(0, 2, b2, NT2) E3_RUN2(1, 2, b2, NT2) E3_RUN2(2, 2, b2, NT2)
+#undef E3_RUN2
+      wave_sync_lds();
+    };
+    put(I1{}, [&](int q, int) { return a0[q >> 2][0][q & 3]; });
+    mul2(I0{});
+    put(I3{}, [&](int q, int c) { return a1[q >> 2][c][q & 3]; });
+    mul2(I1{});
+    if constexpr (NT2 > 0) {
+      put(I5{}, [&](int q, int c) { return a2[q >> 2][c][q & 3]; });
+      mul2(I2{});
+    }
+
+    // ---- epilogue of product #2: transpose through the chunk buffer, norm, residual, store, running max ----
+    float* ot = cbuf;
+    auto emit = [&](auto dtag, const int l3, auto val) {
+      constexpr int D = decltype(dtag)::value;
+      constexpr int TS = 32 * D + 4;
+      constexpr int UPR = 32 * D / 4;
+      const int base = cOoff2[l3];
+      const int cnt = cM2[l3] < 32 ? cM2[l3] : 32;
+      const int width = cnt * D;
+      auto col = [&](int lc) { return ocl2[base + lc / D] + lc % D; };
+      const int colb = col(0);
+      const bool vec = out_vec && ocl2[base + cnt - 1] == colb + (cnt - 1) * D && !(colb & 3) && !(width & 3);
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int c = 0; c < D; ++c) ot[j * TS + D * chan_of(q) + c] = val(q, c);
+      wave_sync_lds();
+      if (vec) {
+        constexpr uint32_t INV = (65536 + UPR - 1) / UPR;
+        static_assert(((16u * UPR - 1) * INV >> 16) == 15 && ((15u * UPR) * INV >> 16) == 15 &&
+                      ((14u * UPR + UPR - 1) * INV >> 16) == 14, "reciprocal");
+        const uint32_t ldo32 = (uint32_t)ldo;
+#pragma unroll 2
+        for (int it = 0; it < UPR / 4; ++it) {   // 16 * UPR units / 64 lanes
+          const uint32_t u = it * 64 + lane;
+          const uint32_t row = __umul24(u, INV) >> 16, un = u - __umul24(row, UPR);
+          const uint32_t lc0 = un * 4;
+          float4 v = *reinterpret_cast<const float4*>(ot + __umul24(row, TS) + un * 4);
+          const float* np = nrm2 + colb + lc0;
+          const float n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+          if ((int)row < nrows && (int)lc0 < width) {
+            v.x *= n0; v.y *= n1; v.z *= n2; v.w *= n3;
+            const uint32_t o = __umul24(row, ldo32) + (uint32_t)colb + lc0;
+            if (segs.residual) {
+              const int64_t ro = (row0 + row) * segs.ldr + colb + lc0;
+              if (IO16) {
+                const uint2 rk = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(segs.residual) + ro);
+                v.x += __builtin_bit_cast(float, rk.x << 16); v.y += __builtin_bit_cast(float, rk.x & 0xffff0000u);
+                v.z += __builtin_bit_cast(float, rk.y << 16); v.w += __builtin_bit_cast(float, rk.y & 0xffff0000u);
+              } else {
+                const float4 rv = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(segs.residual) + ro);
+                v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+              }
+            }
+            amax = fmax_finite4(amax, v);
+            if (IO16) {
+              uint2 pk;
+              pk.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{v.x, v.y}, bf16x2_t));
+              pk.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{v.z, v.w}, bf16x2_t));
+              *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(outv) + row0 * ldo + o) = pk;
+            } else {
+              *reinterpret_cast<float4*>(reinterpret_cast<float*>(outv) + row0 * ldo + o) = v;
+            }
+          }
+        }
+      } else {
+        for (int lc = lane; lc < 32 * D; lc += 64) {
+          if (lc >= width) continue;
+          const int64_t c0 = row0 * ldo + col(lc);
+          const float nv = nrm2[col(lc)];
+          const float* src = ot + lc;
+#pragma unroll 1
+          for (int r = 0; r < nrows; ++r) {
+            float v = src[r * TS] * nv;
+            if (segs.residual) {
+              const int64_t ro = (row0 + r) * segs.ldr + col(lc);
+              v += IO16 ? __builtin_bit_cast(float, (uint32_t)reinterpret_cast<const uint16_t*>(segs.residual)[ro] << 16)
+                        : reinterpret_cast<const float*>(segs.residual)[ro];
+            }
+            amax = fmax_finite(amax, v);
+            if (IO16)
+              reinterpret_cast<uint16_t*>(outv)[c0 + (int64_t)r * ldo] = __builtin_bit_cast(uint16_t, (__bf16)v);
+            else
+              reinterpret_cast<float*>(outv)[c0 + (int64_t)r * ldo] = v;
+          }
+        }
+      }
+      wave_sync_lds();
+    };
+    // isrow is an exact power of two: (acc / s) n == acc (n / s) of the two-launch path's norm table
+    emit(I1{}, 0, [&](int q, int) { return b0[q >> 2][0][q & 3] * isrow; });
+    emit(I3{}, 1, [&](int q, int c) { return b1[q >> 2][c][q & 3] * isrow; });
+    if constexpr (NT2 > 0) emit(I5{}, 2, [&](int q, int c) { return b2[q >> 2][c][q & 3] * isrow; });
+  }
+  if (segs.amax) {  // max over the finite values only, filtered per element above (as e3_pow2_scale does)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (lane == 0 && amax > 0.f) atomicMax(segs.amax, __builtin_bit_cast(uint32_t, amax));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
 struct R16KernelEntry {
@@ -681,6 +1048,92 @@ int fast_forward_r16(const TpFast* F, const void* sa_, const void* in2, int64_t 
   void* args[] = {const_cast<void*>(sa_), &in2f, &ld2, &pk, &outf, &ldo, &B, &dd, &dc, &ocol_tab, &in_scale};
   if (hipLaunchKernel(fn, dim3(grid), dim3(64 * kR16Waves), args, lds_bytes, s) != hipSuccess) return -E3_ERR_HIP;
   fast_note_kernel("e3::tp_fwd_mfma_r16_kernel");
+  return 1;
+}
+
+// fused node update: plan 1 = update #1 (the r16 entry's chunk sequence), plan 2 = update #2
+struct R16PairEntry {
+  int lsh, nt0, nt1, nt2;
+  std::vector<int> l1s;
+  const void* fn[2];  // [mode - 1]
+};
+#define E3_R16_PAIR(LSH, a, b, c, ...)                                                                         \
+  {LSH, a, b, c, {__VA_ARGS__},                                                                                \
+   {(const void*)tp_update_pair_r16_kernel<LSH, a, b, c, 1, __VA_ARGS__>,                                       \
+    (const void*)tp_update_pair_r16_kernel<LSH, a, b, c, 2, __VA_ARGS__>}}
+static const R16PairEntry* r16_pair_find(const TpFast* F1, const TpFast* F2) {
+  static const std::vector<R16PairEntry> k = {
+      E3_R16_PAIR(2, 3, 1, 1, 0, 1, 2, 0, 1, 2),   // hidden 32, l_max 2
+  };
+  const FDev& d = F1->dev;
+  const FDev& d2 = F2->dev;
+  std::vector<int> l1s;
+  for (auto& c : F1->h_chunks) {
+    if (c.count != 32) return nullptr;
+    l1s.push_back(c.l1);
+  }
+  const int nu = 1 + (d.NT[1] > 0) + (d.NT[2] > 0);  // degrees of u
+  if (!fast_gate_shape_ok(F1) || d.M[0] != 32 * nu) return nullptr;
+  // plan 2 reads u: in irreps [32 x0e | 32 x1o (| 32 x2e)], out irreps of the same degrees
+  if (d2.lsh != d.lsh || d2.Dy != d.Dy || (int)F2->h_chunks.size() != nu) return nullptr;
+  for (int l = 0; l < nu; ++l)
+    if (F2->h_chunks[l].l1 != l || F2->h_chunks[l].count != 32) return nullptr;
+  if (d2.NT[0] != 1 || d2.NT[1] != d.NT[1] || d2.NT[2] != d.NT[2]) return nullptr;
+  for (auto& e : k)
+    if (e.lsh == d.lsh && e.nt0 == d.NT[0] && e.nt1 == d.NT[1] && e.nt2 == d.NT[2] && e.l1s == l1s) return &e;
+  return nullptr;
+}
+static size_t r16_pair_lds_bytes(const TpFast* F1, const TpFast* F2, int nwaves) {
+  const FDev& d = F1->dev;
+  const FDev& d2 = F2->dev;
+  const size_t tables =
+      (size_t)(((d.Dout + 15) & ~15) + ((d.ntab + 15) & ~15) + ((d2.Dout + 15) & ~15) + ((d2.ntab + 15) & ~15)) * 4;
+  int lin = 0;
+  for (auto& c : F1->h_chunks) lin = std::max(lin, c.l1);
+  return tables + nwaves * (size_t)(r16_chunk(lin, d.NT[2] > 0 ? 2 : 1) + 160) * 4;
+}
+
+bool r16_pair_supported(const TpFast* F1, const TpFast* F2) {
+  return r16_find(F1) != nullptr && r16_pair_find(F1, F2) != nullptr && 2 * r16_pair_lds_bytes(F1, F2, kR16Waves) <= (size_t)kFastLds;
+}
+
+int fast_forward_pair_r16(const TpFast* F1, const TpFast* F2, const void* sa_, const void* in2, int64_t ld2,
+                          const void* packed1, const void* packed2, void* out, int64_t ldo, int64_t B, int io16,
+                          const int32_t* ocol1, const int32_t* ocol2, const float* in_scale, hipStream_t s) {
+  const SegArgs& sa = *static_cast<const SegArgs*>(sa_);
+  const R16PairEntry* e = r16_pair_find(F1, F2);
+  if (!e || sa.scatter) return 0;
+  // the staging of the pair kernel: plain rows (no row index), 16-byte aligned, whole 16-byte units per chunk
+  const int epu = io16 ? 8 : 4;
+  for (int i = 0; i < sa.nseg; ++i)
+    if (sa.index[i] || (sa.ld[i] % epu) || ((sa.col0[i + 1] - sa.col0[i]) % epu) ||
+        (reinterpret_cast<uintptr_t>(sa.base[i]) & 15))
+      return 0;
+  const void* fn = e->fn[io16 ? 1 : 0];
+  const size_t lds_bytes = r16_pair_lds_bytes(F1, F2, kR16Waves);
+  if (2 * lds_bytes > (size_t)kFastLds) return 0;
+  {  // the dynamic-LDS limit is a per-device attribute of the function
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -E3_ERR_HIP;
+    static std::mutex mu;
+    static std::vector<std::pair<const void*, int>> configured;
+    std::lock_guard<std::mutex> lock(mu);
+    if (std::find(configured.begin(), configured.end(), std::make_pair(fn, dev)) == configured.end()) {
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return -E3_ERR_HIP;
+      configured.emplace_back(fn, dev);
+    }
+  }
+  const int64_t ntiles = (B + 15) / 16;
+  const int grid = (int)std::min<int64_t>((ntiles + kR16Waves - 1) / kR16Waves, 256 * 2);
+  const float* in2f = (const float*)in2;
+  const float* pk = (const float*)packed1;
+  void* outf = out;
+  const FDev* dd = F1->d_dev;
+  const FChunk* dc = F1->d_chunks;
+  PairArgs pa{(const float*)packed2, F2->d_dev, F2->d_chunks, ocol2};
+  void* args[] = {const_cast<void*>(sa_), &in2f, &ld2, &pk, &outf, &ldo, &B, &dd, &dc, &ocol1, &in_scale, &pa};
+  if (hipLaunchKernel(fn, dim3(grid), dim3(64 * kR16Waves), args, lds_bytes, s) != hipSuccess) return -E3_ERR_HIP;
+  fast_note_kernel("e3::tp_update_pair_r16_kernel");
   return 1;
 }
 

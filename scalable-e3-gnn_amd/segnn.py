@@ -160,6 +160,12 @@ class SEGNNLayer(nn.Module):
             if f32 and h_scale is not None and halo is None:
                 sc = ops.join_pow2_scales(h_scale, ops.pow2_scale([a]))
             if self.upd2.fused_supported(False) and h.stride(-1) == 1:
+                if isinstance(self.upd1, SHTensorProduct) and a.stride(-1) == 1:
+                    # both products in one launch: u stays on chip with a power-of-two scale per row
+                    r = self.upd1.forward_update_pair(self.upd2, [(h, None), (a, None)], A, in_scale=sc, residual=h,
+                                                      out_scale=10 if f32 else None)
+                    if r is not None:
+                        return r if f32 else (r, None)
                 # the scale of u comes out of update #1's epilogue; update #2 adds the residual and emits the scale of the
                 # new h in its own: no pass over [N, width] outside the two products
                 u, u_scale = self.upd1.forward_fused([(h, None), (a, None)], A, gate=True, in_scale=sc,

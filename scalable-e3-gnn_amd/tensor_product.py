@@ -221,6 +221,56 @@ class TPPlan:
             return out, sc4
         return out
 
+    def forward_update_pair(self, ws, ns, plan2, ws2, ns2, segments, in2, in_scale=None, residual=None, out_scale=None):
+        """Both products of a SEGNN node update in one launch (``e3_tp_forward_update_pair``):
+        ``plan2(gate(self([seg0 | seg1 ...] ; in2)) ; in2) + residual``; the gated intermediate never reaches HBM.
+        segments: [(tensor [B, ncols], None), ...]; ``in_scale`` / ``out_scale`` as in ``forward_fused``.  Returns None
+        when the pair has no fused kernel (callers then run the two launches)."""
+        lib = _lib.load()
+        B = in2.shape[0]
+        dev = in2.device
+        io = segments[0][0].dtype
+        if io not in (torch.float32, torch.bfloat16) or in2.dtype != torch.float32 or in2.stride(-1) != 1:
+            return None
+        segs = (TPSegment * len(segments))()
+        keep = []
+        for i, (t, idx) in enumerate(segments):
+            if idx is not None or t.dtype != io or t.stride(-1) != 1 or t.shape[0] != B:
+                return None
+            keep.append(t)
+            segs[i].base, segs[i].ld, segs[i].ncols = t.data_ptr(), t.stride(0), t.shape[1]
+        out = torch.empty((B, plan2.out_dim), dtype=io, device=dev)
+        if residual is not None and (residual.shape != out.shape or residual.dtype != io or residual.stride(-1) != 1):
+            raise RuntimeError(f"forward_update_pair: residual must be {tuple(out.shape)} {io}, contiguous rows")
+        with torch.cuda.device(dev):
+            h1, h2 = self.handle(dev), plan2.handle(dev)
+            packed1 = self.packed(ws, ns, io, dev)
+            packed2 = plan2.packed(ws2, ns2, io, dev)
+            if io == torch.float32 and in_scale is None:
+                from . import ops
+                in_scale = ops.pow2_scale(keep)
+            sc = in_scale.data_ptr() if (in_scale is not None and io == torch.float32) else None
+            sc4 = torch.empty(4, dtype=torch.float32, device=dev) if out_scale is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            t0 = profiling.begin() if profiling.enabled() else None
+            st = lib.e3_tp_forward_update_pair(
+                h1, h2, ctypes.byref(segs), len(segments), in2.data_ptr(), in2.stride(0), packed1.data_ptr(),
+                packed2.data_ptr(), sc, residual.data_ptr() if residual is not None else None,
+                residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0), B, _lib.dtype_code(io),
+                sc4.data_ptr() if sc4 is not None else None, int(out_scale) if out_scale is not None else 0, stream)
+            if st == 4:  # E3_ERR_UNSUPPORTED: no fused kernel for this pair / these segments
+                return None
+            _lib.check(st, "e3_tp_forward_update_pair")
+            if t0 is not None:
+                esz = out.element_size()
+                nb = sum(t.numel() * esz for t in keep) + 4 * self.in2_dim * B + esz * out.numel() * (2 if residual is not None else 1)
+                mode = "<bf16 storage, bf16 MFMA>" if io == torch.bfloat16 else "<fp16x3 split MFMA>"
+                profiling.end(f"tp_update_pair B={B}", B, nb, t0, flops=(self.flops_per_row + plan2.flops_per_row) * B,
+                              kernel=(lib.e3_tp_last_fused_kernel() or b"e3::tp_update_pair_r16_kernel").decode() + mode)
+        if out_scale is not None:
+            return out, sc4
+        return out
+
 
 def _rebuild_tpplan(in_blocks, lmax_sh, out_blocks):
     return TPPlan(in_blocks, out_blocks, lmax_sh)
@@ -403,6 +453,14 @@ class SHTensorProduct(nn.Module):
         ws, ns = self._tensors()
         return self._plan.forward_fused(ws, ns, segments, in2, gate, tag=f"{self.iri1}->{self.iro}", scatter=scatter,
                                         in_scale=in_scale, residual=residual, out_scale=out_scale)
+
+    def forward_update_pair(self, second, segments, in2, in_scale=None, residual=None, out_scale=None):
+        """``second(gate(self(segments ; in2)) ; in2) + residual`` in one launch (``TPPlan.forward_update_pair``); None when
+        the pair has no fused kernel."""
+        ws, ns = self._tensors()
+        ws2, ns2 = second._tensors()
+        return self._plan.forward_update_pair(ws, ns, second._plan, ws2, ns2, segments, in2, in_scale=in_scale,
+                                              residual=residual, out_scale=out_scale)
 
     def forward(self, in1: torch.Tensor, in2: torch.Tensor) -> torch.Tensor:
         torch._assert(in1.shape[-1] == self.in1_dim,

@@ -1,0 +1,136 @@
+"""The fused node update (e3_tp_forward_update_pair: update #1 + gate + update #2 + residual + scale in one launch) against
+the two-launch path it replaces and the fp64 oracle (oracle/tp_oracle.py + segnn_oracle.gate_blocks)."""
+import numpy as np
+import pytest
+import torch
+
+import models  # noqa: F401
+from oracle import segnn_oracle as S
+from oracle import tp_oracle as T
+from scale_reference import expected_scale
+from scalable_e3_gnn_amd import _lib
+from scalable_e3_gnn_amd.tensor_product import SHTensorProduct
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _irreps(H):
+    return f"{H}x0e+{H}x1o+{H}x2e", f"{H}x0e+{2 * H}x0e+{H}x1o+{H}x2e"
+
+
+def _pair(H, seed, dtype=torch.float32):
+    hid, gated = _irreps(H)
+    torch.manual_seed(seed)
+    upd1 = SHTensorProduct(f"{hid}+{hid}", gated, 2).to(DEV).to(dtype)
+    upd2 = SHTensorProduct(hid, hid, 2).to(DEV).to(dtype)
+    return upd1, upd2
+
+
+def _np(t):
+    return t.detach().double().cpu().numpy()
+
+
+def _WN(mod):
+    W = {c: getattr(mod, "weights_" + c).detach().double().cpu().numpy() for c in T.CLASSES if hasattr(mod, "weights_" + c)}
+    N = {c: getattr(mod, "norm_" + c).double().cpu().numpy() if hasattr(mod, "norm_" + c) else np.zeros(0) for c in T.CLASSES}
+    return W, N
+
+
+def _oracle(upd1, upd2, h, a, A, H=32):
+    hid, gated = _irreps(H)
+    x, y = np.concatenate([_np(h), _np(a)], 1), _np(A)
+    with np.errstate(invalid="ignore", over="ignore"):
+        u = S.gate_blocks(T.forward(f"{hid}+{hid}", gated, 2, x, y, *_WN(upd1)), H, [(1, H), (2, H)])
+        return T.forward(hid, hid, 2, u, y, *_WN(upd2)) + _np(h)
+
+
+def _two_launch(upd1, upd2, h, a, A):
+    if h.dtype == torch.float32:
+        u, us = upd1.forward_fused([(h, None), (a, None)], A, gate=True, out_scale=10)
+        return upd2.forward_fused([(u, None)], A, gate=False, in_scale=us, residual=h, out_scale=10)
+    u = upd1.forward_fused([(h, None), (a, None)], A, gate=True)
+    return upd2.forward_fused([(u, None)], A, gate=False, residual=h), None
+
+
+def _inputs(B, seed, dtype=torch.float32, spread=True):
+    g = torch.Generator().manual_seed(seed)
+    h, a = torch.randn(B, 288, generator=g), torch.randn(B, 288, generator=g) * 3
+    if spread:   # row magnitudes 1e-4 .. 1e4 inside one tensor
+        rs = 10.0 ** torch.randint(-4, 5, (B, 1), generator=g).float()
+        h, a = h * rs, a * rs
+    A = torch.randn(B, 9, generator=g)
+    return h.to(dtype).to(DEV), a.to(dtype).to(DEV), A.to(DEV)
+
+
+@pytest.mark.parametrize("spread", [False, True])
+@pytest.mark.parametrize("B", [1, 15, 16, 17, 4099])
+def test_fp32_matches_two_launch_and_oracle(B, spread):
+    upd1, upd2 = _pair(32, seed=1)
+    h, a, A = _inputs(B, seed=B, spread=spread)
+    with torch.no_grad():
+        got, sc = upd1.forward_update_pair(upd2, [(h, None), (a, None)], A, residual=h, out_scale=10)
+        assert _lib.load().e3_tp_last_fused_kernel() == b"e3::tp_update_pair_r16_kernel"
+        ref, _ = _two_launch(upd1, upd2, h, a, A)
+    want = _oracle(upd1, upd2, h, a, A)
+    scale = np.abs(want).max()
+    e_fused = np.abs(_np(got) - want).max() / scale
+    e_two = np.abs(_np(ref) - want).max() / scale
+    # per row, relative to the row's own largest value (rows span 8 decades)
+    row = lambda x: float((np.abs(_np(x) - want).max(1) / np.abs(want).max(1)).max())
+    print(f"\nB={B}: fused {e_fused:.2e} (worst row {row(got):.2e}) | two launches {e_two:.2e} (worst row {row(ref):.2e})")
+    if not spread:
+        assert e_fused <= 1e-5 and e_two <= 1e-5
+    else:
+        # rows 1e-4 .. 1e4 share product #1's joint scale in both paths; the per-row scale of u must not lose accuracy
+        assert row(got) <= row(ref) * 1.01 + 1e-7 and e_fused <= 2 * e_two + 1e-7
+    s, inv, _ = expected_scale([got.cpu().numpy()], 10)
+    assert (float(sc[0]), float(sc[1])) == (s, inv)
+
+
+def test_bf16_bit_identical_to_two_launch():
+    upd1, upd2 = _pair(32, seed=2, dtype=torch.bfloat16)
+    h, a, A = _inputs(4099, seed=3, dtype=torch.bfloat16, spread=False)
+    with torch.no_grad():
+        got = upd1.forward_update_pair(upd2, [(h, None), (a, None)], A, residual=h)
+        ref, _ = _two_launch(upd1, upd2, h, a, A)
+    assert got is not None and torch.equal(got, ref)
+
+
+@pytest.mark.parametrize("kind", ["nan", "inf"])
+def test_nonfinite_rows_stay_in_their_row(kind):
+    """A bad value in one row of h or a stays in that row of h' and leaves the scale and every other row alone (the row
+    next to a bad one holds the maximum 1e4, as in tests/test_nonfinite_gpu.py)."""
+    upd1, upd2 = _pair(32, seed=4)
+    B = 203
+    h, a, A = _inputs(B, seed=5, spread=False)
+    h[36, 287] = 1e4
+    bad = [0, 37, 120, B - 1]
+    v = float(kind)
+    h[37, 0] = v
+    a[0, 5] = v
+    a[120, 287] = v
+    h[B - 1, 144] = v
+    with torch.no_grad():
+        got, sc = upd1.forward_update_pair(upd2, [(h, None), (a, None)], A, residual=h, out_scale=10)
+        ref, _ = _two_launch(upd1, upd2, h, a, A)
+    gn = _np(got)
+    badrows = np.flatnonzero(~np.isfinite(gn).all(1))
+    assert sorted(badrows.tolist()) == bad
+    ok = np.setdiff1d(np.arange(B), bad)
+    want = _np(ref)[ok]
+    assert np.abs(gn[ok] - want).max() <= 1e-5 * np.abs(want).max()
+    s, inv, _ = expected_scale([got.cpu().numpy()], 10)
+    assert (float(sc[0]), float(sc[1])) == (s, inv)
+
+
+def test_unsupported_pair_takes_the_fallback():
+    """Hidden 16 has no fused instantiation: the entry reports it and the layer's two launches run unchanged."""
+    from scalable_e3_gnn_amd.segnn import SEGNNLayer
+    upd1, upd2 = _pair(16, seed=6)
+    g = torch.Generator().manual_seed(7)
+    h, a, A = (torch.randn(100, 144, generator=g).to(DEV), torch.randn(100, 144, generator=g).to(DEV),
+               torch.randn(100, 9, generator=g).to(DEV))
+    with torch.no_grad():
+        assert upd1.forward_update_pair(upd2, [(h, None), (a, None)], A, residual=h, out_scale=10) is None
+    assert SEGNNLayer(16, 2).upd1.fused_supported(True)
