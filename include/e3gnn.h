@@ -475,6 +475,39 @@ int e3_edge_geometry_backward_pbc(const float* pos4, const int32_t* rowptr, cons
                                   const float* g_node_a, float* g_pos, void* stream);
 int e3_gather_concat_backward(const float* g_out, int64_t ld_gout, int D, const int32_t* rowptr, const int32_t* src,
                               int64_t N, int n_extra, float* g_h, int64_t ld_gh, float* g_extra, void* stream);
+
+/* =================================================================================================
+ * Strain, virial and stress (first order).  Structure s of an edge = structure of its dst row (structure[dst], NULL = every
+ * row is structure 0); each structure has a 3x3 strain eps_s (strain [S,9] fp32 on the device, row-major eps[3 a + b]).
+ * With r_e the edge vector of the undeformed graph (open box: x_src - x_dst; box != NULL: its minimum image exactly as in
+ * e3_edge_geometry_pbc), the strained vector is
+ *   r'_e = r_e + eps_s r_e      (fp32, per component  r'_a = r_a + (eps[3a] r_0 + eps[3a+1] r_1 + eps[3a+2] r_2))
+ * and Y_e, d_e and A_i are those of r'_e; the edge set is the one of the undeformed graph.  The derivative at eps = 0 is
+ * exact; a finite eps is a first-order tool (finite differences).  At eps = 0 the outputs equal the unstrained entries'.
+ *   dE/deps_s[a,b] = sum over the edges e of s of (dE/dr'_e)_a (r_e)_b
+ *   virial W_s = -dE/deps_s at eps = 0 (not symmetrised: its symmetry is a check);
+ *   stress sigma = (1/V) dE/deps at eps = 0, V = L_x L_y L_z, all three axes periodic (ASE / NequIP / MACE: sigma = -W/V).
+ * Rows with no edges and edges with d = 0 contribute nothing.  A row whose structure id is outside [0, S) reads no strain
+ * and writes no strain gradient: it is computed unstrained.  Units: those of E and pos.
+ * lmax 1 or 2 (edge_y [E,(lmax+1)^2], node_a [N,(lmax+1)^2]); box: host float[3] as in e3_edge_geometry_pbc, or NULL for an
+ * open box.  E3_ERR_INVALID_ARG before any launch for lmax outside {1, 2}, strain NULL, S < 1 or an invalid box.
+ * ================================================================================================= */
+int e3_edge_geometry_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                              const float* box, const float* strain, const int32_t* structure, int S, float* edge_y,
+                              float* edge_d, float* node_a, void* stream);
+/* bytes of the backward's workspace for N rows (needed when S = 1; 9 floats per workgroup, at most 147 456 B) */
+int64_t e3_edge_geometry_backward_strained_workspace_bytes(int64_t N);
+/* Backward of e3_edge_geometry_strained in one pass: g_pos [N,3] (zero-filled by the call; (I + eps_s)^T of the gradient at
+ * r', atomics as e3_edge_geometry_backward) and g_strain [S,9] = dE/deps_s (zero-filled by the call).
+ * S = 1: per-wave register sums and per-workgroup LDS sums written to `workspace`, then a second pass adds them in a fixed
+ * order: g_strain is bitwise reproducible from run to run.  S > 1 (e.g. batched molecules, whose rows are not contiguous
+ * in graph order): one wave reduction per row and one 9-lane atomic add into g_strain[s]: the sums depend on the order of
+ * arrival.  E3_ERR_INVALID_ARG also for g_strain NULL or, when S = 1 and N > 0, a workspace smaller than
+ * e3_edge_geometry_backward_strained_workspace_bytes(N). */
+int e3_edge_geometry_backward_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                       const float* box, const float* strain, const int32_t* structure, int S,
+                                       const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
+                                       float* g_strain, void* workspace, int64_t workspace_bytes, void* stream);
 int e3_gate_blocks_backward(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, float* g_in,
                             int64_t ld_gin, int64_t B, int ns, int nblocks, const int32_t* ls, const int32_t* muls,
                             void* stream);

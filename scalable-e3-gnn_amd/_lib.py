@@ -132,6 +132,13 @@ SIGNATURES = {
                                POINTER(c_int32), c_void_p]),
     "e3_l1tp_backward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, VoidP4, VoidP4, c_void_p, c_int64,
                                  c_void_p, c_int64, c_void_p, VoidP4, c_void_p, c_int64, c_int, c_void_p]),
+    # per-structure strain (box = float[3] as above, or NULL for an open box)
+    "e3_edge_geometry_strained": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ctypes.c_float), c_void_p,
+                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e3_edge_geometry_backward_strained_workspace_bytes": (c_int64, [c_int64]),
+    "e3_edge_geometry_backward_strained": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ctypes.c_float),
+                                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 

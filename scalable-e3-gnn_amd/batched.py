@@ -9,6 +9,8 @@ head is the per-molecule sum of a scalar (`1x0e`) node readout.  The force head 
 through the whole message pass: every stage has a HIP backward (tensor products: `e3_l1tp_backward` / `e3_tp_backward`;
 edge geometry, gather/concat, gates, segment-sum: `e3_*_backward`, csrc/e3_edge_bwd.hip).  First order only: forces can
 be predicted and energies trained on; training ON forces would need the second derivative, which is not implemented.
+Virials and stress are the derivative w.r.t. a zero strain per structure, reduced inside the same geometry backward
+(`e3_edge_geometry_backward_strained`); `PeriodicEnergyModel` is the periodic-box counterpart of `BatchedEnergyModel`.
 """
 from __future__ import annotations
 
@@ -52,6 +54,28 @@ def batched_radius_graph(pos: torch.Tensor, batch: torch.Tensor, r: float):
     return dataclasses.replace(g, pos4=pos4), batch[perm]
 
 
+def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure):
+    """Energy of ``net``'s scalar node readout summed per segment (``seg`` [N] graph order, ``n_seg`` segments; ``seg``
+    None: the 0-d total), and from ONE backward pass through the differentiable chain dE/dpos_g [N,3] (``forces``) and
+    dE/deps [n_strain,3,3] at a zero per-structure strain (``n_strain`` > 0; ``structure`` [N] graph order, None = one
+    structure).  -> (energy, dE/dpos_g | None, dE/deps | None); the energy keeps its graph in training mode."""
+    from . import ops
+    with torch.enable_grad():
+        p = pos_g.detach().float().requires_grad_(forces)
+        eps = torch.zeros((n_strain, 3, 3), dtype=torch.float32, device=p.device, requires_grad=True) if n_strain else None
+        geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p, strain=eps, structure=structure)  # differentiable Y, d, A
+        e_node = net(x_g, g, geometry=geometry)
+        if seg is None:
+            energy = e_node[:, 0].sum()
+        else:
+            energy = torch.zeros(n_seg, dtype=e_node.dtype, device=e_node.device).index_add(0, seg, e_node[:, 0])
+        leaves = ([p] if forces else []) + ([eps] if eps is not None else [])
+        grads = list(torch.autograd.grad(energy.sum(), leaves, retain_graph=net.training))
+    gpos = grads.pop(0) if forces else None
+    geps = grads.pop(0) if eps is not None else None
+    return (energy if net.training else energy.detach()), gpos, geps
+
+
 class BatchedEnergyModel(nn.Module):
     """SEGNN with a scalar node readout summed per molecule: energies [n_mol]."""
 
@@ -59,21 +83,61 @@ class BatchedEnergyModel(nn.Module):
         super().__init__()
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax)
 
-    def forward(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, forces: bool = False):
-        """-> energies [n_mol]; with ``forces=True``: (energies, forces [N,3] = -dE/dpos in the caller's atom order)."""
-        from . import ops
+    def forward(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, forces: bool = False,
+                virial: bool = False):
+        """-> energies [n_mol]; with ``forces=True``: (energies, forces [N,3] = -dE/dpos in the caller's atom order);
+        with ``virial=True`` the per-molecule virials W [n_mol,3,3] = -dE/deps (zero strain per molecule, not
+        symmetrised) come last: (energies, forces, W) or (energies, W)."""
         g, mol = batched_radius_graph(pos, batch, r)
         n_mol = int(batch.max().item()) + 1 if batch.numel() else 0
         perm = g.perm.long()
-        if not forces:
+        if not forces and not virial:
             e_node = self.net(x[perm], g)
             return torch.zeros(n_mol, dtype=e_node.dtype, device=e_node.device).index_add_(0, mol, e_node[:, 0])
-        with torch.enable_grad():
-            pos_g = pos[perm].detach().float().requires_grad_(True)       # graph (Morton) order
-            geometry = ops.edge_geometry(g, lmax=self.net.lmax, pos=pos_g)  # differentiable Y, d, A
-            e_node = self.net(x[perm], g, geometry=geometry)
-            energy = torch.zeros(n_mol, dtype=e_node.dtype, device=e_node.device).index_add(0, mol, e_node[:, 0])
-            (gpos,) = torch.autograd.grad(energy.sum(), pos_g, retain_graph=self.training)
-        f = torch.empty_like(gpos)
-        f[perm] = -gpos
-        return (energy if self.training else energy.detach()), f
+        energy, gpos, geps = _energy_and_gradients(self.net, x[perm], g, pos[perm], mol, n_mol, forces,
+                                                   n_mol if virial else 0, mol if virial else None)
+        out = [energy]
+        if forces:
+            f = torch.empty_like(gpos)
+            f[perm] = -gpos
+            out.append(f)
+        if virial:
+            out.append(-geps)
+        return tuple(out)
+
+
+class PeriodicEnergyModel(nn.Module):
+    """SEGNN with a scalar node readout summed over a periodic (or partly periodic) orthorhombic box: the energy, and on
+    request forces, the virial and the stress of the box (conventions: include/e3gnn.h, e3_edge_geometry_strained).
+    The graph is built inside ``forward`` (``radius_graph(..., periodic=)``)."""
+
+    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2):
+        super().__init__()
+        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax)
+
+    def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo, hi, periodic=True, forces: bool = False,
+                virial: bool = False, stress: bool = False):
+        """x [N, in_dim], pos [N,3] (caller order; coordinates on periodic axes may be unwrapped).  -> the 0-d energy,
+        then whichever of forces [N,3] (= -dE/dpos, caller order), virial W [3,3] (= -dE/deps at eps = 0, not
+        symmetrised) and stress [3,3] (= (1/V) dE/deps = -W/V, V = L_x L_y L_z) were requested, in that order; the
+        energy alone when none was.  ``stress=True`` needs all three axes periodic (ValueError otherwise)."""
+        from .radius_graph import periodic_mask
+        if stress and periodic_mask(periodic, r, lo, hi) != 7:
+            raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
+        g = radius_graph(pos, r, lo, hi, periodic=periodic)
+        perm = g.perm.long()
+        if not (forces or virial or stress):
+            return self.net(x[perm], g)[:, 0].sum()
+        energy, gpos, geps = _energy_and_gradients(self.net, x[perm], g, pos[perm], None, 1, forces,
+                                                   1 if (virial or stress) else 0, None)
+        out = [energy]
+        if forces:
+            f = torch.empty_like(gpos)
+            f[perm] = -gpos
+            out.append(f)
+        if virial:
+            out.append(-geps[0])
+        if stress:
+            V = float(g.box[0]) * float(g.box[1]) * float(g.box[2])
+            out.append((geps[0].double() / V).float())
+        return tuple(out)

@@ -95,6 +95,32 @@ __device__ __forceinline__ void edge_rel(const float4 pj, const float4 pi, const
   }
 }
 
+// per-structure strain of the *_strained geometry entries (include/e3gnn.h): eps [S,9] fp32, row-major (eps[3 a + b]);
+// sid [N] structure id of each dst row, NULL = every row is structure 0
+struct StrainArg {
+  const float* eps;
+  const int32_t* sid;
+  int S;
+};
+// structure of row i, -1 when its id is outside [0, S) (such a row is neither strained nor reduced).  Called by a whole
+// wave on one row: the id is made wave-uniform, so the strain of the row is read with scalar loads into SGPRs
+__device__ __forceinline__ int row_structure(const StrainArg& st, const int64_t i) {
+  const int s = st.sid ? st.sid[i] : 0;
+  return __builtin_amdgcn_readfirstlane((s >= 0 && s < st.S) ? s : -1);
+}
+// eps of structure s into registers (zero for s = -1: no read)
+__device__ __forceinline__ void load_strain(const StrainArg& st, const int s, float e[9]) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) e[k] = s >= 0 ? st.eps[(int64_t)s * 9 + k] : 0.f;
+}
+// r <- r + eps r
+__device__ __forceinline__ void apply_strain(const float e[9], float& rx, float& ry, float& rz) {
+  const float x = rx, y = ry, z = rz;
+  rx = x + (e[0] * x + e[1] * y + e[2] * z);
+  ry = y + (e[3] * x + e[4] * y + e[5] * z);
+  rz = z + (e[6] * x + e[7] * y + e[8] * z);
+}
+
 // host: box[3] of a *_pbc entry (L per axis, 0 = open): finite, no negative length, and 2 r < L on every periodic axis
 inline bool box_valid(const float* box, float r) {
   if (!box) return false;

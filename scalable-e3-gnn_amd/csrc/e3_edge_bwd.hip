@@ -17,17 +17,29 @@ constexpr float kS3 = 1.7320508075688772f, kS5 = 2.2360679774997896f;
 //   g_r      = (g_u - u (u . g_u)) / d + gd u          (0 for d = 0: the forward uses u = 0 there)
 //   gpos[src] += g_r   (atomics),   gpos[dst] -= sum_e g_r   (wave reduction, one atomic per row and component)
 // PBC: r is the minimum image of x_src - x_dst; the shift is piecewise constant, so dr/dx is that of the open box.
-template <int LMAX, bool PBC>
+// STRAIN (r' = r + eps_s r, s = structure of the dst row): g' above is taken at r'; the position gradient is
+// (I + eps_s)^T g', and G_s = dE/deps_s = sum over the structure's edges of g' (x) r (r unstrained) is reduced in the same
+// pass.  S = 1: every lane sums its edges in registers over all of its wave's rows, the workgroup sums its waves through
+// LDS and writes one 9-float partial per block to gpart (fixed grid: the order of every sum is fixed), and
+// strain_partial_sum_kernel adds the partials.  S > 1: the rows of a structure are not contiguous, so each row is
+// wave-reduced and added with one 9-lane atomic into G[s] (order of arrival: not bitwise reproducible).
+template <int LMAX, bool PBC, bool STRAIN>
 __global__ __launch_bounds__(256) void edge_geometry_bwd_kernel(const float4* __restrict__ pos4,
                                                                 const int32_t* __restrict__ rowptr,
                                                                 const int32_t* __restrict__ src, int64_t N,
                                                                 const float* __restrict__ gY, const float* __restrict__ gd,
                                                                 const float* __restrict__ gA, float* __restrict__ gpos,
-                                                                const PbcBox box) {
+                                                                const PbcBox box, const StrainArg st,
+                                                                float* __restrict__ gstrain, float* __restrict__ gpart) {
   constexpr int NY = (LMAX + 1) * (LMAX + 1);
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  float G[9];
+  if constexpr (STRAIN) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = 0.f;
+  }
   for (int64_t i = wave0; i < N; i += nw) {
     const int b = rowptr[i], e = rowptr[i + 1];
     if (b == e) continue;
@@ -36,12 +48,20 @@ __global__ __launch_bounds__(256) void edge_geometry_bwd_kernel(const float4* __
     float ga[NY];
 #pragma unroll
     for (int k = 1; k < NY; ++k) ga[k] = gA ? gA[i * NY + k] * invdeg : 0.f;
+    int srow = 0;
+    float eps[9];
+    if constexpr (STRAIN) {
+      srow = row_structure(st, i);
+      load_strain(st, srow, eps);
+    }
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int q = b + lane; q < e; q += 64) {
       const int j = src[q];
       const float4 pj = pos4[j];
       float rx, ry, rz;
       edge_rel<PBC>(pj, pi, box, rx, ry, rz);
+      const float r0x = rx, r0y = ry, r0z = rz;
+      if constexpr (STRAIN) apply_strain(eps, rx, ry, rz);
       const float d = sqrtf(rx * rx + ry * ry + rz * rz);
       if (!(d > 0.f)) continue;
       const float inv = 1.0f / d;
@@ -59,8 +79,21 @@ __global__ __launch_bounds__(256) void edge_geometry_bwd_kernel(const float4* __
       }
       const float dot = x * ux + y * uy + z * uz;
       const float gdv = gd ? gd[q] : 0.f;
-      const float gx = (ux - x * dot) * inv + gdv * x, gy = (uy - y * dot) * inv + gdv * y,
-                  gz = (uz - z * dot) * inv + gdv * z;
+      float gx = (ux - x * dot) * inv + gdv * x, gy = (uy - y * dot) * inv + gdv * y,
+            gz = (uz - z * dot) * inv + gdv * z;
+      if constexpr (STRAIN) {
+        if (srow >= 0) {
+          G[0] += gx * r0x; G[1] += gx * r0y; G[2] += gx * r0z;
+          G[3] += gy * r0x; G[4] += gy * r0y; G[5] += gy * r0z;
+          G[6] += gz * r0x; G[7] += gz * r0y; G[8] += gz * r0z;
+        }
+        const float tx = gx + (eps[0] * gx + eps[3] * gy + eps[6] * gz);
+        const float ty = gy + (eps[1] * gx + eps[4] * gy + eps[7] * gz);
+        const float tz = gz + (eps[2] * gx + eps[5] * gy + eps[8] * gz);
+        gx = tx; gy = ty; gz = tz;
+      } else {
+        (void)r0x; (void)r0y; (void)r0z;
+      }
       atomicAdd(gpos + (int64_t)j * 3 + 0, gx);
       atomicAdd(gpos + (int64_t)j * 3 + 1, gy);
       atomicAdd(gpos + (int64_t)j * 3 + 2, gz);
@@ -76,7 +109,53 @@ __global__ __launch_bounds__(256) void edge_geometry_bwd_kernel(const float4* __
       atomicAdd(gpos + i * 3 + 1, -sy);
       atomicAdd(gpos + i * 3 + 2, -sz);
     }
+    if constexpr (STRAIN) {
+      if (st.S > 1 && srow >= 0) {
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          for (int o = 32; o > 0; o >>= 1) G[k] += __shfl_xor(G[k], o);
+          if (lane == k) v = G[k];
+          G[k] = 0.f;
+        }
+        if (lane < 9) atomicAdd(gstrain + (int64_t)srow * 9 + lane, v);
+      }
+    }
   }
+  if constexpr (STRAIN) {
+    if (st.S == 1) {
+      __shared__ float part[4][9];
+      const int w = threadIdx.x >> 6;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        for (int o = 32; o > 0; o >>= 1) G[k] += __shfl_xor(G[k], o);
+        if (lane == 0) part[w][k] = G[k];
+      }
+      __syncthreads();
+      if (threadIdx.x < 9)
+        gpart[(int64_t)blockIdx.x * 9 + threadIdx.x] =
+            ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+    }
+  }
+}
+
+// G[k] = sum of the per-block partials gpart[p, k] of edge_geometry_bwd_kernel (S = 1): one wave per component, lanes over
+// the partials in a fixed order (16 loads in flight per lane before their adds), then a fixed butterfly
+__global__ __launch_bounds__(576) void strain_partial_sum_kernel(const float* __restrict__ gpart, int nparts,
+                                                                 float* __restrict__ gstrain) {
+  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+  float acc = 0.f;
+  int p = lane;
+  for (; p + 15 * 64 < nparts; p += 16 * 64) {
+    float v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) v[u] = gpart[(int64_t)(p + u * 64) * 9 + k];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc += v[u];
+  }
+  for (; p < nparts; p += 64) acc += gpart[(int64_t)p * 9 + k];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if (lane == 0) gstrain[k] = acc;
 }
 
 // m[e] = [h[dst] | h[src] | extra[e]]:  g_h[dst] += sum over the row of gm[e, :D] (one atomic per row and column),
@@ -172,20 +251,32 @@ static inline int wave_grid_b(int64_t N) { return (int)std::max<int64_t>(1, std:
 
 using namespace e3;
 
-// box: NULL = open, else validated by the caller
+// box: NULL = open, else validated by the caller; st: NULL = unstrained, else validated by the caller (g_strain [S,9],
+// workspace of e3_edge_geometry_backward_strained_workspace_bytes when S = 1)
 static int edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                                   const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
-                                  const float* box, void* stream) {
+                                  const float* box, const StrainArg* st, float* g_strain, float* gpart, void* stream) {
   if (N < 0 || (lmax != 1 && lmax != 2)) return E3_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (st) E3_HIP_CHECK(hipMemsetAsync(g_strain, 0, (size_t)st->S * 9 * sizeof(float), s));
   if (N == 0) return E3_OK;
   if (!pos4 || !rowptr || !src || !g_pos) return E3_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
   E3_HIP_CHECK(hipMemsetAsync(g_pos, 0, (size_t)N * 3 * sizeof(float), s));
   const PbcBox b = make_box(box);
-  auto kern = lmax == 1 ? (box ? edge_geometry_bwd_kernel<1, true> : edge_geometry_bwd_kernel<1, false>)
-                        : (box ? edge_geometry_bwd_kernel<2, true> : edge_geometry_bwd_kernel<2, false>);
-  hipLaunchKernelGGL(kern, dim3(wave_grid_b(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
-                     g_node_a, g_pos, b);
+  const int grid = wave_grid_b(N);
+  if (!st) {
+    auto kern = lmax == 1 ? (box ? edge_geometry_bwd_kernel<1, true, false> : edge_geometry_bwd_kernel<1, false, false>)
+                          : (box ? edge_geometry_bwd_kernel<2, true, false> : edge_geometry_bwd_kernel<2, false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
+                       g_node_a, g_pos, b, StrainArg{nullptr, nullptr, 0}, nullptr, nullptr);
+  } else {
+    auto kern = lmax == 1 ? (box ? edge_geometry_bwd_kernel<1, true, true> : edge_geometry_bwd_kernel<1, false, true>)
+                          : (box ? edge_geometry_bwd_kernel<2, true, true> : edge_geometry_bwd_kernel<2, false, true>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
+                       g_node_a, g_pos, b, *st, g_strain, gpart);
+    E3_HIP_CHECK(hipGetLastError());
+    if (st->S == 1) hipLaunchKernelGGL(strain_partial_sum_kernel, dim3(1), dim3(576), 0, s, gpart, grid, g_strain);
+  }
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }
@@ -195,14 +286,34 @@ extern "C" {
 int e3_edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                               const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
                               void* stream) {
-  return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, nullptr, stream);
+  return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, nullptr, nullptr, nullptr,
+                                nullptr, stream);
 }
 
 int e3_edge_geometry_backward_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                                   const float box[3], const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
                                   float* g_pos, void* stream) {
   if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
-  return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, box, stream);
+  return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, box, nullptr, nullptr,
+                                nullptr, stream);
+}
+
+int64_t e3_edge_geometry_backward_strained_workspace_bytes(int64_t N) {
+  if (N < 0) return -1;
+  return N == 0 ? 0 : (int64_t)wave_grid_b(N) * 9 * (int64_t)sizeof(float);
+}
+
+int e3_edge_geometry_backward_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                       const float* box, const float* strain, const int32_t* structure, int S,
+                                       const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
+                                       float* g_strain, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (N < 0 || (lmax != 1 && lmax != 2) || !strain || S < 1 || !g_strain || (box && !box_valid(box, 0.0f)))
+    return E3_ERR_INVALID_ARG;
+  if (S == 1 && N > 0 && (!workspace || workspace_bytes < e3_edge_geometry_backward_strained_workspace_bytes(N)))
+    return E3_ERR_INVALID_ARG;
+  const StrainArg st = {strain, structure, S};
+  return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, box, &st, g_strain,
+                                (float*)workspace, stream);
 }
 
 int e3_gather_concat_backward(const float* g_out, int64_t ld_gout, int D, const int32_t* rowptr, const int32_t* src,

@@ -9,24 +9,29 @@ namespace e3 {
 
 constexpr float kSqrt3 = 1.7320508075688772f;
 
-// one wave per dst node: lanes over the row's edges; wave-reduce the mean of Y1
-template <bool PBC>
+// one wave per dst node: lanes over the row's edges; wave-reduce the mean of Y1.
+// STRAIN: r <- r + eps_s r with s the row's structure (StrainArg; read once per row); false = the unstrained kernel
+template <bool PBC, bool STRAIN>
 __global__ __launch_bounds__(256) void edge_geometry_kernel(const float4* __restrict__ pos4,
                                                             const int32_t* __restrict__ rowptr,
                                                             const int32_t* __restrict__ src, int64_t N,
                                                             float4* __restrict__ edge_y, float* __restrict__ edge_d,
-                                                            float4* __restrict__ node_a, const PbcBox box) {
+                                                            float4* __restrict__ node_a, const PbcBox box,
+                                                            const StrainArg st) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
   for (int64_t i = wave0; i < N; i += nw) {
     const int b = rowptr[i], e = rowptr[i + 1];
     const float4 pi = pos4[i];
+    float eps[9];
+    if constexpr (STRAIN) load_strain(st, row_structure(st, i), eps);
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int q = b + lane; q < e; q += 64) {
       const float4 pj = pos4[src[q]];
       float rx, ry, rz;
       edge_rel<PBC>(pj, pi, box, rx, ry, rz);
+      if constexpr (STRAIN) apply_strain(eps, rx, ry, rz);
       const float d = sqrtf(rx * rx + ry * ry + rz * rz);
       const float s = d > 0.f ? kSqrt3 / d : 0.f;
       const float4 y = make_float4(1.0f, s * rx, s * ry, s * rz);
@@ -123,12 +128,13 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const float* __restric
 
 
 // l <= 2 variant: Y [E,9] = [1 | sqrt3 u | sqrt5 b(u)], b = l=2 basis of oracle/cg.py; A [N,9] = [1 | mean Y_1..8]
-template <bool PBC>
+template <bool PBC, bool STRAIN>
 __global__ __launch_bounds__(256) void edge_geometry_l2_kernel(const float4* __restrict__ pos4,
                                                                const int32_t* __restrict__ rowptr,
                                                                const int32_t* __restrict__ src, int64_t N,
                                                                float* __restrict__ edge_y, float* __restrict__ edge_d,
-                                                               float* __restrict__ node_a, const PbcBox box) {
+                                                               float* __restrict__ node_a, const PbcBox box,
+                                                               const StrainArg st) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -136,11 +142,14 @@ __global__ __launch_bounds__(256) void edge_geometry_l2_kernel(const float4* __r
   for (int64_t i = wave0; i < N; i += nw) {
     const int b = rowptr[i], e = rowptr[i + 1];
     const float4 pi = pos4[i];
+    float eps[9];
+    if constexpr (STRAIN) load_strain(st, row_structure(st, i), eps);
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int q = b + lane; q < e; q += 64) {
       const float4 pj = pos4[src[q]];
       float rx, ry, rz;
       edge_rel<PBC>(pj, pi, box, rx, ry, rz);
+      if constexpr (STRAIN) apply_strain(eps, rx, ry, rz);
       const float d = sqrtf(rx * rx + ry * ry + rz * rz);
       const float inv = d > 0.f ? 1.0f / d : 0.f;
       const float x = rx * inv, y = ry * inv, z = rz * inv;
@@ -231,22 +240,25 @@ static inline int wave_grid(int64_t N) { return (int)std::max<int64_t>(1, std::m
 
 using namespace e3;
 
-// lmax 1 / 2, open (box NULL) or periodic (box validated by the caller)
+// lmax 1 / 2, open (box NULL) or periodic (box validated by the caller); st NULL = unstrained, else validated by the caller
 static int edge_geometry(int lmax, const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, float* edge_y,
-                         float* edge_d, float* node_a, const float* box, void* stream) {
+                         float* edge_d, float* node_a, const float* box, const StrainArg* st, void* stream) {
   if (N < 0) return E3_ERR_INVALID_ARG;
   if (N == 0) return E3_OK;
   if (!pos4 || !rowptr || !src || (!edge_y && !node_a)) return E3_ERR_INVALID_ARG;
   const PbcBox b = make_box(box);
+  const StrainArg sa = st ? *st : StrainArg{nullptr, nullptr, 0};
   const hipStream_t s = (hipStream_t)stream;
   if (lmax == 1) {
-    auto kern = box ? edge_geometry_kernel<true> : edge_geometry_kernel<false>;
+    auto kern = st ? (box ? edge_geometry_kernel<true, true> : edge_geometry_kernel<false, true>)
+                   : (box ? edge_geometry_kernel<true, false> : edge_geometry_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3(wave_grid(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, (float4*)edge_y,
-                       edge_d, (float4*)node_a, b);
+                       edge_d, (float4*)node_a, b, sa);
   } else {
-    auto kern = box ? edge_geometry_l2_kernel<true> : edge_geometry_l2_kernel<false>;
+    auto kern = st ? (box ? edge_geometry_l2_kernel<true, true> : edge_geometry_l2_kernel<false, true>)
+                   : (box ? edge_geometry_l2_kernel<true, false> : edge_geometry_l2_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3(wave_grid(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, edge_y, edge_d,
-                       node_a, b);
+                       node_a, b, sa);
   }
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
@@ -256,13 +268,13 @@ extern "C" {
 
 int e3_edge_geometry(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, float* edge_y,
                      float* edge_d, float* node_a, void* stream) {
-  return edge_geometry(1, pos4, rowptr, src, N, edge_y, edge_d, node_a, nullptr, stream);
+  return edge_geometry(1, pos4, rowptr, src, N, edge_y, edge_d, node_a, nullptr, nullptr, stream);
 }
 
 int e3_edge_geometry_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float box[3],
                          float* edge_y, float* edge_d, float* node_a, void* stream) {
   if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
-  return edge_geometry(1, pos4, rowptr, src, N, edge_y, edge_d, node_a, box, stream);
+  return edge_geometry(1, pos4, rowptr, src, N, edge_y, edge_d, node_a, box, nullptr, stream);
 }
 
 int e3_gather_concat(const float* h, int64_t ld_h, int D, const int32_t* rowptr, const int32_t* src, int64_t N,
@@ -311,13 +323,21 @@ int e3_segment_sum_bf16(const void* msg, int64_t ld_msg, const int32_t* rowptr, 
 
 int e3_edge_geometry_l2(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, float* edge_y,
                         float* edge_d, float* node_a, void* stream) {
-  return edge_geometry(2, pos4, rowptr, src, N, edge_y, edge_d, node_a, nullptr, stream);
+  return edge_geometry(2, pos4, rowptr, src, N, edge_y, edge_d, node_a, nullptr, nullptr, stream);
 }
 
 int e3_edge_geometry_l2_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float box[3],
                             float* edge_y, float* edge_d, float* node_a, void* stream) {
   if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
-  return edge_geometry(2, pos4, rowptr, src, N, edge_y, edge_d, node_a, box, stream);
+  return edge_geometry(2, pos4, rowptr, src, N, edge_y, edge_d, node_a, box, nullptr, stream);
+}
+
+int e3_edge_geometry_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                              const float* box, const float* strain, const int32_t* structure, int S, float* edge_y,
+                              float* edge_d, float* node_a, void* stream) {
+  if ((lmax != 1 && lmax != 2) || !strain || S < 1 || (box && !box_valid(box, 0.0f))) return E3_ERR_INVALID_ARG;
+  const StrainArg st = {strain, structure, S};
+  return edge_geometry(lmax, pos4, rowptr, src, N, edge_y, edge_d, node_a, box, &st, stream);
 }
 
 int e3_gate_blocks(const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t B, int ns, int nblocks,

@@ -25,7 +25,7 @@ def _wants_grad(*ts) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
-def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True):
+def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True, strain=None, structure=None):
     N, E, dev = g.rowptr.numel() - 1, g.num_edges, pos4.device
     ny = (lmax + 1) ** 2
     Y = torch.empty((E, ny), dtype=torch.float32, device=dev) if want_edge else None
@@ -35,7 +35,12 @@ def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True)
     outs = (Y.data_ptr() if Y is not None else None, d.data_ptr() if d is not None else None,
             A.data_ptr() if A is not None else None, _stream(pos4))
     with torch.cuda.device(dev):
-        if g.box is not None:  # periodic box: minimum-image edge vectors
+        if strain is not None:  # [S,3,3] contiguous fp32, structure [N] int32 | None (checked by _strain_args)
+            _lib.check(_lib.load().e3_edge_geometry_strained(
+                pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, g.box_arg, strain.data_ptr(),
+                structure.data_ptr() if structure is not None else None, strain.shape[0], *outs),
+                "e3_edge_geometry_strained")
+        elif g.box is not None:  # periodic box: minimum-image edge vectors
             _lib.check(getattr(_lib.load(), fn + "_pbc")(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
                                                          g.box_arg, *outs), fn + "_pbc")
         else:
@@ -44,56 +49,108 @@ def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True)
     return Y, d, A
 
 
+def _strain_args(strain, structure, g):
+    """-> (strain as [S,3,3] contiguous fp32, structure as [N] contiguous int32 | None).  ValueError for a wrong shape,
+    RuntimeError for a tensor that is not on a ROCm device (or a strain that is not fp32)."""
+    N = g.rowptr.numel() - 1
+    if tuple(strain.shape) == (3, 3):
+        strain = strain.reshape(1, 3, 3)
+    if strain.dim() != 3 or tuple(strain.shape[1:]) != (3, 3) or strain.shape[0] < 1:
+        raise ValueError(f"strain must be [S,3,3] (S >= 1) or [3,3], got {tuple(strain.shape)}")
+    if structure is not None:
+        if structure.dim() != 1 or structure.shape[0] != N:
+            raise ValueError(f"structure must be [N] = [{N}] (graph order), got {tuple(structure.shape)}")
+        if structure.dtype.is_floating_point or structure.dtype.is_complex or structure.dtype == torch.bool:
+            raise ValueError(f"structure must be an integer tensor, got {structure.dtype}")
+    _check(strain, "strain")
+    if structure is not None:
+        if not structure.is_cuda:
+            raise RuntimeError("structure: ROCm tensor required (no CPU path)")
+        structure = structure.to(torch.int32).contiguous()
+    return strain.contiguous(), structure
+
+
 class _EdgeGeometryFn(torch.autograd.Function):
-    """pos [N,3] (graph order) -> Y, d, A; backward = e3_edge_geometry_backward (dY/dpos, dd/dpos, dA/dpos)."""
+    """pos [N,3] (graph order) -> Y, d, A; backward = e3_edge_geometry_backward (dY/dpos, dd/dpos, dA/dpos).
+    With a strain [S,3,3] (and structure [N] int32 | None) the strained entries run instead, and ONE backward launch
+    (e3_edge_geometry_backward_strained) returns the gradients of both pos and strain."""
 
     @staticmethod
-    def forward(ctx, pos, g, lmax):
+    def forward(ctx, pos, strain, g, lmax, structure):
         pos4 = torch.zeros((pos.shape[0], 4), dtype=torch.float32, device=pos.device)
         pos4[:, :3] = pos
-        Y, d, A = _edge_geometry_raw(pos4, g, True, True, lmax)
-        ctx.g, ctx.lmax = g, lmax
-        ctx.save_for_backward(pos4)
+        Y, d, A = _edge_geometry_raw(pos4, g, True, True, lmax, strain=strain, structure=structure)
+        ctx.g, ctx.lmax, ctx.structure = g, lmax, structure
+        ctx.save_for_backward(pos4, strain)
         return Y, d, A
 
     @staticmethod
     def backward(ctx, gY, gd, gA):
-        (pos4,) = ctx.saved_tensors
+        pos4, strain = ctx.saved_tensors
         g = ctx.g
         N = pos4.shape[0]
         gpos = torch.empty((N, 3), dtype=torch.float32, device=pos4.device)
         c = lambda t: t.contiguous() if t is not None else None
         gY, gd, gA = c(gY), c(gd), c(gA)
         p = lambda t: t.data_ptr() if t is not None else None
+        gstrain = None
         with torch.cuda.device(pos4.device):
-            if g.box is not None:
-                _lib.check(_lib.load().e3_edge_geometry_backward_pbc(
+            lib = _lib.load()
+            if strain is not None:
+                gstrain = torch.empty_like(strain)
+                ws = torch.empty(max(1, lib.e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
+                                 device=pos4.device)
+                _lib.check(lib.e3_edge_geometry_backward_strained(
+                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.box_arg, strain.data_ptr(),
+                    p(ctx.structure), strain.shape[0], p(gY), p(gd), p(gA), gpos.data_ptr(), gstrain.data_ptr(),
+                    ws.data_ptr(), ws.numel(), _stream(pos4)), "e3_edge_geometry_backward_strained")
+            elif g.box is not None:
+                _lib.check(lib.e3_edge_geometry_backward_pbc(
                     pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.box_arg, p(gY), p(gd), p(gA),
                     gpos.data_ptr(), _stream(pos4)), "e3_edge_geometry_backward_pbc")
             else:
-                _lib.check(_lib.load().e3_edge_geometry_backward(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(),
-                                                                 N, ctx.lmax, p(gY), p(gd), p(gA), gpos.data_ptr(),
-                                                                 _stream(pos4)), "e3_edge_geometry_backward")
-        return gpos, None, None
+                _lib.check(lib.e3_edge_geometry_backward(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(),
+                                                         N, ctx.lmax, p(gY), p(gd), p(gA), gpos.data_ptr(),
+                                                         _stream(pos4)), "e3_edge_geometry_backward")
+        return gpos, gstrain, None, None, None
 
 
 def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int = 1, pos: torch.Tensor | None = None,
-                  want_edge=True):
+                  want_edge=True, strain: torch.Tensor | None = None, structure: torch.Tensor | None = None):
     """-> Y [E,(lmax+1)^2] | None, d [E] | None, A [N,(lmax+1)^2] | None.  ``want_edge=False``: only the node attribute
     (the fused message kernel computes the spherical harmonics of its edges itself).
 
     ``pos`` [N,3] (graph order, i.e. ``original_pos[g.perm]``): when given and it requires grad, the three outputs are
     differentiable w.r.t. it (forces = -dE/dpos); otherwise the graph's own ``pos4`` is used.  A periodic graph
-    (``g.box``) takes the minimum image of every edge vector, so ``pos`` may be the unwrapped coordinates."""
+    (``g.box``) takes the minimum image of every edge vector, so ``pos`` may be the unwrapped coordinates.
+
+    ``strain`` [S,3,3] (or [3,3]: one structure), fp32 on the device, and ``structure`` [N] integer structure id of every
+    row (graph order; None = every row is structure 0): every edge vector r of structure s (the structure of its dst row)
+    becomes r + strain[s] r before Y, d and A are formed (include/e3gnn.h, e3_edge_geometry_strained).  When ``pos`` or
+    ``strain`` requires grad, the outputs are differentiable w.r.t. both (virial = -dE/dstrain at strain = 0, stress =
+    dE/dstrain / V); a strain without grad still deforms the forward.  ``strain=None`` is the unstrained call."""
     _check(g.pos4, "pos4")
-    if pos is not None and _wants_grad(pos):
+    if strain is None:
+        if structure is not None:
+            raise ValueError("structure= is the structure of each row for a strain=; it needs strain=")
+        if pos is not None and _wants_grad(pos):
+            _check(pos, "pos")
+            return _EdgeGeometryFn.apply(pos, None, g, lmax, None)
+        pos4 = g.pos4
+        if pos is not None:
+            pos4 = torch.zeros_like(g.pos4)
+            pos4[:, :3] = pos
+        return _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge)
+    eps, sid = _strain_args(strain, structure, g)
+    if pos is not None:
         _check(pos, "pos")
-        return _EdgeGeometryFn.apply(pos, g, lmax)
+    if _wants_grad(pos, strain):
+        return _EdgeGeometryFn.apply(pos if pos is not None else g.pos4[:, :3], eps, g, lmax, sid)
     pos4 = g.pos4
     if pos is not None:
         pos4 = torch.zeros_like(g.pos4)
         pos4[:, :3] = pos
-    return _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge)
+    return _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge, strain=eps, structure=sid)
 
 
 class _GatherConcatFn(torch.autograd.Function):
