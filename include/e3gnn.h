@@ -236,6 +236,37 @@ int e3_halo_select_fill(const float* pos_wrapped, int64_t n, const float lo[3], 
                         const e3_halo_entry* entries, int n_entries, int64_t total, int32_t* idx, float* ghost_pos,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Morton-range halo (sharding.MortonPartition / MortonHalo): equal-COUNT ownership of a non-uniform cloud, open boxes only.
+ *   grid   : the domain lo[3] / hi[3] (host fp32) cut into n_cells[a] cells per axis, each a power of two in [1, 128];
+ *            cell and key of a position exactly as in e3_rg_sort_count: c_a = clamp(floorf(fl32(fl32(p_a - lo_a) * inv_a)),
+ *            0, n_a - 1), inv_a = fl32(n_a / fl32(hi_a - lo_a)), key = Morton interleave of (cx, cy, cz), x lowest bit.
+ *   keys   : e3_morton_keys writes key_i (int32) of every position: the input of the partition's histogram.
+ *   owner  : splitters[n_ranks + 1] (host int32, non-decreasing, splitters[0] = 0): rank q owns the cells with
+ *            splitters[q] <= key < splitters[q + 1]; equal neighbours = a rank that owns nothing; a key at or beyond the
+ *            last splitter belongs to the last rank.
+ *   select : particle i (owned by self_rank) goes to rank q != self_rank iff q owns at least one cell (x, y, z) with
+ *            cell(fl32(p_a - r)) <= c_a <= cell(fl32(p_a + r)) on every axis.  Cells are at least r wide, so these are at
+ *            most 3 (4 under adverse rounding of p +- r) cells per axis, and rounding is monotone: every p' with
+ *            |p'_a - p_a| <= r on every axis lies in one of them, whatever fp32 does to p +- r.
+ *   output : idx [total] int32, grouped by destination rank ascending, ascending particle ids inside a group (the order of
+ *            nonzero() on a rank-major [n_ranks, n] mask); counts[q] (device, n_ranks values, counts[self_rank] = 0) = the
+ *            size of group q, total = sum of counts.
+ * Call sequence: e3_morton_select_workspace_bytes -> e3_morton_select_count (counts) -> read counts -> e3_morton_select_fill
+ *   (idx; the same workspace, grid, splitters and r; `total` = the capacity of idx).
+ * E3_ERR_INVALID_ARG before any launch (and before any HIP call) for n_ranks outside [1, 64], self_rank outside the ranks,
+ * splitters that decrease or do not start at 0, n_cells not powers of two in [1, 128], a cell narrower than r on an axis with
+ * more than one cell (fl32(hi_a - lo_a) / n_a < r; a single cell is selected whatever r is), r <= 0 or non-finite, a non-finite or empty box, or n * n_ranks >= 2^31 - 1. */
+#define E3_MORTON_MAX_RANKS 64
+int e3_morton_keys(const float* pos, int64_t n, const float lo[3], const float hi[3], const int32_t n_cells[3], int32_t* keys,
+                   void* stream);
+int64_t e3_morton_select_workspace_bytes(int64_t n, int n_ranks);
+int e3_morton_select_count(const float* pos, int64_t n, const float lo[3], const float hi[3], const int32_t n_cells[3], float r,
+                           const int32_t* splitters, int n_ranks, int self_rank, int32_t* counts, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+int e3_morton_select_fill(const float* pos, int64_t n, const float lo[3], const float hi[3], const int32_t n_cells[3], float r,
+                          const int32_t* splitters, int n_ranks, int self_rank, int64_t total, int32_t* idx, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* =================================================================================================
  * General SH tensor product, l <= 2 (builder-defined generalisation of the reference operator, which
  * hard-asserts lmax == 1, l1_tensor_prod.py:13-14).

@@ -22,6 +22,7 @@ _lib = None
 
 VoidP4 = c_void_p * 4
 Float3 = ctypes.c_float * 3  # a host float[3] argument (periodic box lengths)
+Int3 = c_int32 * 3           # a host int32[3] argument (cells per axis)
 
 
 class HaloEntry(ctypes.Structure):
@@ -63,6 +64,13 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_int64, c_void_p]),
     "e3_halo_select_fill": (c_int, [c_void_p, c_int64, Float3, Float3, c_int32, ctypes.c_float, c_void_p, c_int, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    # Morton-range halo (n_cells = int32[3], splitters = host int32[n_ranks + 1])
+    "e3_morton_keys": (c_int, [c_void_p, c_int64, Float3, Float3, Int3, c_void_p, c_void_p]),
+    "e3_morton_select_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "e3_morton_select_count": (c_int, [c_void_p, c_int64, Float3, Float3, Int3, ctypes.c_float, POINTER(c_int32), c_int,
+                                       c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_morton_select_fill": (c_int, [c_void_p, c_int64, Float3, Float3, Int3, ctypes.c_float, POINTER(c_int32), c_int,
+                                      c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "e3_tp_plan_create": (c_int, [POINTER(c_int32), c_int, c_int, POINTER(c_int32), c_int, POINTER(c_void_p)]),
     "e3_tp_plan_destroy": (c_int, [c_void_p]),
     "e3_tp_in1_dim": (c_int, [c_void_p]),

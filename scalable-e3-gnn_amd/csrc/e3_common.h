@@ -82,6 +82,24 @@ __device__ __forceinline__ float wrap_coord(const float p, const float lo, const
   else if (w < lo) w = __fadd_rn(w, L);
   return w;
 }
+// cell grid of the graph builder (include/e3gnn.h, e3_rg_sort_count), shared with the Morton partition of the sharded path:
+// 30-bit Morton interleave of the cell coordinates (x lowest bit) and the cell of one coordinate, explicitly rounded
+__host__ __device__ inline uint32_t spread3(uint32_t v) {  // 10 bits -> every third bit
+  v &= 0x3ff;
+  v = (v | (v << 16)) & 0x030000FF;
+  v = (v | (v << 8)) & 0x0300F00F;
+  v = (v | (v << 4)) & 0x030C30C3;
+  v = (v | (v << 2)) & 0x09249249;
+  return v;
+}
+__host__ __device__ inline uint32_t morton3(int cx, int cy, int cz) {
+  return spread3((uint32_t)cx) | (spread3((uint32_t)cy) << 1) | (spread3((uint32_t)cz) << 2);
+}
+__device__ __forceinline__ int cell_of(float p, float lo, float inv, int n) {
+  float t = __fmul_rn(__fsub_rn(p, lo), inv);
+  int c = (int)floorf(t);
+  return c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
+}
 // edge vector x_src - x_dst of the geometry kernels; PBC: its minimum image (the rint form, so unwrapped coordinates work too)
 template <bool PBC>
 __device__ __forceinline__ void edge_rel(const float4 pj, const float4 pi, const PbcBox& box, float& rx, float& ry,

@@ -13,14 +13,6 @@ namespace e3 {
 
 constexpr int kCandCap = 1024;  // candidates staged per chunk (16 KiB of LDS per wave)
 
-__host__ __device__ inline uint32_t spread3(uint32_t v) {  // 10 bits -> every third bit
-  v &= 0x3ff;
-  v = (v | (v << 16)) & 0x030000FF;
-  v = (v | (v << 8)) & 0x0300F00F;
-  v = (v | (v << 4)) & 0x030C30C3;
-  v = (v | (v << 2)) & 0x09249249;
-  return v;
-}
 __host__ __device__ inline uint32_t compact3(uint32_t v) {
   v &= 0x09249249;
   v = (v | (v >> 2)) & 0x030C30C3;
@@ -29,10 +21,6 @@ __host__ __device__ inline uint32_t compact3(uint32_t v) {
   v = (v | (v >> 16)) & 0x3ff;
   return v;
 }
-__host__ __device__ inline uint32_t morton3(int cx, int cy, int cz) {
-  return spread3((uint32_t)cx) | (spread3((uint32_t)cy) << 1) | (spread3((uint32_t)cz) << 2);
-}
-
 struct RgDev {
   float lo[3], inv[3];
   int n[3];
@@ -56,12 +44,6 @@ __device__ __forceinline__ float3 load_pos(const float* __restrict__ pos, const 
     if (pb.periodic & 4) p.z = wrap_coord(p.z, g.lo[2], pb.hi[2], pb.L[2], pb.invL[2]);
   }
   return p;
-}
-
-__device__ __forceinline__ int cell_of(float p, float lo, float inv, int n) {
-  float t = __fmul_rn(__fsub_rn(p, lo), inv);
-  int c = (int)floorf(t);
-  return c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
 }
 
 template <bool PBC>

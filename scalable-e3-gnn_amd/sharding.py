@@ -16,15 +16,30 @@ box, wrapped modulo ``dims`` on periodic axes, and ``t`` (whole box lengths per 
                      isend/irecv), the interior edges' message kernel runs meanwhile, ``finish`` waits and writes the ghost
                      rows of ``h`` IN PLACE (inference only: see ``finish``), then the boundary edges run.
 
-Two layouts are built on it:
+Three layouts are built on it:
 
   * ``SlabHalo``   — slabs along x (grid N x 1 x 1): what ``bench.py --gpus N`` uses for WEAK scaling (N unit cubes side by
                      side, 1 M particles each): a face costs r / 1 = 1.8 % ghosts per side, every rank has <= 2 neighbours.
   * ``GridHalo((2, 2, 2), ...)`` — octants of ONE box, i.e. the top level of the Morton order (each octant is one contiguous
                      Morton key range): the STRONG-scaling layout.  A unit cube cut 8 ways costs ~3 r / (1/2)
                      = 11 % ghosts per rank spread over 7 neighbours (7 xGMI links) against 2 r / (1/8) = 29 % over 2 links
-                     for slabs of width 1/8; tests/test_sharding_gloo.py prints both.  (Equal-COUNT Morton ranges for a
-                     non-uniform cloud are not implemented: boxes are equal-volume.)
+                     for slabs of width 1/8; tests/test_sharding_gloo.py prints both.  Boxes are equal-VOLUME.
+  * ``MortonHalo(MortonPartition(lo, hi, r, world).fit(pos))`` -- equal-COUNT Morton key ranges for a non-uniform cloud in
+                     an open box.  The box is cut into a power-of-two grid of cells at least ``r`` wide, a
+                     particle's key is the Morton interleave of its cell (the graph builder's fp32 ``cell_of``), and rank q
+                     owns the keys in ``[s_q, s_{q+1})``; ``fit`` takes the splitters from the global key histogram (one
+                     ``all_reduce``), ``s_q`` = the smallest key k with ``P * #(key < k) >= q N``.  A cell is never split,
+                     so ``|n_q - N/P| < max(hist)``: every rank is within the fullest cell of the mean.  The regions are not
+                     boxes; the halo has one entry per other rank (translation 0), and an owned particle p goes to rank q iff
+                     q owns a cell of ``[cell(fl32(p - r)), cell(fl32(p + r))]`` on every axis.  Rounding is monotone, so
+                     every p' within r of p on every axis lies in one of those cells: a rank's ghosts are a superset of what
+                     its owned rows need, with the open halo's rounding contract (a pair within about one ulp of the cutoff
+                     may differ; exact for dyadic inputs).  On ROCm tensors the selection is one HIP launch pair
+                     (``csrc/e3_morton_halo.hip``), on CPU tensors ``select_morton_torch``, bit for bit the same.  Peers
+                     with nothing to exchange cost one count message per ``setup`` and nothing per layer.  Not covered:
+                     periodic boxes (``GridHalo(periodic=)`` is the route), splitting ONE over-full cell (the bound above
+                     is as good as the fullest cell is small; ``max_bits`` caps the grid at 2^7 cells per axis), and
+                     ``bench.py --gpus N``, which keeps its slabs.
 
 Open box: an entry's ghosts are the owned particles in ``[blo - r, bhi + r)`` of the peer's box, bounds in the positions'
 dtype, one torch mask and ONE ``nonzero`` over all entries; positions and features keep their dtypes.
@@ -43,8 +58,9 @@ HIP launch pair (``csrc/e3_halo.hip``); on CPU tensors (gloo rehearsal) a torch 
 Self entries are served by local copies, never by ``torch.distributed`` (world 1 needs no process group).  The others are
 point-to-point traffic between adjacent boxes (``batch_isend_irecv`` = grouped ncclSend/ncclRecv on RCCL: every pair talks
 over its own xGMI link; no ring, no collective over all ranks), posted per peer in tag order.  Host syncs: two per graph
-build (the selection -- open: the ``nonzero``; periodic: one read of the counts --, one read of the outgoing and incoming
-counts), one per graph in ``split_graph`` (three edge counts), none per layer.
+build (the selection -- open: the ``nonzero``; periodic and Morton ranges: one read of the counts --, one read of the outgoing
+and incoming counts), one per graph in ``split_graph`` (three edge counts), none per layer; ``MortonPartition.fit`` reads the
+key histogram once.
 """
 from __future__ import annotations
 
@@ -300,12 +316,15 @@ class GridHalo:
         for d, s in staged:
             d.copy_(s)
 
+    def _check_cutoff(self, pos, r):
+        check_cutoff(self.dims, self.lo, self.hi, self._axes, r)
+
     # -- once per graph build -------------------------------------------------------------------------
     def setup(self, pos: torch.Tensor, feats: torch.Tensor, r: float):
         """pos [n,3], feats [n,F] of the owned particles -> (local_pos, local_feats) = ``[owned | ghosts]``, the ghosts in
         entry order (``images``).  Positions and features travel in their own dtypes (periodic: positions fp32, the owned
         ones wrapped)."""
-        check_cutoff(self.dims, self.lo, self.hi, self._axes, r)        # ValueError before any transfer
+        self._check_cutoff(pos, r)                                        # ValueError before any transfer
         dev = pos.device
         n = pos.shape[0]
         pos, idx, cnt, gpos = self._select(pos, r)                        # host sync #1
@@ -431,3 +450,283 @@ class SlabHalo(GridHalo):
         by = {d: c for (_, d, _), c in zip(self.images, self.recv_counts)}
         self.n_ghost_left, self.n_ghost_right = by.get((-1, 0, 0), 0), by.get((1, 0, 0), 0)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# equal-COUNT Morton key ranges (open boxes): MortonPartition (ownership) + MortonHalo (ghosts of regions that are not boxes)
+# ---------------------------------------------------------------------------------------------------------------------
+MORTON_MAX_RANKS = 64     # E3_MORTON_MAX_RANKS of include/e3gnn.h: the destinations of a particle are one 64-bit mask
+
+
+def _spread3(v: torch.Tensor) -> torch.Tensor:
+    """csrc/e3_common.h ``spread3`` on an integer tensor: 10 bits -> every third bit."""
+    v = v & 0x3FF
+    v = (v | (v << 16)) & 0x030000FF
+    v = (v | (v << 8)) & 0x0300F00F
+    v = (v | (v << 4)) & 0x030C30C3
+    v = (v | (v << 2)) & 0x09249249
+    return v
+
+
+def _compact3(v: np.ndarray) -> np.ndarray:
+    v = v & 0x09249249
+    v = (v | (v >> 2)) & 0x030C30C3
+    v = (v | (v >> 4)) & 0x0300F00F
+    v = (v | (v >> 8)) & 0x030000FF
+    v = (v | (v >> 16)) & 0x3FF
+    return v
+
+
+def _cells_torch(x, lo_a, inv_a, n_a):
+    """The graph builder's ``cell_of`` of one fp32 coordinate column, each operation rounded once -> int64."""
+    return torch.floor((x - lo_a) * inv_a).clamp_(0, n_a - 1).long()
+
+
+def _morton_grid_args(lo, hi, n_cells):
+    lo32, hi32 = [_f32(v) for v in lo], [_f32(v) for v in hi]
+    L = [_f32(np.float32(hi32[a]) - np.float32(lo32[a])) for a in range(3)]
+    inv = [float(np.float32(n_cells[a]) / np.float32(L[a])) for a in range(3)]
+    return lo32, hi32, inv
+
+
+def _check_f32_pos(pos, what):
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
+        raise TypeError(f"{what} positions must be [n,3] float32, got {tuple(pos.shape)} {pos.dtype}")
+
+
+def morton_keys_torch(pos, lo, hi, n_cells):
+    """Torch restatement of ``e3_morton_keys`` (any device): Morton cell key of every fp32 position -> int64 [n]."""
+    _check_f32_pos(pos, "Morton partition")
+    lo32, _, inv = _morton_grid_args(lo, hi, n_cells)
+    c = [_cells_torch(pos[:, a], lo32[a], inv[a], int(n_cells[a])) for a in range(3)]
+    return _spread3(c[0]) | (_spread3(c[1]) << 1) | (_spread3(c[2]) << 2)
+
+
+def morton_keys(pos, lo, hi, n_cells):
+    """``morton_keys_torch``'s result, bit for bit; ROCm tensors: the HIP kernel ``e3_morton_keys``."""
+    if not pos.is_cuda:
+        return morton_keys_torch(pos, lo, hi, n_cells)
+    from . import _lib
+    _check_f32_pos(pos, "Morton partition")
+    lib = _lib.load()
+    pos = pos.contiguous()
+    n = pos.shape[0]
+    keys = torch.empty(n, dtype=torch.int32, device=pos.device)
+    with torch.cuda.device(pos.device):
+        _lib.check(lib.e3_morton_keys(pos.data_ptr(), n, _lib.Float3(*lo), _lib.Float3(*hi), _lib.Int3(*n_cells),
+                                      keys.data_ptr(), torch.cuda.current_stream(pos.device).cuda_stream), "e3_morton_keys")
+    return keys.long()
+
+
+def select_morton_torch(pos, lo, hi, n_cells, r, splitters, self_rank):
+    """Torch restatement of ``e3_morton_select_count`` / ``_fill`` (any device): -> (idx [total] int64, counts (list of
+    ``len(splitters) - 1`` ints)).  Owned particle ``p`` goes to rank ``q != self_rank`` iff ``q`` owns a cell of
+    ``[cell(fl32(p - r)), cell(fl32(p + r))]`` on every axis; grouped by rank, ascending ids inside a group."""
+    _check_f32_pos(pos, "Morton halo")
+    P = len(splitters) - 1
+    dev, n = pos.device, pos.shape[0]
+    if n == 0 or P == 1:
+        return torch.empty(0, dtype=torch.long, device=dev), [0] * P
+    lo32, _, inv = _morton_grid_args(lo, hi, n_cells)
+    r32 = _f32(r)
+    c0 = [_cells_torch(pos[:, a] - r32, lo32[a], inv[a], int(n_cells[a])) for a in range(3)]
+    c1 = [_cells_torch(pos[:, a] + r32, lo32[a], inv[a], int(n_cells[a])) for a in range(3)]
+    span = torch.stack([(c1[a] - c0[a]).max() for a in range(3)]).tolist()      # <= 2 (3 under adverse rounding) per axis
+    inner = torch.as_tensor(list(splitters[1:P]), dtype=torch.long, device=dev)
+    ids = torch.arange(n, device=dev)
+    mask = torch.zeros((P, n), dtype=torch.bool, device=dev)
+    for dz in range(span[2] + 1):
+        for dy in range(span[1] + 1):
+            for dx in range(span[0] + 1):
+                x, y, z = c0[0] + dx, c0[1] + dy, c0[2] + dz
+                ok = (x <= c1[0]) & (y <= c1[1]) & (z <= c1[2])
+                key = _spread3(x) | (_spread3(y) << 1) | (_spread3(z) << 2)
+                owner = torch.searchsorted(inner, key, right=True)
+                mask[owner[ok], ids[ok]] = True
+    mask[self_rank] = False
+    dest, idx = mask.nonzero(as_tuple=True)
+    return idx, [int(v) for v in torch.bincount(dest, minlength=P).tolist()]
+
+
+def select_morton(pos, lo, hi, n_cells, r, splitters, self_rank, workspace=None):
+    """``select_morton_torch``'s result, bit for bit.  ROCm tensors: the HIP pair ``e3_morton_select_count`` / ``_fill``
+    (csrc/e3_morton_halo.hip; one host read of the counts); CPU tensors: the torch restatement.  ``workspace``: an optional
+    uint8 device tensor of at least ``e3_morton_select_workspace_bytes`` bytes to reuse."""
+    if not pos.is_cuda:
+        return select_morton_torch(pos, lo, hi, n_cells, r, splitters, self_rank)
+    from . import _lib
+    _check_f32_pos(pos, "Morton halo")
+    lib = _lib.load()
+    pos = pos.contiguous()
+    dev, n, P = pos.device, pos.shape[0], len(splitters) - 1
+    spl = (ctypes.c_int32 * (P + 1))(*[int(v) for v in splitters])
+    args = (_lib.Float3(*lo), _lib.Float3(*hi), _lib.Int3(*[int(v) for v in n_cells]), float(r), spl, P, int(self_rank))
+    counts = torch.zeros(max(P, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        wbytes = int(lib.e3_morton_select_workspace_bytes(n, P))
+        if wbytes < 0:
+            raise RuntimeError(f"e3_morton_select_workspace_bytes: unsupported size (n = {n}, {P} ranks)")
+        if workspace is None or workspace.numel() < wbytes:
+            workspace = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
+        _lib.check(lib.e3_morton_select_count(pos.data_ptr(), n, *args, counts.data_ptr(), workspace.data_ptr(), wbytes, stream),
+                   "e3_morton_select_count")
+        cnt = [int(v) for v in counts[:P].tolist()]                                 # the one host read of the selection
+        total = sum(cnt)
+        idx = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+        _lib.check(lib.e3_morton_select_fill(pos.data_ptr(), n, *args, total, idx.data_ptr(), workspace.data_ptr(), wbytes,
+                                             stream), "e3_morton_select_fill")
+    return idx[:total].long(), cnt
+
+
+class MortonPartition:
+    """Equal-count ownership of a non-uniform cloud in the open box ``[lo, hi)``: the box is cut into ``grid = (nx, ny, nz)``
+    cells, per axis the largest power of two with ``n_a r <= L_a`` (``L_a = fl32(hi_a - lo_a)``: a cell is never narrower
+    than ``r``) and ``n_a <= 2**max_bits``; a particle's cell is the graph builder's (``cell_of``, fp32), its key the Morton
+    interleave of the cell, and rank ``q`` owns the keys in ``[splitters[q], splitters[q + 1])``.  ``fit`` chooses the
+    splitters from the global key histogram: ``s_q`` = the smallest key ``k`` with ``P * #(key < k) >= q N``.  A cell is never
+    split between ranks, so every rank's count is within the fullest cell of ``N / P``: ``|n_q - N/P| < max(hist)``.
+    Equal neighbours in ``splitters`` are legal (that rank owns nothing)."""
+
+    def __init__(self, lo, hi, r, world, max_bits=6, periodic=False):
+        if periodic_mask(periodic, 0.0, [float(v) for v in lo], [float(v) for v in hi]):
+            raise NotImplementedError("Morton key ranges cover open boxes only; periodic boxes are sharded by "
+                                      "GridHalo(periodic=)")
+        self.world = int(world)
+        if not 1 <= self.world <= MORTON_MAX_RANKS:
+            raise ValueError(f"MortonPartition supports 1..{MORTON_MAX_RANKS} ranks, got {world}")
+        if not 0 <= int(max_bits) <= 7:
+            raise ValueError(f"max_bits must be in [0, 7], got {max_bits}")
+        self.r = float(r)
+        if not (np.isfinite(self.r) and self.r > 0.0):
+            raise ValueError(f"cutoff must be positive and finite, got {r}")
+        self.lo, self.hi = [_f32(v) for v in lo], [_f32(v) for v in hi]
+        grid = []
+        for a in range(3):
+            L = np.float32(self.hi[a]) - np.float32(self.lo[a])
+            if not (np.isfinite(self.lo[a]) and np.isfinite(self.hi[a]) and np.isfinite(L) and L > 0):
+                raise ValueError(f"box [{lo[a]}, {hi[a]}) on axis {a} is empty or not finite")
+            n = 1
+            # L / n is exact for a power of two, so this is n r <= L without rounding
+            while 2 * n <= 2 ** int(max_bits) and L / np.float32(2 * n) >= np.float32(self.r):
+                n *= 2
+            grid.append(n)
+        self.grid = tuple(grid)
+        self.bits = max(n.bit_length() - 1 for n in grid)
+        self.n_keys = 8 ** self.bits
+        self.splitters = None
+        self.counts = None
+        self.hist_max = 0
+
+    def cell_width(self, a):
+        return float(np.float32(np.float32(self.hi[a]) - np.float32(self.lo[a])) / np.float32(self.grid[a]))
+
+    def keys(self, pos: torch.Tensor) -> torch.Tensor:
+        """Morton cell key of every position (int64 [n]; ROCm tensors: ``e3_morton_keys``)."""
+        return morton_keys(pos, self.lo, self.hi, self.grid)
+
+    def fit(self, pos_owned: torch.Tensor, group=None):
+        """Choose the splitters from the particles this process holds (any subset; with a process group the histograms of
+        all ranks are summed, host-staged under gloo as the halo's transfers are).  One host read.  -> self."""
+        hist = torch.bincount(self.keys(pos_owned), minlength=self.n_keys)
+        if dist.is_initialized():
+            if hist.is_cuda and dist.get_backend(group) == "gloo":
+                hist = hist.cpu()
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=group)
+        hist = hist.cpu()
+        P, N = self.world, int(hist.sum())
+        below = torch.zeros(self.n_keys + 1, dtype=torch.int64)             # below[k] = number of particles with key < k
+        below[1:] = torch.cumsum(hist, 0)
+        s = torch.searchsorted(below * P, torch.arange(1, P, dtype=torch.int64) * N)   # smallest k: P below[k] >= q N
+        self.splitters = [0] + [int(v) for v in s.tolist()] + [self.n_keys]
+        self.counts = [int(below[self.splitters[q + 1]] - below[self.splitters[q]]) for q in range(P)]
+        self.hist_max = int(hist.max())
+        return self
+
+    def _fitted(self):
+        if self.splitters is None:
+            raise RuntimeError("MortonPartition.fit has not been called")
+
+    def owner_of(self, pos: torch.Tensor) -> torch.Tensor:
+        """Rank that owns each position (positions outside the box are clamped into the edge cells)."""
+        self._fitted()
+        inner = torch.as_tensor(self.splitters[1:self.world], dtype=torch.long, device=pos.device)
+        return torch.searchsorted(inner, self.keys(pos), right=True)
+
+    def owned_cell_bounds(self, rank):
+        """Bounding box of the cells ``rank`` owns -> (lo3, hi3), or None when it owns no cell of the grid."""
+        self._fitted()
+        k = np.arange(self.splitters[rank], self.splitters[rank + 1], dtype=np.int64)
+        c = np.stack([_compact3(k >> a) for a in range(3)], 1)
+        c = c[(c < np.asarray(self.grid)).all(1)]
+        if not len(c):
+            return None
+        w = [self.cell_width(a) for a in range(3)]
+        return ([self.lo[a] + int(c[:, a].min()) * w[a] for a in range(3)],
+                [self.lo[a] + (int(c[:, a].max()) + 1) * w[a] for a in range(3)])
+
+
+class MortonHalo(GridHalo):
+    """Ghost halo of a fitted ``MortonPartition``: one entry per other rank, in ascending rank order, translation 0.  An
+    owned particle is sent to every rank that owns a cell of ``[cell(p - r), cell(p + r)]`` (``select_morton``): cells are
+    at least ``r`` wide and rounding is monotone, so a rank's ghosts are a superset of what its owned rows need.  After
+    ``setup`` everything is ``GridHalo``'s code; ``neighbours`` then lists the peers with a non-zero count in either
+    direction, and a peer with nothing to exchange costs one count message per ``setup`` and nothing per layer."""
+
+    def __init__(self, partition: MortonPartition, group=None):
+        partition._fitted()
+        self.partition = partition
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        if partition.world != self.world:
+            raise ValueError(f"the partition was made for {partition.world} ranks, the group has {self.world}")
+        self.dims = None
+        self.lo, self.hi = list(partition.lo), list(partition.hi)
+        self.n_owned = 0
+        self.bytes_last_exchange = 0
+        self.periodic, self._axes = 0, (False, False, False)
+        self.images = [(q, (0, 0, 0), (0.0, 0.0, 0.0)) for q in range(self.world) if q != self.rank]
+        self.neighbours = [q for q, _, _ in self.images]
+        self._self_pairs = []
+        self._remote = list(range(len(self.images)))
+        self._send_ops = self._recv_ops = [(q, 0, e) for e, (q, _, _) in enumerate(self.images)]
+
+    def _check_cutoff(self, pos, r):
+        _check_f32_pos(pos, "Morton halo")
+        part = self.partition
+        if not (np.isfinite(r) and r > 0.0):
+            raise ValueError(f"cutoff must be positive and finite, got {r}")
+        for a in range(3):
+            if part.grid[a] > 1 and np.float32(r) > np.float32(part.cell_width(a)):
+                raise ValueError(f"cutoff {r} exceeds the cell width {part.cell_width(a)} of the Morton partition on axis "
+                                 f"{a}: ghosts would come from beyond the adjacent cells")
+
+    def _select(self, pos, r):
+        part = self.partition
+        idx, cnt = select_morton(pos, part.lo, part.hi, part.grid, r, part.splitters, self.rank)
+        cnt = [c for q, c in enumerate(cnt) if q != self.rank]
+        return pos, idx, cnt, pos[idx]
+
+    def setup(self, pos: torch.Tensor, feats: torch.Tensor, r: float):
+        """``GridHalo.setup`` with the Morton selection: fp32 positions (``TypeError`` otherwise), features of any dtype;
+        ``ValueError`` when ``r`` exceeds the partition's cell width on an axis with more than one cell."""
+        out = super().setup(pos, feats, r)
+        self.neighbours = [q for (q, _, _), s, c in zip(self.images, self.send_counts, self.recv_counts) if s or c]
+        return out
+
+    def local_bounds(self, r):
+        """Box for the local ``radius_graph`` call: the bounding box of the owned cells widened by ``2 r`` (a rank that owns
+        no cell: the whole domain)."""
+        b = self.partition.owned_cell_bounds(self.rank)
+        if b is None:
+            return list(self.lo), list(self.hi)
+        return [v - 2 * r for v in b[0]], [v + 2 * r for v in b[1]]
+
+    def owner_of(self, pos: torch.Tensor) -> torch.Tensor:
+        return self.partition.owner_of(pos)
+
+    def box(self, rank):
+        raise NotImplementedError("a Morton key range is not a box: see MortonPartition.owned_cell_bounds")
+
+    coords = box
