@@ -185,6 +185,11 @@ int mfma_pack(const e3_l1tp_plan* plan, const void* const weights[4], const void
               void* packed, hipStream_t stream);
 int mfma_forward(const e3_l1tp_plan* plan, const void* in1, int64_t ld1, const void* in2, int64_t ld2,
                  const void* packed, void* out, int64_t ldo, int64_t B, int dtype, hipStream_t stream);
+// e3_scan.hip: the library's one exclusive prefix sum over int32 (the only instantiation of hipcub's DeviceScan), shared by
+// the graph builder, the edge split and the two halo selections.  Temporary storage for n elements (hipcub's own figure, not
+// rounded), and out[i] = in[0] + ... + in[i - 1] for i < n on stream s with at least that much at `temp`
+size_t scan_temp_bytes(int64_t n);
+hipError_t exclusive_sum(void* temp, size_t temp_bytes, const int32_t* in, int32_t* out, int64_t n, hipStream_t s);
 // shared by e3_l1tp.hip / e3_l1tp_bwd.hip
 int ensure_device(const e3_l1tp_plan* plan);
 constexpr double kC3 = 0.57735026918962576451;  // 1/sqrt(3)  cg110 = cg011, L1TP.py:92-93

@@ -4,16 +4,12 @@
 // an exclusive scan over the entry-major [n_entries, n_blocks] block counts gives every (entry, block) its output offset.
 // The fill pass recomputes the same predicate, so the output is grouped by entry with ascending particle ids inside a
 // group -- the order of mask.nonzero() on an entry-major [n_entries, n] mask.
-#include "e3_common.h"
-
-#include <hipcub/hipcub.hpp>
+// The count / scan / fill scaffold is e3_select.h, shared with e3_morton_halo.hip.
+#include "e3_select.h"
 
 #include <cmath>
 
 namespace e3 {
-
-constexpr int kHaloThreads = 256;
-constexpr int kHaloWaves = kHaloThreads / 64;
 
 // by value as a kernel argument (~1 KiB)
 struct HaloDev {
@@ -29,10 +25,10 @@ __device__ __forceinline__ bool in_entry(const float3 p, const HaloDev& h, const
 }
 
 // wrapped positions out; per (entry, block) hit counts, entry-major: bcnt[e * nb + b]
-__global__ __launch_bounds__(kHaloThreads) void halo_count_kernel(const float* __restrict__ pos, int64_t n, const HaloDev h,
+__global__ __launch_bounds__(kSelectThreads) void halo_count_kernel(const float* __restrict__ pos, int64_t n, const HaloDev h,
                                                                   float* __restrict__ pos_w, int32_t* __restrict__ bcnt) {
-  __shared__ int32_t wcnt[kHaloWaves][E3_HALO_MAX_ENTRIES];
-  const int64_t i = blockIdx.x * (int64_t)kHaloThreads + threadIdx.x;
+  __shared__ int32_t wcnt[kSelectWaves][E3_HALO_MAX_ENTRIES];
+  const int64_t i = blockIdx.x * (int64_t)kSelectThreads + threadIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const bool live = i < n;
   float3 p = make_float3(0.0f, 0.0f, 0.0f);
@@ -48,24 +44,14 @@ __global__ __launch_bounds__(kHaloThreads) void halo_count_kernel(const float* _
     if (lane == 0) wcnt[wave][e] = __popcll(m);
   }
   __syncthreads();
-  if (threadIdx.x < h.n_entries) {
-    int s = 0;
-    for (int w = 0; w < kHaloWaves; ++w) s += wcnt[w][threadIdx.x];
-    bcnt[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
-  }
+  store_block_counts(wcnt, h.n_entries, bcnt);
 }
 
-// off = exclusive scan of bcnt (n_entries * nb + 1 elements): counts[e] = off[(e + 1) nb] - off[e nb]
-__global__ void halo_counts_kernel(const int32_t* __restrict__ off, int nb, int n_entries, int32_t* __restrict__ counts) {
-  const int e = threadIdx.x;
-  if (e < n_entries) counts[e] = off[(int64_t)(e + 1) * nb] - off[(int64_t)e * nb];
-}
-
-__global__ __launch_bounds__(kHaloThreads) void halo_fill_kernel(const float* __restrict__ pos_w, int64_t n, const HaloDev h,
+__global__ __launch_bounds__(kSelectThreads) void halo_fill_kernel(const float* __restrict__ pos_w, int64_t n, const HaloDev h,
                                                                  const int32_t* __restrict__ off, int64_t total,
                                                                  int32_t* __restrict__ idx, float* __restrict__ ghost) {
-  __shared__ int32_t wcnt[kHaloWaves][E3_HALO_MAX_ENTRIES];
-  const int64_t i = blockIdx.x * (int64_t)kHaloThreads + threadIdx.x;
+  __shared__ int32_t wcnt[kSelectWaves][E3_HALO_MAX_ENTRIES];
+  const int64_t i = blockIdx.x * (int64_t)kSelectThreads + threadIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const bool live = i < n;
   const float3 p = live ? make_float3(pos_w[3 * i + 0], pos_w[3 * i + 1], pos_w[3 * i + 2]) : make_float3(0.0f, 0.0f, 0.0f);
@@ -83,8 +69,7 @@ __global__ __launch_bounds__(kHaloThreads) void halo_fill_kernel(const float* __
     const bool in = (hit >> e) & 1;
     const unsigned long long m = __ballot(in);
     if (!in) continue;
-    int64_t o = off[(int64_t)e * gridDim.x + blockIdx.x] + __popcll(m & below);
-    for (int w = 0; w < wave; ++w) o += wcnt[w][e];
+    const int64_t o = select_slot(off, wcnt, e, wave, m, below);
     if (o >= total) continue;   // only a caller that changed the inputs between the two calls gets here
     idx[o] = (int32_t)i;
     ghost[3 * o + 0] = __fadd_rn(p.x, h.esh[e][0]);
@@ -93,31 +78,7 @@ __global__ __launch_bounds__(kHaloThreads) void halo_fill_kernel(const float* __
   }
 }
 
-struct HaloWs {
-  size_t bcnt, off, cub, total;
-};
-
-static size_t halo_scan_bytes(int64_t m) {
-  size_t t = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, (int)m);
-  return t;
-}
-
-static HaloWs halo_ws(int64_t n, int n_entries) {
-  const int64_t nb = (n + kHaloThreads - 1) / kHaloThreads;
-  const int64_t m = (int64_t)n_entries * nb + 1;
-  const size_t arr = ((size_t)m * 4 + 255) / 256 * 256;
-  HaloWs w;
-  w.bcnt = 0;
-  w.off = arr;
-  w.cub = 2 * arr;
-  w.total = w.cub + (halo_scan_bytes(m) + 255) / 256 * 256;
-  return w;
-}
-
-static bool halo_sizes_ok(int64_t n, int n_entries) {
-  return n >= 0 && n_entries >= 0 && n_entries <= E3_HALO_MAX_ENTRIES && n * (int64_t)(n_entries > 0 ? n_entries : 1) < 0x7fffffffLL;
-}
+static bool halo_sizes_ok(int64_t n, int n_entries) { return select_sizes_ok(n, n_entries, 0, E3_HALO_MAX_ENTRIES); }
 
 // host: validated device parameters (finite non-empty bounds, a mask in [0, 7], 2 r < L on periodic axes)
 static int halo_dev(const float lo[3], const float hi[3], int periodic, float r, const e3_halo_entry* entries, int n_entries,
@@ -157,7 +118,7 @@ extern "C" {
 
 int64_t e3_halo_select_workspace_bytes(int64_t n, int n_entries) {
   if (!halo_sizes_ok(n, n_entries)) return -1;
-  return (int64_t)halo_ws(n, n_entries).total;
+  return (int64_t)select_ws(n, n_entries).total;
 }
 
 int e3_halo_select_count(const float* pos, int64_t n, const float lo[3], const float hi[3], int32_t periodic, float r,
@@ -168,27 +129,17 @@ int e3_halo_select_count(const float* pos, int64_t n, const float lo[3], const f
   const int st = halo_dev(lo, hi, periodic, r, entries, n_entries, &h);
   if (st != E3_OK) return st;
   if ((n > 0 && (!pos || !pos_wrapped)) || (n_entries > 0 && !counts) || !workspace) return E3_ERR_INVALID_ARG;
-  const HaloWs w = halo_ws(n, n_entries);
+  const SelectWs w = select_ws(n, n_entries);
   if ((int64_t)w.total > workspace_bytes) return E3_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) {
     if (n_entries > 0) E3_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n_entries * 4, s));
     return E3_OK;
   }
-  char* ws = static_cast<char*>(workspace);
-  int32_t* bcnt = (int32_t*)(ws + w.bcnt);
-  int32_t* off = (int32_t*)(ws + w.off);
-  const int nb = (int)((n + kHaloThreads - 1) / kHaloThreads);
-  const int64_t m = (int64_t)n_entries * nb + 1;
-  E3_HIP_CHECK(hipMemsetAsync(bcnt + (m - 1), 0, 4, s));
-  hipLaunchKernelGGL(halo_count_kernel, dim3(nb), dim3(kHaloThreads), 0, s, pos, n, h, pos_wrapped, bcnt);
-  if (n_entries > 0) {
-    size_t tb = halo_scan_bytes(m);
-    E3_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws + w.cub, tb, bcnt, off, (int)m, s));
-    hipLaunchKernelGGL(halo_counts_kernel, dim3(1), dim3(64), 0, s, off, nb, n_entries, counts);
-  }
-  E3_HIP_CHECK(hipGetLastError());
-  return E3_OK;
+  const int nb = select_blocks(n);
+  return select_count(workspace, w, nb, n_entries, counts, s, [&](int32_t* bcnt) {   // no entries: the wrap alone
+    hipLaunchKernelGGL(halo_count_kernel, dim3(nb), dim3(kSelectThreads), 0, s, pos, n, h, pos_wrapped, bcnt);
+  });
 }
 
 int e3_halo_select_fill(const float* pos_wrapped, int64_t n, const float lo[3], const float hi[3], int32_t periodic, float r,
@@ -201,11 +152,10 @@ int e3_halo_select_fill(const float* pos_wrapped, int64_t n, const float lo[3], 
   if (total < 0) return E3_ERR_INVALID_ARG;
   if (n == 0 || n_entries == 0 || total == 0) return E3_OK;
   if (!pos_wrapped || !idx || !ghost_pos || !workspace) return E3_ERR_INVALID_ARG;
-  const HaloWs w = halo_ws(n, n_entries);
+  const SelectWs w = select_ws(n, n_entries);
   if ((int64_t)w.total > workspace_bytes) return E3_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int nb = (int)((n + kHaloThreads - 1) / kHaloThreads);
-  hipLaunchKernelGGL(halo_fill_kernel, dim3(nb), dim3(kHaloThreads), 0, s, pos_wrapped, n, h,
+  hipLaunchKernelGGL(halo_fill_kernel, dim3(select_blocks(n)), dim3(kSelectThreads), 0, s, pos_wrapped, n, h,
                      (const int32_t*)(static_cast<char*>(workspace) + w.off), total, idx, ghost_pos);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;

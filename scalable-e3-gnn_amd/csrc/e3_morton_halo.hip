@@ -3,21 +3,16 @@
 // Spec: include/e3gnn.h, e3_morton_select_count.  Integer / HBM work, no MFMA: one thread per particle builds a 64-bit mask
 // of destination ranks in registers (owner of a cell = branch-free binary search of its key in the splitters, staged once
 // per block in LDS); a particle whose range is one cell costs one search, the others 8 to 27 (cells are between r and 2r wide
-// unless the grid is capped, so 2 or 3 per axis is the rule).  Counting and placement follow e3_halo.hip:
+// unless the grid is capped, so 2 or 3 per axis is the rule).  Counting and placement are e3_select.h's, as in e3_halo.hip:
 // one 64-bit ballot + popcount per destination and wave -- only for the destinations some lane of the wave has --, the waves
 // of a block summed in LDS into a rank-major [n_ranks, n_blocks] array, one exclusive scan, and a fill pass that recomputes
 // the predicate: the output is grouped by destination with ascending particle ids inside a group, the order of
 // mask.nonzero() on a rank-major [n_ranks, n] mask.
-#include "e3_common.h"
-
-#include <hipcub/hipcub.hpp>
+#include "e3_select.h"
 
 #include <cmath>
 
 namespace e3 {
-
-constexpr int kMortonThreads = 256;
-constexpr int kMortonWaves = kMortonThreads / 64;
 
 // by value as a kernel argument.  split[k] = s_{k+1} for k < n_ranks - 1, 0xFFFFFFFF beyond (no key reaches it): the owner
 // of a key is the number of entries <= key
@@ -84,9 +79,9 @@ __device__ __forceinline__ unsigned long long wave_or(const unsigned long long v
   return ((unsigned long long)b << 32) | a;
 }
 
-__global__ __launch_bounds__(kMortonThreads) void morton_keys_kernel(const float* __restrict__ pos, int64_t n, const MortonDev m,
+__global__ __launch_bounds__(kSelectThreads) void morton_keys_kernel(const float* __restrict__ pos, int64_t n, const MortonDev m,
                                                                      int32_t* __restrict__ keys) {
-  const int64_t i = blockIdx.x * (int64_t)kMortonThreads + threadIdx.x;
+  const int64_t i = blockIdx.x * (int64_t)kSelectThreads + threadIdx.x;
   if (i >= n) return;
   const float3 p = load3(pos, i);
   keys[i] = (int32_t)morton3(cell_of(p.x, m.lo[0], m.inv[0], m.n[0]), cell_of(p.y, m.lo[1], m.inv[1], m.n[1]),
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(kMortonThreads) void morton_keys_kernel(const float
 __device__ __forceinline__ unsigned long long block_masks(const float* __restrict__ pos, const int64_t n, const MortonDev& m,
                                                           uint32_t* __restrict__ s_split,
                                                           int32_t (*__restrict__ wcnt)[E3_MORTON_MAX_RANKS]) {
-  const int64_t i = blockIdx.x * (int64_t)kMortonThreads + threadIdx.x;
+  const int64_t i = blockIdx.x * (int64_t)kSelectThreads + threadIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   stage_splitters(m, s_split);
   wcnt[wave][lane] = 0;
@@ -113,31 +108,21 @@ __device__ __forceinline__ unsigned long long block_masks(const float* __restric
 }
 
 // per (rank, block) hit counts, rank-major: bcnt[q * nb + b]
-__global__ __launch_bounds__(kMortonThreads) void morton_count_kernel(const float* __restrict__ pos, int64_t n, const MortonDev m,
+__global__ __launch_bounds__(kSelectThreads) void morton_count_kernel(const float* __restrict__ pos, int64_t n, const MortonDev m,
                                                                       int32_t* __restrict__ bcnt) {
   __shared__ uint32_t s_split[E3_MORTON_MAX_RANKS];
-  __shared__ int32_t wcnt[kMortonWaves][E3_MORTON_MAX_RANKS];
+  __shared__ int32_t wcnt[kSelectWaves][E3_MORTON_MAX_RANKS];
   block_masks(pos, n, m, s_split, wcnt);
-  if (threadIdx.x < m.n_ranks) {
-    int s = 0;
-    for (int w = 0; w < kMortonWaves; ++w) s += wcnt[w][threadIdx.x];
-    bcnt[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
-  }
+  store_block_counts(wcnt, m.n_ranks, bcnt);
 }
 
-// off = exclusive scan of bcnt (n_ranks * nb + 1 elements): counts[q] = off[(q + 1) nb] - off[q nb]
-__global__ void morton_counts_kernel(const int32_t* __restrict__ off, int nb, int n_ranks, int32_t* __restrict__ counts) {
-  const int q = threadIdx.x;
-  if (q < n_ranks) counts[q] = off[(int64_t)(q + 1) * nb] - off[(int64_t)q * nb];
-}
-
-__global__ __launch_bounds__(kMortonThreads) void morton_fill_kernel(const float* __restrict__ pos, int64_t n, const MortonDev m,
+__global__ __launch_bounds__(kSelectThreads) void morton_fill_kernel(const float* __restrict__ pos, int64_t n, const MortonDev m,
                                                                      const int32_t* __restrict__ off, int64_t total,
                                                                      int32_t* __restrict__ idx) {
   __shared__ uint32_t s_split[E3_MORTON_MAX_RANKS];
-  __shared__ int32_t wcnt[kMortonWaves][E3_MORTON_MAX_RANKS];
+  __shared__ int32_t wcnt[kSelectWaves][E3_MORTON_MAX_RANKS];
   const unsigned long long mask = block_masks(pos, n, m, s_split, wcnt);
-  const int64_t i = blockIdx.x * (int64_t)kMortonThreads + threadIdx.x;
+  const int64_t i = blockIdx.x * (int64_t)kSelectThreads + threadIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;   // lanes < this one
   for (unsigned long long left = wave_or(mask); left; left &= left - 1) {
@@ -145,38 +130,13 @@ __global__ __launch_bounds__(kMortonThreads) void morton_fill_kernel(const float
     const bool in = (mask >> q) & 1;
     const unsigned long long b = __ballot(in);
     if (!in) continue;
-    int64_t o = off[(int64_t)q * gridDim.x + blockIdx.x] + __popcll(b & below);
-    for (int w = 0; w < wave; ++w) o += wcnt[w][q];
+    const int64_t o = select_slot(off, wcnt, q, wave, b, below);
     if (o >= total) continue;   // only a caller that changed the inputs between the two calls gets here
     idx[o] = (int32_t)i;
   }
 }
 
-struct MortonWs {
-  size_t bcnt, off, cub, total;
-};
-
-static size_t morton_scan_bytes(int64_t m) {
-  size_t t = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, (int)m);
-  return t;
-}
-
-static MortonWs morton_ws(int64_t n, int n_ranks) {
-  const int64_t nb = (n + kMortonThreads - 1) / kMortonThreads;
-  const int64_t m = (int64_t)n_ranks * nb + 1;
-  const size_t arr = ((size_t)m * 4 + 255) / 256 * 256;
-  MortonWs w;
-  w.bcnt = 0;
-  w.off = arr;
-  w.cub = 2 * arr;
-  w.total = w.cub + (morton_scan_bytes(m) + 255) / 256 * 256;
-  return w;
-}
-
-static bool morton_sizes_ok(int64_t n, int n_ranks) {
-  return n >= 0 && n_ranks >= 1 && n_ranks <= E3_MORTON_MAX_RANKS && n * (int64_t)n_ranks < 0x7fffffffLL;
-}
+static bool morton_sizes_ok(int64_t n, int n_ranks) { return select_sizes_ok(n, n_ranks, 1, E3_MORTON_MAX_RANKS); }
 
 // host: the validated grid (finite non-empty box, n_cells powers of two in [1, 128])
 static int morton_grid(const float lo[3], const float hi[3], const int32_t n_cells[3], MortonDev* m) {
@@ -226,15 +186,15 @@ int e3_morton_keys(const float* pos, int64_t n, const float lo[3], const float h
   if (st != E3_OK) return st;
   if (n < 0 || n >= 0x7fffffffLL || (n > 0 && (!pos || !keys))) return E3_ERR_INVALID_ARG;
   if (n == 0) return E3_OK;
-  const int nb = (int)((n + kMortonThreads - 1) / kMortonThreads);
-  hipLaunchKernelGGL(morton_keys_kernel, dim3(nb), dim3(kMortonThreads), 0, (hipStream_t)stream, pos, n, m, keys);
+  hipLaunchKernelGGL(morton_keys_kernel, dim3(select_blocks(n)), dim3(kSelectThreads), 0, (hipStream_t)stream, pos, n, m,
+                     keys);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }
 
 int64_t e3_morton_select_workspace_bytes(int64_t n, int n_ranks) {
   if (!morton_sizes_ok(n, n_ranks)) return -1;
-  return (int64_t)morton_ws(n, n_ranks).total;
+  return (int64_t)select_ws(n, n_ranks).total;
 }
 
 int e3_morton_select_count(const float* pos, int64_t n, const float lo[3], const float hi[3], const int32_t n_cells[3], float r,
@@ -245,25 +205,17 @@ int e3_morton_select_count(const float* pos, int64_t n, const float lo[3], const
   const int st = morton_dev(lo, hi, n_cells, r, splitters, n_ranks, self_rank, &m);
   if (st != E3_OK) return st;
   if ((n > 0 && !pos) || !counts || !workspace) return E3_ERR_INVALID_ARG;
-  const MortonWs w = morton_ws(n, n_ranks);
+  const SelectWs w = select_ws(n, n_ranks);
   if ((int64_t)w.total > workspace_bytes) return E3_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) {
     E3_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n_ranks * 4, s));
     return E3_OK;
   }
-  char* ws = static_cast<char*>(workspace);
-  int32_t* bcnt = (int32_t*)(ws + w.bcnt);
-  int32_t* off = (int32_t*)(ws + w.off);
-  const int nb = (int)((n + kMortonThreads - 1) / kMortonThreads);
-  const int64_t len = (int64_t)n_ranks * nb + 1;
-  E3_HIP_CHECK(hipMemsetAsync(bcnt + (len - 1), 0, 4, s));
-  hipLaunchKernelGGL(morton_count_kernel, dim3(nb), dim3(kMortonThreads), 0, s, pos, n, m, bcnt);
-  size_t tb = morton_scan_bytes(len);
-  E3_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws + w.cub, tb, bcnt, off, (int)len, s));
-  hipLaunchKernelGGL(morton_counts_kernel, dim3(1), dim3(64), 0, s, off, nb, n_ranks, counts);
-  E3_HIP_CHECK(hipGetLastError());
-  return E3_OK;
+  const int nb = select_blocks(n);
+  return select_count(workspace, w, nb, n_ranks, counts, s, [&](int32_t* bcnt) {
+    hipLaunchKernelGGL(morton_count_kernel, dim3(nb), dim3(kSelectThreads), 0, s, pos, n, m, bcnt);
+  });
 }
 
 int e3_morton_select_fill(const float* pos, int64_t n, const float lo[3], const float hi[3], const int32_t n_cells[3], float r,
@@ -276,10 +228,9 @@ int e3_morton_select_fill(const float* pos, int64_t n, const float lo[3], const 
   if (total < 0) return E3_ERR_INVALID_ARG;
   if (n == 0 || total == 0) return E3_OK;
   if (!pos || !idx || !workspace) return E3_ERR_INVALID_ARG;
-  const MortonWs w = morton_ws(n, n_ranks);
+  const SelectWs w = select_ws(n, n_ranks);
   if ((int64_t)w.total > workspace_bytes) return E3_ERR_INVALID_ARG;
-  const int nb = (int)((n + kMortonThreads - 1) / kMortonThreads);
-  hipLaunchKernelGGL(morton_fill_kernel, dim3(nb), dim3(kMortonThreads), 0, (hipStream_t)stream, pos, n, m,
+  hipLaunchKernelGGL(morton_fill_kernel, dim3(select_blocks(n)), dim3(kSelectThreads), 0, (hipStream_t)stream, pos, n, m,
                      (const int32_t*)(static_cast<char*>(workspace) + w.off), total, idx);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;

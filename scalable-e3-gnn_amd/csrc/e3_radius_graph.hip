@@ -4,7 +4,7 @@
 // so that the CPU oracle reproduces them bit for bit.
 #include "e3_common.h"
 
-#include <hipcub/hipcub.hpp>
+#include <hipcub/hipcub.hpp>   // DeviceRadixSort; the scan is e3_scan.hip's
 
 #include <algorithm>
 #include <cmath>
@@ -205,11 +205,10 @@ static RgWs rg_ws(int64_t N, int bits) {
   w.keys = take(N * 4); w.skeys = take((N + 1) * 4); w.idx = take(N * 4);
   w.cbegin = take(ncode * 4); w.cend = take(ncode * 4);
   w.heads = take(N * 4); w.nheads = take(256); w.deg = take((N + 1) * 4);
-  size_t s1 = 0, s2 = 0;
+  size_t s1 = 0;
   hipcub::DeviceRadixSort::SortPairs(nullptr, s1, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
                                      (int32_t*)nullptr, (int)N, 0, 3 * bits);
-  hipcub::DeviceScan::ExclusiveSum(nullptr, s2, (int32_t*)nullptr, (int32_t*)nullptr, (int)(N + 1));
-  w.cub_bytes = std::max(s1, s2) + 256;
+  w.cub_bytes = std::max(s1, scan_temp_bytes(N + 1)) + 256;
   w.cub = take(w.cub_bytes);
   w.total = pos;
   return w;
@@ -304,8 +303,7 @@ static int rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, con
   hipLaunchKernelGGL((rg_scan_kernel<false, PBC>), dim3(grid), dim3(64), 0, s, (const float4*)sorted_pos4, skeys, cbegin,
                      cend, heads, nheads, g, deg, (const int32_t*)nullptr, (int32_t*)nullptr, pb);
   E3_HIP_CHECK(hipMemsetAsync(deg + N, 0, 4, s));
-  cb = w.cub_bytes;
-  E3_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws + w.cub, cb, deg, rowptr, (int)(N + 1), s));
+  E3_HIP_CHECK(exclusive_sum(ws + w.cub, w.cub_bytes, deg, rowptr, N + 1, s));
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }

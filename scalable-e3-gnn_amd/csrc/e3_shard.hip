@@ -1,9 +1,7 @@
 // Sharded graphs: drop the edges into ghost rows and split the rest by the ownership of their src -- one classification +
-// compaction on the device (sharding.GridHalo.split_graph).  Integer / HBM work: no MFMA; rows are whole (a CSR row is kept
+// compaction on the device (sharding.Halo.split_graph).  Integer / HBM work: no MFMA; rows are whole (a CSR row is kept
 // or dropped as a unit), so one thread per row walks its ~24 edges and every output list stays sorted by dst.
 #include "e3_common.h"
-
-#include <hipcub/hipcub.hpp>
 
 namespace e3 {
 
@@ -41,11 +39,7 @@ __global__ void split_fill_kernel(const int32_t* __restrict__ rowptr, const int3
   }
 }
 
-static size_t scan_temp_bytes(int64_t n) {
-  size_t t = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, (int)n);
-  return (t + 255) / 256 * 256;
-}
+static size_t split_temp_bytes(int64_t N) { return (scan_temp_bytes(N + 1) + 255) / 256 * 256; }
 
 }  // namespace e3
 
@@ -56,7 +50,7 @@ extern "C" {
 int64_t e3_split_edges_workspace_bytes(int64_t N) {
   if (N < 0 || N + 1 > 0x7fffffffLL) return -1;
   const size_t arr = ((size_t)(N + 1) * 4 + 255) / 256 * 256;
-  return (int64_t)(5 * arr + scan_temp_bytes(N + 1));
+  return (int64_t)(5 * arr + split_temp_bytes(N));
 }
 
 int e3_split_edges(const int32_t* rowptr, const int32_t* src, const uint8_t* is_ghost, int64_t N, int64_t E,
@@ -71,13 +65,13 @@ int e3_split_edges(const int32_t* rowptr, const int32_t* src, const uint8_t* is_
   int32_t *ck = (int32_t*)w, *ci = (int32_t*)(w + arr), *cb = (int32_t*)(w + 2 * arr), *oi = (int32_t*)(w + 3 * arr),
           *ob = (int32_t*)(w + 4 * arr);
   void* temp = w + 5 * arr;
-  size_t tb = scan_temp_bytes(N + 1);
+  const size_t tb = split_temp_bytes(N);
   const int threads = 256;
   const unsigned blocks = (unsigned)((N + 1 + threads - 1) / threads);
   hipLaunchKernelGGL(split_count_kernel, dim3(blocks), dim3(threads), 0, s, rowptr, src, is_ghost, N, ck, ci, cb);
-  E3_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, ck, rowptr_kept, (int)(N + 1), s));
-  E3_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, ci, oi, (int)(N + 1), s));
-  E3_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, cb, ob, (int)(N + 1), s));
+  E3_HIP_CHECK(exclusive_sum(temp, tb, ck, rowptr_kept, N + 1, s));
+  E3_HIP_CHECK(exclusive_sum(temp, tb, ci, oi, N + 1, s));
+  E3_HIP_CHECK(exclusive_sum(temp, tb, cb, ob, N + 1, s));
   hipLaunchKernelGGL(split_fill_kernel, dim3(blocks), dim3(threads), 0, s, rowptr, src, is_ghost, N, rowptr_kept, oi, ob,
                      src_kept, dst_kept, src_interior, dst_interior, src_boundary, dst_boundary, counts);
   E3_HIP_CHECK(hipGetLastError());

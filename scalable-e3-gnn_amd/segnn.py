@@ -85,7 +85,7 @@ class SEGNNLayer(nn.Module):
         return f
 
     def forward(self, h, g: RadiusGraph, Y, d, A, h_scale=None, halo=None, split=None):
-        """-> (h_next, operand scale of h_next | None).  ``halo`` / ``split`` (sharding.GridHalo / SplitGraph): the layer
+        """-> (h_next, operand scale of h_next | None).  ``halo`` / ``split`` (sharding.Halo / SplitGraph): the layer
         refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges."""
         if (halo is not None or split is not None) and g.box is not None:
             raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
@@ -201,7 +201,7 @@ class SEGNN(nn.Module):
     def forward(self, x: torch.Tensor, g: RadiusGraph, geometry=None, halo=None, split=None) -> torch.Tensor:
         """x [N, in_dim] node features in the graph's (Morton) order -> [N, out_dim] in the same order.
 
-        ``halo`` (``sharding.SlabHalo``): when the cloud is spatially sharded, ghost rows of ``h`` are
+        ``halo`` (a ``sharding.Halo``): when the cloud is spatially sharded, ghost rows of ``h`` are
         refreshed from their owners before every message-passing layer; only owned rows of the result
         are meaningful.  ``split`` (``halo.split_graph(g)``): edges into ghost rows dropped and the rest split into
         interior / boundary lists so that the refresh overlaps the interior edges."""

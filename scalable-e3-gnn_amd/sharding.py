@@ -16,7 +16,7 @@ box, wrapped modulo ``dims`` on periodic axes, and ``t`` (whole box lengths per 
                      isend/irecv), the interior edges' message kernel runs meanwhile, ``finish`` waits and writes the ghost
                      rows of ``h`` IN PLACE (inference only: see ``finish``), then the boundary edges run.
 
-Three layouts are built on it:
+The exchange above needs only the entry table and is the base class ``Halo``.  Three layouts add their geometry and selection:
 
   * ``SlabHalo``   — slabs along x (grid N x 1 x 1): what ``bench.py --gpus N`` uses for WEAK scaling (N unit cubes side by
                      side, 1 M particles each): a face costs r / 1 = 1.8 % ghosts per side, every rank has <= 2 neighbours.
@@ -136,6 +136,35 @@ def _wrap_torch(pos, lo, hi, mask):
     return out
 
 
+def _check_f32_pos(pos, what):
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
+        raise TypeError(f"{what} positions must be [n,3] float32, got {tuple(pos.shape)} {pos.dtype}")
+
+
+def _select_on_device(kind, what, dev, n, n_groups, count_head, fill_head, rows=(), workspace=None):
+    """The two-pass device selection of ``select_images`` (``kind`` "halo") and ``select_morton`` ("morton"): workspace
+    query, ``e3_<kind>_select_count(*count_head, counts, workspace ...)``, the ONE host read of the per-group counts,
+    ``e3_<kind>_select_fill(*fill_head, total, idx, *more, workspace ...)`` with one ``(shape, dtype)`` in ``rows`` for every
+    further per-hit output.  -> (counts (list of ``n_groups`` ints), [idx [total] int32, *more])."""
+    from . import _lib
+    lib = _lib.load()
+    names = [f"e3_{kind}_select_{part}" for part in ("workspace_bytes", "count", "fill")]
+    counts = torch.zeros(max(n_groups, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        wbytes = int(getattr(lib, names[0])(n, n_groups))
+        if wbytes < 0:
+            raise RuntimeError(f"{names[0]}: unsupported size (n = {n}, {n_groups} {what})")
+        if workspace is None or workspace.numel() < wbytes:
+            workspace = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
+        ws = (workspace.data_ptr(), wbytes, torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(getattr(lib, names[1])(*count_head, counts.data_ptr(), *ws), names[1])
+        cnt = [int(v) for v in counts[:n_groups].tolist()] if n_groups else []      # the one host read of the selection
+        total = sum(cnt)
+        out = [torch.empty((max(total, 1), *shape), dtype=dt, device=dev) for shape, dt in (((), torch.int32), *rows)]
+        _lib.check(getattr(lib, names[2])(*fill_head, total, *[t.data_ptr() for t in out], *ws), names[2])
+    return cnt, [t[:total] for t in out]
+
+
 def _in_boxes(pos, elo, ehi):
     """(entry, index) of every position inside ``[elo_e, ehi_e)`` on all three axes, entry-major, then by index."""
     m = ((pos[None, :, :] >= elo[:, None, :]) & (pos[None, :, :] < ehi[:, None, :])).all(-1)   # [ne, n]
@@ -146,8 +175,7 @@ def select_images_torch(pos, lo, hi, periodic, r, entries):
     """Torch restatement of ``e3_halo_select_count`` / ``_fill`` (any device): -> (pos_wrapped [n,3] fp32, idx [total]
     int64, counts (list of int), ghost_pos [total,3] fp32).  ``entries``: ``[(lo3, hi3, shift3), ...]`` fp32 values."""
     mask = periodic_mask(periodic, r, lo, hi)
-    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
-        raise TypeError(f"periodic halo positions must be [n,3] float32, got {tuple(pos.shape)} {pos.dtype}")
+    _check_f32_pos(pos, "periodic halo")
     dev = pos.device
     pw = _wrap_torch(pos, lo, hi, mask)
     ne = len(entries)
@@ -169,9 +197,7 @@ def select_images(pos, lo, hi, periodic, r, entries):
         return select_images_torch(pos, lo, hi, periodic, r, entries)
     from . import _lib
     mask = periodic_mask(periodic, r, lo, hi)
-    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
-        raise TypeError(f"periodic halo positions must be [n,3] float32, got {tuple(pos.shape)} {pos.dtype}")
-    lib = _lib.load()
+    _check_f32_pos(pos, "periodic halo")
     pos = pos.contiguous()
     dev, n, ne = pos.device, pos.shape[0], len(entries)
     arr = (_lib.HaloEntry * max(ne, 1))()
@@ -180,22 +206,9 @@ def select_images(pos, lo, hi, periodic, r, entries):
             arr[i].lo[a], arr[i].hi[a], arr[i].shift[a] = elo[a], ehi[a], esh[a]
     args = (_lib.Float3(*lo), _lib.Float3(*hi), mask, float(r), arr, ne)
     pw = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    counts = torch.zeros(max(ne, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        wbytes = int(lib.e3_halo_select_workspace_bytes(n, ne))
-        if wbytes < 0:
-            raise RuntimeError(f"e3_halo_select_workspace_bytes: unsupported size (n = {n}, {ne} entries)")
-        ws = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
-        _lib.check(lib.e3_halo_select_count(pos.data_ptr(), n, *args, pw.data_ptr(), counts.data_ptr(), ws.data_ptr(),
-                                            wbytes, stream), "e3_halo_select_count")
-        cnt = [int(v) for v in counts[:ne].tolist()] if ne else []                  # the one host read of the selection
-        total = sum(cnt)
-        idx = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        ghost = torch.empty((max(total, 1), 3), dtype=torch.float32, device=dev)
-        _lib.check(lib.e3_halo_select_fill(pw.data_ptr(), n, *args, total, idx.data_ptr(), ghost.data_ptr(), ws.data_ptr(),
-                                           wbytes, stream), "e3_halo_select_fill")
-    return pw, idx[:total].long(), cnt, ghost[:total]
+    cnt, (idx, ghost) = _select_on_device("halo", "entries", dev, n, ne, (pos.data_ptr(), n, *args, pw.data_ptr()),
+                                          (pw.data_ptr(), n, *args), rows=[((3,), torch.float32)])
+    return pw, idx.long(), cnt, ghost
 
 
 @dataclass
@@ -207,80 +220,35 @@ class SplitGraph:
     dropped: int                  # edges into ghost rows that were removed
 
 
-class GridHalo:
-    """Ghost-cell halo of a ``dims = (px, py, pz)`` grid of equal boxes covering ``[lo, hi)``; rank = (ix py + iy) pz + iz.
+def _world_rank(group):
+    return (dist.get_world_size(group), dist.get_rank(group)) if dist.is_initialized() else (1, 0)
+
+
+class Halo:
+    """The entry-based ghost exchange every layout shares: it needs nothing but the entry table.
 
     ``images`` lists the halo's entries ``(peer, d, t)`` (module docstring); ``send_counts`` / ``recv_counts`` are per
-    entry and ``neighbours`` is the sorted distinct peers other than this rank.  ``periodic`` (bool or 3 bools, validated by
-    ``radius_graph.periodic_mask``): those axes wrap at ``[lo, hi)``; positions must then be fp32, and ``setup`` returns the
-    owned ones wrapped.  Works without a process group at world 1 (dims (1, 1, 1) with periodic axes: a pure self-halo)."""
+    entry and ``neighbours`` is the sorted distinct peers other than this rank.  A layout supplies ``_check_cutoff(pos, r)``
+    (raises before any transfer), ``owner_of(pos)`` and ``_select(pos, r)`` -> (owned positions as the local cloud holds
+    them, indices sent [total], per-entry counts, positions sent), the particles grouped by entry, ascending within one."""
 
-    def __init__(self, dims, lo, hi, group=None, periodic=False):
+    periodic = 0    # axis bit mask of the axes that wrap; only a GridHalo has any
+
+    def __init__(self, group, entries, send_tags, recv_tags):
+        """``send_tags[e]`` / ``recv_tags[e]``: P2POp tag of what this rank sends for entry ``e`` / receives into it."""
         self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.dims = tuple(int(d) for d in dims)
-        if self.dims[0] * self.dims[1] * self.dims[2] != self.world:
-            raise ValueError(f"grid {self.dims} needs {self.dims[0] * self.dims[1] * self.dims[2]} ranks, the group has {self.world}")
-        self.lo = [float(v) for v in lo]
-        self.hi = [float(v) for v in hi]
+        self.world, self.rank = _world_rank(group)
         self.n_owned = 0
         self.bytes_last_exchange = 0
-        self.periodic = periodic_mask(periodic, 0.0, self.lo, self.hi)   # axis bit mask; 0 = open box
-        self._axes = tuple(bool((self.periodic >> a) & 1) for a in range(3))
-        ent = self.images = image_entries(self.dims, self.lo, self.hi, self._axes, self.rank)
+        ent = self.images = entries
         self.neighbours = sorted({q for q, _, _ in ent if q != self.rank})
         at = {d: e for e, (_, d, _) in enumerate(ent)}
         # self entry e receives what this rank sends for its entry (me, -d)
         self._self_pairs = [(e, at[tuple(-v for v in d)]) for e, (q, d, _) in enumerate(ent) if q == self.rank]
         self._remote = [e for e, (q, _, _) in enumerate(ent) if q != self.rank]
-        # per peer, in tag order (the receiver-side offset: -d for what I send, d for what I receive)
-        self._send_ops = sorted((ent[e][0], OFFSETS.index(tuple(-v for v in ent[e][1])), e) for e in self._remote)
-        self._recv_ops = sorted((ent[e][0], OFFSETS.index(ent[e][1]), e) for e in self._remote)
-
-    # -- geometry -------------------------------------------------------------------------------------
-    def coords(self, rank):
-        px, py, pz = self.dims
-        return rank // (py * pz), (rank // pz) % py, rank % pz
-
-    def box(self, rank):
-        c = self.coords(rank)
-        w = [(self.hi[a] - self.lo[a]) / self.dims[a] for a in range(3)]
-        return [self.lo[a] + c[a] * w[a] for a in range(3)], [self.lo[a] + (c[a] + 1) * w[a] for a in range(3)]
-
-    def owner_of(self, pos: torch.Tensor) -> torch.Tensor:
-        """Rank that owns each position (positions outside [lo, hi) are clamped into the edge boxes; periodic axes: the
-        positions are wrapped first, in fp32, as ``setup`` wraps them)."""
-        if self.periodic:
-            pos = _wrap_torch(pos.float(), self.lo, self.hi, self.periodic)
-        idx = []
-        for a in range(3):
-            w = (self.hi[a] - self.lo[a]) / self.dims[a]
-            idx.append(((pos[:, a] - self.lo[a]) / w).floor().long().clamp_(0, self.dims[a] - 1))
-        return (idx[0] * self.dims[1] + idx[1]) * self.dims[2] + idx[2]
-
-    def _selection(self, r):
-        """fp32 selection bounds and shift of every entry, sender side: the owned particles in ``[blo + t - r, bhi + t + r)``
-        of the peer's box go to it, at ``p - t``."""
-        out = []
-        for q, _, t in self.images:
-            blo, bhi = self.box(q)
-            out.append(([_f32(blo[a] + t[a] - r) for a in range(3)], [_f32(bhi[a] + t[a] + r) for a in range(3)],
-                        [-t[a] if t[a] else 0.0 for a in range(3)]))
-        return out
-
-    def _select(self, pos, r):
-        """-> (owned positions as the local cloud holds them, indices sent [total], per-entry counts, positions sent), the
-        particles grouped by entry, ascending within an entry."""
-        if self.periodic:
-            return select_images(pos, self.lo, self.hi, self._axes, r, self._selection(r))
-        if not self.images:
-            return pos, torch.empty(0, dtype=torch.long, device=pos.device), [], pos[:0]
-        # bounds in pos.dtype: per axis a superset of the r-ball
-        blo = torch.tensor([self.box(q)[0] for q, _, _ in self.images], dtype=pos.dtype, device=pos.device)
-        bhi = torch.tensor([self.box(q)[1] for q, _, _ in self.images], dtype=pos.dtype, device=pos.device)
-        ent, idx = _in_boxes(pos, blo - r, bhi + r)
-        return pos, idx, torch.bincount(ent, minlength=len(self.images)), pos[idx]
+        # per peer, in tag order
+        self._send_ops = sorted((ent[e][0], send_tags[e], e) for e in self._remote)
+        self._recv_ops = sorted((ent[e][0], recv_tags[e], e) for e in self._remote)
 
     # -- p2p helpers ----------------------------------------------------------------------------------
     def _post(self, sends, recvs):
@@ -315,9 +283,6 @@ class GridHalo:
             w.wait()
         for d, s in staged:
             d.copy_(s)
-
-    def _check_cutoff(self, pos, r):
-        check_cutoff(self.dims, self.lo, self.hi, self._axes, r)
 
     # -- once per graph build -------------------------------------------------------------------------
     def setup(self, pos: torch.Tensor, feats: torch.Tensor, r: float):
@@ -433,11 +398,77 @@ class GridHalo:
         return self._recv_idx
 
 
+class GridHalo(Halo):
+    """Ghost-cell halo of a ``dims = (px, py, pz)`` grid of equal boxes covering ``[lo, hi)``; rank = (ix py + iy) pz + iz.
+
+    ``periodic`` (bool or 3 bools, validated by ``radius_graph.periodic_mask``): those axes wrap at ``[lo, hi)``; positions
+    must then be fp32, and ``setup`` returns the owned ones wrapped.  Works without a process group at world 1 (dims
+    (1, 1, 1) with periodic axes: a pure self-halo)."""
+
+    def __init__(self, dims, lo, hi, group=None, periodic=False):
+        world, rank = _world_rank(group)
+        self.dims = tuple(int(d) for d in dims)
+        if self.dims[0] * self.dims[1] * self.dims[2] != world:
+            raise ValueError(f"grid {self.dims} needs {self.dims[0] * self.dims[1] * self.dims[2]} ranks, the group has {world}")
+        self.lo = [float(v) for v in lo]
+        self.hi = [float(v) for v in hi]
+        self.periodic = periodic_mask(periodic, 0.0, self.lo, self.hi)   # axis bit mask; 0 = open box
+        self._axes = tuple(bool((self.periodic >> a) & 1) for a in range(3))
+        ent = image_entries(self.dims, self.lo, self.hi, self._axes, rank)
+        # tag = index of the RECEIVER-side offset: -d for what I send, d for what I receive
+        super().__init__(group, ent, [OFFSETS.index(tuple(-v for v in d)) for _, d, _ in ent],
+                         [OFFSETS.index(d) for _, d, _ in ent])
+
+    def coords(self, rank):
+        px, py, pz = self.dims
+        return rank // (py * pz), (rank // pz) % py, rank % pz
+
+    def box(self, rank):
+        c = self.coords(rank)
+        w = [(self.hi[a] - self.lo[a]) / self.dims[a] for a in range(3)]
+        return [self.lo[a] + c[a] * w[a] for a in range(3)], [self.lo[a] + (c[a] + 1) * w[a] for a in range(3)]
+
+    def owner_of(self, pos: torch.Tensor) -> torch.Tensor:
+        """Rank that owns each position (positions outside [lo, hi) are clamped into the edge boxes; periodic axes: the
+        positions are wrapped first, in fp32, as ``setup`` wraps them)."""
+        if self.periodic:
+            pos = _wrap_torch(pos.float(), self.lo, self.hi, self.periodic)
+        idx = []
+        for a in range(3):
+            w = (self.hi[a] - self.lo[a]) / self.dims[a]
+            idx.append(((pos[:, a] - self.lo[a]) / w).floor().long().clamp_(0, self.dims[a] - 1))
+        return (idx[0] * self.dims[1] + idx[1]) * self.dims[2] + idx[2]
+
+    def _selection(self, r):
+        """fp32 selection bounds and shift of every entry, sender side: the owned particles in ``[blo + t - r, bhi + t + r)``
+        of the peer's box go to it, at ``p - t``."""
+        out = []
+        for q, _, t in self.images:
+            blo, bhi = self.box(q)
+            out.append(([_f32(blo[a] + t[a] - r) for a in range(3)], [_f32(bhi[a] + t[a] + r) for a in range(3)],
+                        [-t[a] if t[a] else 0.0 for a in range(3)]))
+        return out
+
+    def _select(self, pos, r):
+        if self.periodic:
+            return select_images(pos, self.lo, self.hi, self._axes, r, self._selection(r))
+        if not self.images:
+            return pos, torch.empty(0, dtype=torch.long, device=pos.device), [], pos[:0]
+        # bounds in pos.dtype: per axis a superset of the r-ball
+        blo = torch.tensor([self.box(q)[0] for q, _, _ in self.images], dtype=pos.dtype, device=pos.device)
+        bhi = torch.tensor([self.box(q)[1] for q, _, _ in self.images], dtype=pos.dtype, device=pos.device)
+        ent, idx = _in_boxes(pos, blo - r, bhi + r)
+        return pos, idx, torch.bincount(ent, minlength=len(self.images)), pos[idx]
+
+    def _check_cutoff(self, pos, r):
+        check_cutoff(self.dims, self.lo, self.hi, self._axes, r)
+
+
 class SlabHalo(GridHalo):
     """Slabs along x: rank k owns ``x in [slab_lo, slab_hi)`` (given at ``setup``), unbounded in y and z."""
 
     def __init__(self, group=None):
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        world = _world_rank(group)[0]
         super().__init__((world, 1, 1), (0.0, -1e30, -1e30), (float(world), 1e30, 1e30), group)
         self.left = self.rank - 1 if self.rank > 0 else None
         self.right = self.rank + 1 if self.rank < self.world - 1 else None
@@ -487,11 +518,6 @@ def _morton_grid_args(lo, hi, n_cells):
     L = [_f32(np.float32(hi32[a]) - np.float32(lo32[a])) for a in range(3)]
     inv = [float(np.float32(n_cells[a]) / np.float32(L[a])) for a in range(3)]
     return lo32, hi32, inv
-
-
-def _check_f32_pos(pos, what):
-    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
-        raise TypeError(f"{what} positions must be [n,3] float32, got {tuple(pos.shape)} {pos.dtype}")
 
 
 def morton_keys_torch(pos, lo, hi, n_cells):
@@ -556,27 +582,13 @@ def select_morton(pos, lo, hi, n_cells, r, splitters, self_rank, workspace=None)
         return select_morton_torch(pos, lo, hi, n_cells, r, splitters, self_rank)
     from . import _lib
     _check_f32_pos(pos, "Morton halo")
-    lib = _lib.load()
     pos = pos.contiguous()
-    dev, n, P = pos.device, pos.shape[0], len(splitters) - 1
+    n, P = pos.shape[0], len(splitters) - 1
     spl = (ctypes.c_int32 * (P + 1))(*[int(v) for v in splitters])
     args = (_lib.Float3(*lo), _lib.Float3(*hi), _lib.Int3(*[int(v) for v in n_cells]), float(r), spl, P, int(self_rank))
-    counts = torch.zeros(max(P, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        wbytes = int(lib.e3_morton_select_workspace_bytes(n, P))
-        if wbytes < 0:
-            raise RuntimeError(f"e3_morton_select_workspace_bytes: unsupported size (n = {n}, {P} ranks)")
-        if workspace is None or workspace.numel() < wbytes:
-            workspace = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
-        _lib.check(lib.e3_morton_select_count(pos.data_ptr(), n, *args, counts.data_ptr(), workspace.data_ptr(), wbytes, stream),
-                   "e3_morton_select_count")
-        cnt = [int(v) for v in counts[:P].tolist()]                                 # the one host read of the selection
-        total = sum(cnt)
-        idx = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.e3_morton_select_fill(pos.data_ptr(), n, *args, total, idx.data_ptr(), workspace.data_ptr(), wbytes,
-                                             stream), "e3_morton_select_fill")
-    return idx[:total].long(), cnt
+    head = (pos.data_ptr(), n, *args)
+    cnt, (idx,) = _select_on_device("morton", "ranks", pos.device, n, P, head, head, workspace=workspace)
+    return idx.long(), cnt
 
 
 class MortonPartition:
@@ -666,31 +678,22 @@ class MortonPartition:
                 [self.lo[a] + (int(c[:, a].max()) + 1) * w[a] for a in range(3)])
 
 
-class MortonHalo(GridHalo):
+class MortonHalo(Halo):
     """Ghost halo of a fitted ``MortonPartition``: one entry per other rank, in ascending rank order, translation 0.  An
     owned particle is sent to every rank that owns a cell of ``[cell(p - r), cell(p + r)]`` (``select_morton``): cells are
     at least ``r`` wide and rounding is monotone, so a rank's ghosts are a superset of what its owned rows need.  After
-    ``setup`` everything is ``GridHalo``'s code; ``neighbours`` then lists the peers with a non-zero count in either
+    ``setup`` everything is ``Halo``'s code; ``neighbours`` then lists the peers with a non-zero count in either
     direction, and a peer with nothing to exchange costs one count message per ``setup`` and nothing per layer."""
 
     def __init__(self, partition: MortonPartition, group=None):
         partition._fitted()
         self.partition = partition
-        self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        if partition.world != self.world:
-            raise ValueError(f"the partition was made for {partition.world} ranks, the group has {self.world}")
-        self.dims = None
+        world, rank = _world_rank(group)
+        if partition.world != world:
+            raise ValueError(f"the partition was made for {partition.world} ranks, the group has {world}")
         self.lo, self.hi = list(partition.lo), list(partition.hi)
-        self.n_owned = 0
-        self.bytes_last_exchange = 0
-        self.periodic, self._axes = 0, (False, False, False)
-        self.images = [(q, (0, 0, 0), (0.0, 0.0, 0.0)) for q in range(self.world) if q != self.rank]
-        self.neighbours = [q for q, _, _ in self.images]
-        self._self_pairs = []
-        self._remote = list(range(len(self.images)))
-        self._send_ops = self._recv_ops = [(q, 0, e) for e, (q, _, _) in enumerate(self.images)]
+        ent = [(q, (0, 0, 0), (0.0, 0.0, 0.0)) for q in range(world) if q != rank]
+        super().__init__(group, ent, [0] * len(ent), [0] * len(ent))     # one message per peer and direction: tag 0
 
     def _check_cutoff(self, pos, r):
         _check_f32_pos(pos, "Morton halo")
@@ -709,7 +712,7 @@ class MortonHalo(GridHalo):
         return pos, idx, cnt, pos[idx]
 
     def setup(self, pos: torch.Tensor, feats: torch.Tensor, r: float):
-        """``GridHalo.setup`` with the Morton selection: fp32 positions (``TypeError`` otherwise), features of any dtype;
+        """``Halo.setup`` with the Morton selection: fp32 positions (``TypeError`` otherwise), features of any dtype;
         ``ValueError`` when ``r`` exceeds the partition's cell width on an axis with more than one cell."""
         out = super().setup(pos, feats, r)
         self.neighbours = [q for (q, _, _), s, c in zip(self.images, self.send_counts, self.recv_counts) if s or c]
@@ -725,8 +728,3 @@ class MortonHalo(GridHalo):
 
     def owner_of(self, pos: torch.Tensor) -> torch.Tensor:
         return self.partition.owner_of(pos)
-
-    def box(self, rank):
-        raise NotImplementedError("a Morton key range is not a box: see MortonPartition.owned_cell_bounds")
-
-    coords = box
