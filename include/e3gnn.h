@@ -173,6 +173,47 @@ int e3_rg_sort_count_pbc(const float* pos, int64_t N, const e3_rg_params* prm, i
 int e3_rg_fill_pbc(int64_t N, const e3_rg_params* prm, int32_t periodic, const float* sorted_pos4,
                    const int32_t* rowptr, int32_t* src, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* General (triclinic) periodic cell, periodic on all three lattice directions: the *_cell entries of the graph builder, the
+ * geometry, its backward, the strained pair and e3_msg_forward.  cell[9] (host fp32, row-major) holds the lattice vectors as
+ * rows, a_a = cell[3 a .. 3 a + 2] (the ASE convention); origin[3] (host fp32) is the corner the cell is spanned from.
+ * Derived on the host in fp64 from the fp32 entries and rounded once to fp32 (e3_cell_derive returns them):
+ *   G = cell^-1 (cofactors over the determinant), so the fractional coordinate is s = (p - origin) G;
+ *   heights h_a = 1 / |G[:, a]| (the distance between the two faces that a_a joins);  V = |det cell|.
+ * Every fp32 operation below is rounded on its own (no FMA contraction):
+ *   frac(v)_a   = fl(fl(fl(v_0 G[0,a]) + fl(v_1 G[1,a])) + fl(v_2 G[2,a]))
+ *   shift(v, n) : v_c <- fl(v_c - fl(fl(fl(n_0 cell[0,c]) + fl(n_1 cell[1,c])) + fl(n_2 cell[2,c])))
+ *   wrap   : s = frac(fl(p - origin)); w = shift(p, floorf(s)); then ONE correction step: s' = frac(fl(w - origin)) and, for
+ *            a = 0, 1, 2 in turn, s'_a >= 1 -> w = fl(w - a_a), else s'_a < 0 -> w = fl(w + a_a).  sorted_pos4 holds the
+ *            Cartesian w.
+ *   grid   : the open grid (e3_rg_grid, cell_of, Morton key above) of the points q_a = fl(frac(fl(w - origin))_a h_a) in the
+ *            box lo = 0, hi = h: n_a = clamp(floor(h_a / (r 1.0001f)), 1, 256).  prm is what e3_rg_grid makes of
+ *            lo = (0,0,0), hi = (h_0,h_1,h_2) and r; workspace, sort and call sequence are those of e3_rg_sort_count.
+ *   cells  : the 27 neighbour cells modulo n_a in every direction (a cell named twice, n_a <= 2, is scanned once).  q_a is
+ *            the coordinate along the unit normal of the faces of direction a, so a pair with |d| <= r has
+ *            |dq_a| <= r (modulo h_a) and lies at most one grid cell apart when the rounding of q is below half of the
+ *            1e-4 r margin of the cell width.  q carries 3 roundings of s and one of the product:
+ *            |err q_a| <= 2^-22 h_a K_a, K_a = sum_c |p_c - origin_c| |G[c,a]| (K_a = s_a <= 1 in an orthorhombic cell,
+ *            and at most the sum of the |s_b| |a_b| / h_a of a wrapped point in a skewed one), i.e. the bound holds for
+ *            r / h_a >= 2^-7 K_a at least (2 * 2^-22 K_a h_a <= 1e-4 r) -- the order of the n_a <= 256 clamp of the grid.
+ *   edge   : d = fl(x_i - x_j) on wrapped positions; in the cells whose 3x3x3 neighbourhood crosses a face of the grid, and
+ *            everywhere when some n_a < 5: d = shift(d, rintf(frac(d))) (elsewhere rintf(frac(d)) = 0: the shift is the
+ *            identity); then d2 and the test d2 <= fl(r*r) exactly as in the open box.
+ *   rel    : the edge vector of the geometry, message and backward kernels: d = fl(x_src - x_dst), rel = shift(d,
+ *            rintf(frac(d))) -- valid for wrapped and for unwrapped coordinates (positions moved by whole lattice vectors).
+ *            The shift is constant, so the backward is the open backward at rel.
+ * Requires finite entries, a non-singular cell and 0 < 2 r < min_a h_a (fp32 compare): the image of a pair with |d| <= r is
+ * then unique and is the one with every |ds_a| < 1/2, which rintf finds; for wrapped points n is in {-1,0,1}^3.  Otherwise
+ * E3_ERR_INVALID_ARG before any launch (the geometry and message entries have no cutoff: they check the cell alone).
+ * e3_rg_sort_count_cell also rejects a prm whose lo / hi are not 0 / the heights.  cell and origin must be the same in both
+ * calls of the builder.  Strain: r' = (I + eps_s) rel exactly as in e3_edge_geometry_strained; stress = (1/V) dE/deps. */
+int e3_cell_derive(const float cell[9], float ginv[9], float heights[3], float* volume);  /* host only */
+int e3_rg_sort_count_cell(const float* pos, int64_t N, const e3_rg_params* prm, const float cell[9], const float origin[3],
+                          int32_t* perm, float* sorted_pos4, int32_t* rowptr,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int e3_rg_fill_cell(int64_t N, const e3_rg_params* prm, const float cell[9], const float origin[3],
+                    const float* sorted_pos4, const int32_t* rowptr, int32_t* src,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =================================================================================================
  * Edge / node stages of the SEGNN forward around the tensor product (builder-defined, SURVEY.md
  * §8a-N2, N3; fp32).  Graph = CSR by dst from e3_rg_* (rowptr [N+1], src [E], positions pos4 [N,4]).
@@ -190,6 +231,9 @@ int e3_edge_geometry(const float* pos4, const int32_t* rowptr, const int32_t* sr
  * the backward is the open-box backward at the shifted vector.  A negative or non-finite L is E3_ERR_INVALID_ARG. */
 int e3_edge_geometry_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float box[3],
                          float* edge_y, float* edge_d, float* node_a, void* stream);
+/* general cell (cell[9] as in e3_rg_sort_count_cell): rel_e = the minimum image defined there */
+int e3_edge_geometry_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float cell[9],
+                          float* edge_y, float* edge_d, float* node_a, void* stream);
 /* out[e] = [ h[dst_e] (D) | h[src_e] (D) | extra[e] (n_extra, may be 0) ]   row strides in elements */
 int e3_gather_concat(const float* h, int64_t ld_h, int D, const int32_t* rowptr, const int32_t* src, int64_t N,
                      const float* extra, int n_extra, float* out, int64_t ld_out, void* stream);
@@ -467,6 +511,11 @@ int e3_msg_forward_pbc(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N
                        const int32_t* src, const int32_t* dst, int64_t E, const void* packed, const float* in_scale,
                        const float* premix, float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block,
                        const float box[3], void* stream);
+/* e3_msg_forward with Y_e, d_e of the minimum image in a general cell (cell[9] as in e3_rg_sort_count_cell) */
+int e3_msg_forward_cell(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const float* pos4,
+                        const int32_t* src, const int32_t* dst, int64_t E, const void* packed, const float* in_scale,
+                        const float* premix, float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block,
+                        const float cell[9], void* stream);
 /*
  * bf16 storage (dtype E3_BF16, BASELINE config 3): segments / in1 / out / weights / norms are bf16, in2 (the
  * spherical harmonics) stays fp32, products run once on v_mfma_f32_16x16x32_bf16 with fp32 accumulation and one
@@ -480,6 +529,9 @@ int e3_edge_geometry_l2(const float* pos4, const int32_t* rowptr, const int32_t*
 /* periodic box: as e3_edge_geometry_pbc */
 int e3_edge_geometry_l2_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float box[3],
                             float* edge_y, float* edge_d, float* node_a, void* stream);
+/* general cell: as e3_edge_geometry_cell */
+int e3_edge_geometry_l2_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float cell[9],
+                             float* edge_y, float* edge_d, float* node_a, void* stream);
 /* general gate: in = [ns scalars | g gate scalars | gated blocks], block i = mul_i x (2 l_i + 1) with one gate per
  * channel, gates consumed in block order; out = [silu(s) | sigmoid(gate) * block].  ls/muls: host int arrays. */
 int e3_gate_blocks(const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t B, int ns,
@@ -504,6 +556,10 @@ int e3_edge_geometry_backward(const float* pos4, const int32_t* rowptr, const in
 int e3_edge_geometry_backward_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                                   const float box[3], const float* g_edge_y, const float* g_edge_d,
                                   const float* g_node_a, float* g_pos, void* stream);
+/* general cell: as e3_edge_geometry_cell */
+int e3_edge_geometry_backward_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                   const float cell[9], const float* g_edge_y, const float* g_edge_d,
+                                   const float* g_node_a, float* g_pos, void* stream);
 int e3_gather_concat_backward(const float* g_out, int64_t ld_gout, int D, const int32_t* rowptr, const int32_t* src,
                               int64_t N, int n_extra, float* g_h, int64_t ld_gh, float* g_extra, void* stream);
 
@@ -539,6 +595,17 @@ int e3_edge_geometry_backward_strained(const float* pos4, const int32_t* rowptr,
                                        const float* box, const float* strain, const int32_t* structure, int S,
                                        const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
                                        float* g_strain, void* workspace, int64_t workspace_bytes, void* stream);
+/* The strained pair in a general cell (cell[9] as in e3_rg_sort_count_cell, required): r_e = the cell's minimum image,
+ * stress = (1/V) dE/deps with V = |det cell|.  Same outputs, workspace (e3_edge_geometry_backward_strained_workspace_bytes)
+ * and reproducibility contract (S = 1 fixed order, S > 1 atomics) as the two entries above. */
+int e3_edge_geometry_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                   const float cell[9], const float* strain, const int32_t* structure, int S,
+                                   float* edge_y, float* edge_d, float* node_a, void* stream);
+int e3_edge_geometry_backward_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N,
+                                            int lmax, const float cell[9], const float* strain, const int32_t* structure,
+                                            int S, const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
+                                            float* g_pos, float* g_strain, void* workspace, int64_t workspace_bytes,
+                                            void* stream);
 int e3_gate_blocks_backward(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, float* g_in,
                             int64_t ld_gin, int64_t B, int ns, int nblocks, const int32_t* ls, const int32_t* muls,
                             void* stream);

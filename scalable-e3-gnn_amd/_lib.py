@@ -22,6 +22,7 @@ _lib = None
 
 VoidP4 = c_void_p * 4
 Float3 = ctypes.c_float * 3  # a host float[3] argument (periodic box lengths)
+Float9 = ctypes.c_float * 9  # a host float[9] argument (a cell: rows = lattice vectors)
 Int3 = c_int32 * 3           # a host int32[3] argument (cells per axis)
 
 
@@ -110,6 +111,26 @@ SIGNATURES = {
     "e3_msg_forward_pbc": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, Float3,
                                    c_void_p]),
+    # general periodic cells (cell = float[9], rows = lattice vectors; origin = float[3])
+    "e3_cell_derive": (c_int, [Float9, Float9, Float3, POINTER(ctypes.c_float)]),
+    "e3_rg_sort_count_cell": (c_int, [c_void_p, c_int64, c_void_p, Float9, Float3, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_void_p]),
+    "e3_rg_fill_cell": (c_int, [c_int64, c_void_p, Float9, Float3, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                c_void_p]),
+    "e3_edge_geometry_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, Float9, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "e3_edge_geometry_l2_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, Float9, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "e3_edge_geometry_backward_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p]),
+    "e3_msg_forward_cell": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, Float9,
+                                    c_void_p]),
+    "e3_edge_geometry_strained_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p,
+                                               c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e3_edge_geometry_backward_strained_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p,
+                                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        c_void_p, c_int64, c_void_p]),
     "e3_gather_concat_backward": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
                                           c_void_p, c_void_p]),
     "e3_gate_blocks_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,

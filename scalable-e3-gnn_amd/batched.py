@@ -107,24 +107,33 @@ class BatchedEnergyModel(nn.Module):
 
 
 class PeriodicEnergyModel(nn.Module):
-    """SEGNN with a scalar node readout summed over a periodic (or partly periodic) orthorhombic box: the energy, and on
-    request forces, the virial and the stress of the box (conventions: include/e3gnn.h, e3_edge_geometry_strained).
-    The graph is built inside ``forward`` (``radius_graph(..., periodic=)``)."""
+    """SEGNN with a scalar node readout summed over a periodic (or partly periodic) orthorhombic box, or over a general
+    (triclinic) cell: the energy, and on request forces, the virial and the stress of the box (conventions:
+    include/e3gnn.h, e3_edge_geometry_strained).  The graph is built inside ``forward`` (``radius_graph(..., periodic=)``
+    or ``radius_graph(..., cell=)``)."""
 
     def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2):
         super().__init__()
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax)
 
-    def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo, hi, periodic=True, forces: bool = False,
-                virial: bool = False, stress: bool = False):
+    def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, forces: bool = False,
+                virial: bool = False, stress: bool = False, cell=None, origin=None):
         """x [N, in_dim], pos [N,3] (caller order; coordinates on periodic axes may be unwrapped).  -> the 0-d energy,
         then whichever of forces [N,3] (= -dE/dpos, caller order), virial W [3,3] (= -dE/deps at eps = 0, not
         symmetrised) and stress [3,3] (= (1/V) dE/deps = -W/V, V = L_x L_y L_z) were requested, in that order; the
-        energy alone when none was.  ``stress=True`` needs all three axes periodic (ValueError otherwise)."""
+        energy alone when none was.  ``stress=True`` needs all three axes periodic (ValueError otherwise).
+
+        ``cell`` (3x3, rows = lattice vectors) with ``origin``: a general cell instead of ``lo`` / ``hi`` / ``periodic``
+        (``radius_graph(cell=)``; always periodic on all three directions); the stress uses V = |det cell|."""
         from .radius_graph import periodic_mask
-        if stress and periodic_mask(periodic, r, lo, hi) != 7:
-            raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
-        g = radius_graph(pos, r, lo, hi, periodic=periodic)
+        if cell is not None:
+            if lo is not None or hi is not None or periodic is not True:
+                raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
+            g = radius_graph(pos, r, cell=cell, origin=origin)
+        else:
+            if stress and periodic_mask(periodic, r, lo, hi) != 7:
+                raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
+            g = radius_graph(pos, r, lo, hi, periodic=periodic)
         perm = g.perm.long()
         if not (forces or virial or stress):
             return self.net(x[perm], g)[:, 0].sum()
@@ -138,6 +147,6 @@ class PeriodicEnergyModel(nn.Module):
         if virial:
             out.append(-geps[0])
         if stress:
-            V = float(g.box[0]) * float(g.box[1]) * float(g.box[2])
+            V = float(g.volume) if g.cell is not None else float(g.box[0]) * float(g.box[1]) * float(g.box[2])
             out.append((geps[0].double() / V).float())
         return tuple(out)

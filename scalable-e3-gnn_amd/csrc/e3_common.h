@@ -100,11 +100,42 @@ __device__ __forceinline__ int cell_of(float p, float lo, float inv, int n) {
   int c = (int)floorf(t);
   return c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
 }
-// edge vector x_src - x_dst of the geometry kernels; PBC: its minimum image (the rint form, so unwrapped coordinates work too)
-template <bool PBC>
-__device__ __forceinline__ void edge_rel(const float4 pj, const float4 pi, const PbcBox& box, float& rx, float& ry,
-                                         float& rz) {
-  if constexpr (PBC) {
+// general (triclinic) periodic cell of the *_cell entries, periodic on all three lattice directions: h = the lattice vectors
+// (row a = a_a, row-major), g = fl32(h^-1) (row-major: the fractional coordinate is s_a = sum_c p_c g[3 c + a])
+struct PbcCell {
+  float h[9], g[9];
+};
+// periodicity of a kernel instantiation: open box, orthorhombic box (PbcBox), general cell (PbcCell); kOpen / kBox keep the
+// values of the former bool flag.  PbcArg<MODE>: the kernel argument of a mode (the open kernels carry an unread PbcBox)
+enum PbcMode : int { kOpen = 0, kBox = 1, kCell = 2 };
+template <int MODE> struct PbcArg { using type = PbcBox; };
+template <> struct PbcArg<kCell> { using type = PbcCell; };
+// fractional component a of a Cartesian vector, explicitly rounded: fl(fl(fl(x g0a) + fl(y g1a)) + fl(z g2a))
+__device__ __forceinline__ float cell_frac(const PbcCell& c, const int a, const float x, const float y, const float z) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(x, c.g[a]), __fmul_rn(y, c.g[3 + a])), __fmul_rn(z, c.g[6 + a]));
+}
+// d <- d - (n0 a_0 + n1 a_1 + n2 a_2), per component fl(d_c - fl(fl(fl(n0 h0c) + fl(n1 h1c)) + fl(n2 h2c)))
+__device__ __forceinline__ void cell_shift(const PbcCell& c, const float n0, const float n1, const float n2, float& dx,
+                                           float& dy, float& dz) {
+  dx = __fsub_rn(dx, __fadd_rn(__fadd_rn(__fmul_rn(n0, c.h[0]), __fmul_rn(n1, c.h[3])), __fmul_rn(n2, c.h[6])));
+  dy = __fsub_rn(dy, __fadd_rn(__fadd_rn(__fmul_rn(n0, c.h[1]), __fmul_rn(n1, c.h[4])), __fmul_rn(n2, c.h[7])));
+  dz = __fsub_rn(dz, __fadd_rn(__fadd_rn(__fmul_rn(n0, c.h[2]), __fmul_rn(n1, c.h[5])), __fmul_rn(n2, c.h[8])));
+}
+// minimum image of d in a cell (include/e3gnn.h): d - rint(d g) h -- the image with every |ds_a| <= 1/2
+__device__ __forceinline__ void min_image(const PbcCell& c, float& dx, float& dy, float& dz) {
+  const float n0 = rintf(cell_frac(c, 0, dx, dy, dz)), n1 = rintf(cell_frac(c, 1, dx, dy, dz)),
+              n2 = rintf(cell_frac(c, 2, dx, dy, dz));
+  cell_shift(c, n0, n1, n2, dx, dy, dz);
+}
+// edge vector x_src - x_dst of the geometry kernels; kBox / kCell: its minimum image (the rint form, so unwrapped
+// coordinates work too)
+template <int PBC>
+__device__ __forceinline__ void edge_rel(const float4 pj, const float4 pi, const typename PbcArg<PBC>::type& box, float& rx,
+                                         float& ry, float& rz) {
+  if constexpr (PBC == kCell) {
+    rx = __fsub_rn(pj.x, pi.x); ry = __fsub_rn(pj.y, pi.y); rz = __fsub_rn(pj.z, pi.z);
+    min_image(box, rx, ry, rz);
+  } else if constexpr (PBC == kBox) {
     rx = min_image(__fsub_rn(pj.x, pi.x), box.L[0], box.invL[0]);
     ry = min_image(__fsub_rn(pj.y, pi.y), box.L[1], box.invL[1]);
     rz = min_image(__fsub_rn(pj.z, pi.z), box.L[2], box.invL[2]);
@@ -156,6 +187,21 @@ inline PbcBox make_box(const float* box) {
     b.invL[a] = box[a] > 0.0f ? 1.0f / box[a] : 0.0f;
   }
   return b;
+}
+// host: what a cell[9] (rows = lattice vectors) derives (include/e3gnn.h, e3_cell_derive), in fp64 from the fp32 entries and
+// rounded once: ginv = cell^-1 (cofactors over the determinant), heights h_a = 1 / |column a of cell^-1|, volume = |det|.
+// false for a NULL, non-finite or singular cell (any derived value zero or non-finite in fp32).  e3_edge_ops.hip
+bool cell_derive(const float* cell, float ginv[9], float heights[3], float* volume);
+// host: the device cell of a *_cell entry, derived once: false unless the cell is derivable and 2 r < every height (r = 0:
+// the geometry entries, which have no cutoff).  `heights` (optional) receives the three perpendicular heights
+inline bool make_cell(const float* cell, float r, PbcCell* out, float* heights = nullptr) {
+  float hloc[3], v;
+  float* h = heights ? heights : hloc;
+  if (!cell_derive(cell, out->g, h, &v) || !(r >= 0.0f)) return false;
+  for (int a = 0; a < 3; ++a)
+    if (!(2.0f * r < h[a])) return false;
+  for (int k = 0; k < 9; ++k) out->h[k] = cell[k];
+  return true;
 }
 
 }  // namespace e3

@@ -23,13 +23,13 @@ constexpr float kS3 = 1.7320508075688772f, kS5 = 2.2360679774997896f;
 // LDS and writes one 9-float partial per block to gpart (fixed grid: the order of every sum is fixed), and
 // strain_partial_sum_kernel adds the partials.  S > 1: the rows of a structure are not contiguous, so each row is
 // wave-reduced and added with one 9-lane atomic into G[s] (order of arrival: not bitwise reproducible).
-template <int LMAX, bool PBC, bool STRAIN>
+template <int LMAX, int PBC, bool STRAIN>
 __global__ __launch_bounds__(256) void edge_geometry_bwd_kernel(const float4* __restrict__ pos4,
                                                                 const int32_t* __restrict__ rowptr,
                                                                 const int32_t* __restrict__ src, int64_t N,
                                                                 const float* __restrict__ gY, const float* __restrict__ gd,
                                                                 const float* __restrict__ gA, float* __restrict__ gpos,
-                                                                const PbcBox box, const StrainArg st,
+                                                                const typename PbcArg<PBC>::type box, const StrainArg st,
                                                                 float* __restrict__ gstrain, float* __restrict__ gpart) {
   constexpr int NY = (LMAX + 1) * (LMAX + 1);
   const int lane = threadIdx.x & 63;
@@ -251,27 +251,26 @@ static inline int wave_grid_b(int64_t N) { return (int)std::max<int64_t>(1, std:
 
 using namespace e3;
 
-// box: NULL = open, else validated by the caller; st: NULL = unstrained, else validated by the caller (g_strain [S,9],
-// workspace of e3_edge_geometry_backward_strained_workspace_bytes when S = 1)
+// one periodicity mode (box: the mode's kernel argument, validated by the caller); st: NULL = unstrained, else validated by
+// the caller (g_strain [S,9], workspace of e3_edge_geometry_backward_strained_workspace_bytes when S = 1)
+template <int PBC>
 static int edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                                   const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
-                                  const float* box, const StrainArg* st, float* g_strain, float* gpart, void* stream) {
+                                  const typename PbcArg<PBC>::type& b, const StrainArg* st, float* g_strain, float* gpart,
+                                  void* stream) {
   if (N < 0 || (lmax != 1 && lmax != 2)) return E3_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (st) E3_HIP_CHECK(hipMemsetAsync(g_strain, 0, (size_t)st->S * 9 * sizeof(float), s));
   if (N == 0) return E3_OK;
   if (!pos4 || !rowptr || !src || !g_pos) return E3_ERR_INVALID_ARG;
   E3_HIP_CHECK(hipMemsetAsync(g_pos, 0, (size_t)N * 3 * sizeof(float), s));
-  const PbcBox b = make_box(box);
   const int grid = wave_grid_b(N);
   if (!st) {
-    auto kern = lmax == 1 ? (box ? edge_geometry_bwd_kernel<1, true, false> : edge_geometry_bwd_kernel<1, false, false>)
-                          : (box ? edge_geometry_bwd_kernel<2, true, false> : edge_geometry_bwd_kernel<2, false, false>);
+    auto kern = lmax == 1 ? edge_geometry_bwd_kernel<1, PBC, false> : edge_geometry_bwd_kernel<2, PBC, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
                        g_node_a, g_pos, b, StrainArg{nullptr, nullptr, 0}, nullptr, nullptr);
   } else {
-    auto kern = lmax == 1 ? (box ? edge_geometry_bwd_kernel<1, true, true> : edge_geometry_bwd_kernel<1, false, true>)
-                          : (box ? edge_geometry_bwd_kernel<2, true, true> : edge_geometry_bwd_kernel<2, false, true>);
+    auto kern = lmax == 1 ? edge_geometry_bwd_kernel<1, PBC, true> : edge_geometry_bwd_kernel<2, PBC, true>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
                        g_node_a, g_pos, b, *st, g_strain, gpart);
     E3_HIP_CHECK(hipGetLastError());
@@ -279,6 +278,16 @@ static int edge_geometry_backward(const float* pos4, const int32_t* rowptr, cons
   }
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
+}
+// open (box NULL) or orthorhombic box
+static int edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,
+                                  const float* box, const StrainArg* st, float* g_strain, float* gpart, void* stream) {
+  const PbcBox b = make_box(box);
+  return box ? edge_geometry_backward<kBox>(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, b, st,
+                                            g_strain, gpart, stream)
+             : edge_geometry_backward<kOpen>(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, b, st,
+                                             g_strain, gpart, stream);
 }
 
 extern "C" {
@@ -314,6 +323,30 @@ int e3_edge_geometry_backward_strained(const float* pos4, const int32_t* rowptr,
   const StrainArg st = {strain, structure, S};
   return edge_geometry_backward(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, box, &st, g_strain,
                                 (float*)workspace, stream);
+}
+
+int e3_edge_geometry_backward_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                   const float cell[9], const float* g_edge_y, const float* g_edge_d,
+                                   const float* g_node_a, float* g_pos, void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_backward<kCell>(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, c, nullptr, nullptr,
+                                       nullptr, stream);
+}
+
+int e3_edge_geometry_backward_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N,
+                                            int lmax, const float cell[9], const float* strain, const int32_t* structure,
+                                            int S, const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
+                                            float* g_pos, float* g_strain, void* workspace, int64_t workspace_bytes,
+                                            void* stream) {
+  PbcCell c;
+  if (N < 0 || (lmax != 1 && lmax != 2) || !strain || S < 1 || !g_strain || !make_cell(cell, 0.0f, &c))
+    return E3_ERR_INVALID_ARG;
+  if (S == 1 && N > 0 && (!workspace || workspace_bytes < e3_edge_geometry_backward_strained_workspace_bytes(N)))
+    return E3_ERR_INVALID_ARG;
+  const StrainArg st = {strain, structure, S};
+  return edge_geometry_backward<kCell>(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, g_pos, c, &st, g_strain,
+                                       (float*)workspace, stream);
 }
 
 int e3_gather_concat_backward(const float* g_out, int64_t ld_gout, int D, const int32_t* rowptr, const int32_t* src,

@@ -4,6 +4,7 @@
 #include "e3_common.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace e3 {
 
@@ -11,13 +12,13 @@ constexpr float kSqrt3 = 1.7320508075688772f;
 
 // one wave per dst node: lanes over the row's edges; wave-reduce the mean of Y1.
 // STRAIN: r <- r + eps_s r with s the row's structure (StrainArg; read once per row); false = the unstrained kernel
-template <bool PBC, bool STRAIN>
+template <int PBC, bool STRAIN>
 __global__ __launch_bounds__(256) void edge_geometry_kernel(const float4* __restrict__ pos4,
                                                             const int32_t* __restrict__ rowptr,
                                                             const int32_t* __restrict__ src, int64_t N,
                                                             float4* __restrict__ edge_y, float* __restrict__ edge_d,
-                                                            float4* __restrict__ node_a, const PbcBox box,
-                                                            const StrainArg st) {
+                                                            float4* __restrict__ node_a,
+                                                            const typename PbcArg<PBC>::type box, const StrainArg st) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -128,13 +129,13 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const float* __restric
 
 
 // l <= 2 variant: Y [E,9] = [1 | sqrt3 u | sqrt5 b(u)], b = l=2 basis of oracle/cg.py; A [N,9] = [1 | mean Y_1..8]
-template <bool PBC, bool STRAIN>
+template <int PBC, bool STRAIN>
 __global__ __launch_bounds__(256) void edge_geometry_l2_kernel(const float4* __restrict__ pos4,
                                                                const int32_t* __restrict__ rowptr,
                                                                const int32_t* __restrict__ src, int64_t N,
                                                                float* __restrict__ edge_y, float* __restrict__ edge_d,
-                                                               float* __restrict__ node_a, const PbcBox box,
-                                                               const StrainArg st) {
+                                                               float* __restrict__ node_a,
+                                                               const typename PbcArg<PBC>::type box, const StrainArg st) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -240,28 +241,62 @@ static inline int wave_grid(int64_t N) { return (int)std::max<int64_t>(1, std::m
 
 using namespace e3;
 
-// lmax 1 / 2, open (box NULL) or periodic (box validated by the caller); st NULL = unstrained, else validated by the caller
+// lmax 1 / 2 in one periodicity mode (box: the mode's kernel argument, validated by the caller); st NULL = unstrained, else
+// validated by the caller
+template <int PBC>
 static int edge_geometry(int lmax, const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, float* edge_y,
-                         float* edge_d, float* node_a, const float* box, const StrainArg* st, void* stream) {
+                         float* edge_d, float* node_a, const typename PbcArg<PBC>::type& b, const StrainArg* st,
+                         void* stream) {
   if (N < 0) return E3_ERR_INVALID_ARG;
   if (N == 0) return E3_OK;
   if (!pos4 || !rowptr || !src || (!edge_y && !node_a)) return E3_ERR_INVALID_ARG;
-  const PbcBox b = make_box(box);
   const StrainArg sa = st ? *st : StrainArg{nullptr, nullptr, 0};
   const hipStream_t s = (hipStream_t)stream;
   if (lmax == 1) {
-    auto kern = st ? (box ? edge_geometry_kernel<true, true> : edge_geometry_kernel<false, true>)
-                   : (box ? edge_geometry_kernel<true, false> : edge_geometry_kernel<false, false>);
+    auto kern = st ? edge_geometry_kernel<PBC, true> : edge_geometry_kernel<PBC, false>;
     hipLaunchKernelGGL(kern, dim3(wave_grid(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, (float4*)edge_y,
                        edge_d, (float4*)node_a, b, sa);
   } else {
-    auto kern = st ? (box ? edge_geometry_l2_kernel<true, true> : edge_geometry_l2_kernel<false, true>)
-                   : (box ? edge_geometry_l2_kernel<true, false> : edge_geometry_l2_kernel<false, false>);
+    auto kern = st ? edge_geometry_l2_kernel<PBC, true> : edge_geometry_l2_kernel<PBC, false>;
     hipLaunchKernelGGL(kern, dim3(wave_grid(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, edge_y, edge_d,
                        node_a, b, sa);
   }
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
+}
+// open (box NULL) or orthorhombic box
+static int edge_geometry(int lmax, const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, float* edge_y,
+                         float* edge_d, float* node_a, const float* box, const StrainArg* st, void* stream) {
+  const PbcBox b = make_box(box);
+  return box ? edge_geometry<kBox>(lmax, pos4, rowptr, src, N, edge_y, edge_d, node_a, b, st, stream)
+             : edge_geometry<kOpen>(lmax, pos4, rowptr, src, N, edge_y, edge_d, node_a, b, st, stream);
+}
+
+// fp64 from the fp32 entries; contraction off: tests/triclinic_reference.py restates these expressions bit for bit
+bool e3::cell_derive(const float* cell, float ginv[9], float heights[3], float* volume) {
+#pragma clang fp contract(off)
+  if (!cell) return false;
+  double a[9];
+  for (int k = 0; k < 9; ++k) {
+    if (!(fabs((double)cell[k]) < 3.0e38)) return false;
+    a[k] = (double)cell[k];
+  }
+  const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
+  const double c10 = a[2] * a[7] - a[1] * a[8], c11 = a[0] * a[8] - a[2] * a[6], c12 = a[1] * a[6] - a[0] * a[7];
+  const double c20 = a[1] * a[5] - a[2] * a[4], c21 = a[2] * a[3] - a[0] * a[5], c22 = a[0] * a[4] - a[1] * a[3];
+  const double det = (a[0] * c00 + a[1] * c01) + a[2] * c02;
+  if (!(fabs(det) > 0.0)) return false;
+  const double g[9] = {c00 / det, c10 / det, c20 / det, c01 / det, c11 / det, c21 / det, c02 / det, c12 / det, c22 / det};
+  for (int k = 0; k < 9; ++k) {
+    ginv[k] = (float)g[k];
+    if (!(fabsf(ginv[k]) < 3.0e38f)) return false;
+  }
+  for (int c = 0; c < 3; ++c) {
+    heights[c] = (float)(1.0 / sqrt((g[c] * g[c] + g[3 + c] * g[3 + c]) + g[6 + c] * g[6 + c]));
+    if (!(heights[c] > 0.0f && heights[c] < 3.0e38f)) return false;
+  }
+  *volume = (float)fabs(det);
+  return *volume > 0.0f && *volume < 3.0e38f;
 }
 
 extern "C" {
@@ -275,6 +310,34 @@ int e3_edge_geometry_pbc(const float* pos4, const int32_t* rowptr, const int32_t
                          float* edge_y, float* edge_d, float* node_a, void* stream) {
   if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
   return edge_geometry(1, pos4, rowptr, src, N, edge_y, edge_d, node_a, box, nullptr, stream);
+}
+
+int e3_cell_derive(const float cell[9], float ginv[9], float heights[3], float* volume) {
+  if (!ginv || !heights || !volume) return E3_ERR_INVALID_ARG;
+  return cell_derive(cell, ginv, heights, volume) ? E3_OK : E3_ERR_INVALID_ARG;
+}
+
+int e3_edge_geometry_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float cell[9],
+                          float* edge_y, float* edge_d, float* node_a, void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return edge_geometry<kCell>(1, pos4, rowptr, src, N, edge_y, edge_d, node_a, c, nullptr, stream);
+}
+
+int e3_edge_geometry_l2_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, const float cell[9],
+                             float* edge_y, float* edge_d, float* node_a, void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return edge_geometry<kCell>(2, pos4, rowptr, src, N, edge_y, edge_d, node_a, c, nullptr, stream);
+}
+
+int e3_edge_geometry_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                   const float cell[9], const float* strain, const int32_t* structure, int S,
+                                   float* edge_y, float* edge_d, float* node_a, void* stream) {
+  PbcCell c;
+  if ((lmax != 1 && lmax != 2) || !strain || S < 1 || !make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  const StrainArg st = {strain, structure, S};
+  return edge_geometry<kCell>(lmax, pos4, rowptr, src, N, edge_y, edge_d, node_a, c, &st, stream);
 }
 
 int e3_gather_concat(const float* h, int64_t ld_h, int D, const int32_t* rowptr, const int32_t* src, int64_t N,

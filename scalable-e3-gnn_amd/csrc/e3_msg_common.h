@@ -116,14 +116,11 @@ __device__ __forceinline__ void split8(const float (&f)[8], uint4& bh, uint4& bl
 }
 
 // real "component" spherical harmonics of the edge vector (same expressions as edge_geometry_l2_kernel, e3_edge_ops.hip)
-template <bool PBC = false>
-__device__ __forceinline__ void edge_sh(const float4 ps, const float4 pd, float (&y)[9], float& dist, const PbcBox& box = {}) {
-  float rx = ps.x - pd.x, ry = ps.y - pd.y, rz = ps.z - pd.z;
-  if constexpr (PBC) {
-    rx = min_image(__fsub_rn(ps.x, pd.x), box.L[0], box.invL[0]);
-    ry = min_image(__fsub_rn(ps.y, pd.y), box.L[1], box.invL[1]);
-    rz = min_image(__fsub_rn(ps.z, pd.z), box.L[2], box.invL[2]);
-  }
+template <int PBC = kOpen>
+__device__ __forceinline__ void edge_sh(const float4 ps, const float4 pd, float (&y)[9], float& dist,
+                                        const typename PbcArg<PBC>::type& box = {}) {
+  float rx, ry, rz;
+  edge_rel<PBC>(ps, pd, box, rx, ry, rz);
   const float d = sqrtf(rx * rx + ry * ry + rz * rz);
   const float inv = d > 0.f ? 1.0f / d : 0.f;
   const float x = rx * inv, yy = ry * inv, z = rz * inv;
@@ -138,14 +135,11 @@ __device__ __forceinline__ void edge_sh(const float4 ps, const float4 pd, float 
   dist = d;
 }
 // l <= 1 variant: identical to edge_geometry_kernel (s = sqrt3 / d folded first)
-template <bool PBC = false>
-__device__ __forceinline__ void edge_sh1(const float4 ps, const float4 pd, float (&y)[9], float& dist, const PbcBox& box = {}) {
-  float rx = ps.x - pd.x, ry = ps.y - pd.y, rz = ps.z - pd.z;
-  if constexpr (PBC) {
-    rx = min_image(__fsub_rn(ps.x, pd.x), box.L[0], box.invL[0]);
-    ry = min_image(__fsub_rn(ps.y, pd.y), box.L[1], box.invL[1]);
-    rz = min_image(__fsub_rn(ps.z, pd.z), box.L[2], box.invL[2]);
-  }
+template <int PBC = kOpen>
+__device__ __forceinline__ void edge_sh1(const float4 ps, const float4 pd, float (&y)[9], float& dist,
+                                        const typename PbcArg<PBC>::type& box = {}) {
+  float rx, ry, rz;
+  edge_rel<PBC>(ps, pd, box, rx, ry, rz);
   const float d = sqrtf(rx * rx + ry * ry + rz * rz);
   const float s = d > 0.f ? 1.7320508075688772f / d : 0.f;
   y[0] = 1.0f; y[1] = s * rx; y[2] = s * ry; y[3] = s * rz;

@@ -26,7 +26,9 @@
 #include "e3_msg_ws.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -530,14 +532,24 @@ constexpr int msg_waves_per_simd(int lmax, int tt) {
   return (lmax == 2 ? 44 : 20) * tt <= 96 ? ((lmax == 2 && tt == 2) ? E3_MSG_WPS : 2) : 1;
 }
 
-template <int LMAX, int TT, bool IO16, bool PBC>
+// The explicit arguments of msg_fused_kernel as the kernel-argument segment lays them out (in order, natural alignment):
+// where the cell instantiations find their cell.  CONTRACT: this is the kernel's parameter list, field for field; the
+// static_asserts behind the kernel compare the two and pin the offset, so a parameter added or moved there fails the build
+// here instead of reading something else as the cell.
+struct MsgFusedKernarg {
+  const void* hv; int64_t ldh; const float4* pos4; const int32_t *src, *dst; int64_t E; const float *packed, *U, *in_scale;
+  float* out; int64_t ldo; int blk;
+  PbcCell cell;
+};
+template <int LMAX, int TT, bool IO16, int PBC>
 // (waves per SIMD fixed from both sides: with the minimum alone the scheduler of a small instantiation -- l_max = 1 needs ~120
 // registers -- trades its load / compute overlap for an occupancy the launch does not use: 6.7 -> 8.7 ms)
 __global__ __launch_bounds__(256, msg_waves_per_simd(LMAX, TT))
 __attribute__((amdgpu_waves_per_eu(msg_waves_per_simd(LMAX, TT), msg_waves_per_simd(LMAX, TT)))) void msg_fused_kernel(
     const void* __restrict__ hv, int64_t ldh, const float4* __restrict__ pos4, const int32_t* __restrict__ src,
     const int32_t* __restrict__ dst, int64_t E, const float* __restrict__ packed, const float* __restrict__ U,
-    const float* __restrict__ in_scale, float* __restrict__ out, int64_t ldo, int blk, const PbcBox box) {
+    const float* __restrict__ in_scale, float* __restrict__ out, int64_t ldo, int blk,
+    const typename PbcArg<PBC>::type box) {
   using G = MsgGeom<LMAX, TT>;
   constexpr int H = G::H, D = G::D, T0 = G::T(0), NS = G::NS;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -709,7 +721,27 @@ __attribute__((amdgpu_waves_per_eu(msg_waves_per_simd(LMAX, TT), msg_waves_per_s
       float y[9], dist;
       {
         const float4 ps = pos4[sid], pd = pos4[did];
-        if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, box); else edge_sh1<PBC>(ps, pd, y, dist, box);
+        if constexpr (PBC == kCell) {
+          // The 18 cell entries are read from the kernel-argument segment HERE, once per tile: scalar loads into SGPRs that
+          // are free again after the geometry (the offset passes through an empty asm, so the loads are not hoisted out
+          // of the tile loop).  Held across the products they took the SGPRs that the tile loop's uniform values live
+          // in, and those moved to VGPRs: the bf16 l_max = 1, H = 32 instantiation went from 104 to 131 VGPRs and lost
+          // a wave per SIMD.
+          typedef const __attribute__((address_space(4))) char* karg_ptr_t;
+          const karg_ptr_t ka = (karg_ptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+          int off = offsetof(MsgFusedKernarg, cell);
+          asm volatile("" : "+s"(off));
+          const __attribute__((address_space(4))) float* cp = (const __attribute__((address_space(4))) float*)(ka + off);
+          PbcCell c;
+#pragma unroll
+          for (int k = 0; k < 9; ++k) {
+            c.h[k] = cp[k];
+            c.g[k] = cp[9 + k];
+          }
+          if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, c); else edge_sh1<PBC>(ps, pd, y, dist, c);
+        } else {
+          if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, box); else edge_sh1<PBC>(ps, pd, y, dist, box);
+        }
       }
       f32x4 a0[T0], a1[TT][3], a2[LMAX == 2 ? TT : 1][5];
       const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -959,6 +991,17 @@ __attribute__((amdgpu_waves_per_eu(msg_waves_per_simd(LMAX, TT), msg_waves_per_s
 #undef E3_STAMP
 }
 
+// MsgFusedKernarg against the kernel's signature (see the struct)
+static_assert(std::is_same_v<decltype(&msg_fused_kernel<1, 1, false, kCell>),
+                             void (*)(decltype(MsgFusedKernarg::hv), decltype(MsgFusedKernarg::ldh), decltype(MsgFusedKernarg::pos4),
+                                      decltype(MsgFusedKernarg::src), decltype(MsgFusedKernarg::dst), decltype(MsgFusedKernarg::E),
+                                      decltype(MsgFusedKernarg::packed), decltype(MsgFusedKernarg::U),
+                                      decltype(MsgFusedKernarg::in_scale), decltype(MsgFusedKernarg::out),
+                                      decltype(MsgFusedKernarg::ldo), decltype(MsgFusedKernarg::blk),
+                                      decltype(MsgFusedKernarg::cell))>,
+              "MsgFusedKernarg must list the parameters of msg_fused_kernel in order");
+static_assert(offsetof(MsgFusedKernarg, cell) == 92 && sizeof(PbcCell) == 72, "the cell follows `int blk` at byte 92");
+
 // ------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------
@@ -966,6 +1009,7 @@ struct MsgKernels {
   int lmax, tt;
   const void* fused[2];   // [0] fp32 storage, [1] bf16 storage (nullptr: not instantiated)
   const void* fused_pbc[2];  // the same with the periodic minimum image (e3_msg_forward_pbc)
+  const void* fused_cell[2];  // the same with the minimum image of a general cell (e3_msg_forward_cell)
   const void* premix[2];
   int64_t total_floats;
   int UD, D, lds_tab, lds_wave, nblk, NS, WD, o_norm1, o_norm2, o_wd, o_w, waves_per_simd;
@@ -973,14 +1017,16 @@ struct MsgKernels {
 template <int LMAX, int TT>
 static MsgKernels make_entry() {
   using G = MsgGeom<LMAX, TT>;
-  MsgKernels k = {LMAX, TT, {(const void*)msg_fused_kernel<LMAX, TT, false, false>, nullptr},
-                  {(const void*)msg_fused_kernel<LMAX, TT, false, true>, nullptr},
+  MsgKernels k = {LMAX, TT, {(const void*)msg_fused_kernel<LMAX, TT, false, kOpen>, nullptr},
+                  {(const void*)msg_fused_kernel<LMAX, TT, false, kBox>, nullptr},
+                  {(const void*)msg_fused_kernel<LMAX, TT, false, kCell>, nullptr},
                   {(const void*)msg_premix_kernel<LMAX, TT, false>, nullptr}, G::total_floats,
                   G::UD, G::D, G::lds_tab, G::lds_wave, G::nblk(), G::NS, G::WD, G::o_norm1, G::o_norm2, G::o_wd, G::o_w,
                   msg_waves_per_simd(LMAX, TT)};
   if constexpr (TT >= 2) {  // bf16 storage: the [0e] region of a staged row must be at least 4 units of 16 bytes (H >= 32)
-    k.fused[1] = (const void*)msg_fused_kernel<LMAX, TT, true, false>;
-    k.fused_pbc[1] = (const void*)msg_fused_kernel<LMAX, TT, true, true>;
+    k.fused[1] = (const void*)msg_fused_kernel<LMAX, TT, true, kOpen>;
+    k.fused_pbc[1] = (const void*)msg_fused_kernel<LMAX, TT, true, kBox>;
+    k.fused_cell[1] = (const void*)msg_fused_kernel<LMAX, TT, true, kCell>;
     k.premix[1] = (const void*)msg_premix_kernel<LMAX, TT, true>;
   }
   return k;
@@ -1005,6 +1051,7 @@ struct e3_msg_plan {
   int device = -1;
   int grid[2] = {0, 0};  // workgroups of a full launch per storage type: CUs x resident workgroups per CU (occupancy query)
   int grid_pbc[2] = {0, 0};  // the same for the periodic instantiations
+  int grid_cell[2] = {0, 0};  // ... and the cell instantiations (0 until the first cell launch: msg_ensure_cell)
   std::mutex mu;
 };
 
@@ -1039,6 +1086,22 @@ static int msg_ensure_device(e3_msg_plan* P) {
   }
   P->device = cur;
   P->d_desc = d;
+  return E3_OK;
+}
+
+// The cell kernels' slot of a plan that msg_ensure_device has set up, filled by the first cell launch: a plan that only
+// ever sees open or orthorhombic graphs never touches the cell instantiations.
+static int msg_ensure_cell(e3_msg_plan* P, int io) {
+  std::lock_guard<std::mutex> lock(P->mu);
+  if (P->grid_cell[io]) return E3_OK;
+  const size_t lds = (size_t)(P->k->lds_tab + 4 * P->k->lds_wave) * 4 + 4 * 256;
+  int cus = 0, per_cu = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, P->device) != hipSuccess || cus <= 0) cus = 256;
+  const void* kern = P->k->fused_cell[io];
+  if (!kern || hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu < 1)
+    return E3_ERR_HIP;
+  P->grid_cell[io] = cus * (per_cu < 4 ? per_cu : 4);
   return E3_OK;
 }
 
@@ -1171,11 +1234,12 @@ int e3_msg_premix(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const 
 
 }  // extern "C"
 
-// box: NULL = the open kernels; else L per axis (0 = open axis), already validated
+// box: NULL = the open kernels; else L per axis (0 = open axis), already validated.  cell (excludes box): NULL, or what
+// make_cell derived = the cell kernels
 static int msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
                        const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
                        float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block, void* stream,
-                       const float* box) {
+                       const float* box, const PbcCell* cell = nullptr) {
   if (!P || N < 0 || E < 0 || E > 0x7fffffffLL - 16) return E3_ERR_INVALID_ARG;  // edge ids are int32
   if (!e3_msg_supports(P, dtype)) return E3_ERR_UNSUPPORTED;
   const MsgKernels& k = *P->k;
@@ -1194,20 +1258,24 @@ static int msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, c
   // tiles_per_block < 0 asks for this file's one-wave-per-tile kernel with |tiles_per_block| tiles per wave block.
   if (tiles_per_block >= 0 && msg_ws_supported(P->lmax, P->H, dtype)) {
     st = msg_ws_launch(P->lmax, P->H, dtype, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out,
-                       tiles_per_block > (1 << 20) ? (1 << 24) : tiles_per_block * 16, s, box);
+                       tiles_per_block > (1 << 20) ? (1 << 24) : tiles_per_block * 16, s, box, cell);
     if (st != E3_ERR_UNSUPPORTED) return st;
   }
   if (tiles_per_block < 0) tiles_per_block = -tiles_per_block;
+  if (cell && (st = msg_ensure_cell(P, io)) != E3_OK) return st;
   const int64_t ntiles = (E + 15) / 16;
-  int nwg = (box ? P->grid_pbc : P->grid)[io];  // 4 waves per workgroup, every CU filled once
+  int nwg = (cell ? P->grid_cell : (box ? P->grid_pbc : P->grid))[io];  // 4 waves per workgroup, every CU filled once
   nwg = (int)std::min<int64_t>(nwg, (ntiles + 3) / 4);
   nwg = std::max(8, (nwg + 7) / 8 * 8);
   int blk = tiles_per_block > 0 ? tiles_per_block : 4;  // default: 64 edges (2-3 dst nodes) per wave block
   if (blk > (1 << 16)) blk = 1 << 16;
   const size_t lds = (size_t)(k.lds_tab + 4 * k.lds_wave) * 4 + 4 * 256;
-  PbcBox pbox = make_box(box);
-  void* args[] = {&h, &ld_h, &pos4, &src, &dst, &E, &packed, &premix, &in_scale, &out, &ld_out, &blk, &pbox};
-  if (hipLaunchKernel(box ? k.fused_pbc[io] : k.fused[io], dim3(nwg), dim3(256), args, lds, s) != hipSuccess)
+  PbcBox pbox;
+  if (!cell) pbox = make_box(box);
+  void* args[] = {&h, &ld_h, &pos4, &src, &dst, &E, &packed, &premix, &in_scale, &out, &ld_out, &blk,
+                  cell ? (void*)cell : (void*)&pbox};
+  if (hipLaunchKernel(cell ? k.fused_cell[io] : (box ? k.fused_pbc[io] : k.fused[io]), dim3(nwg), dim3(256), args, lds,
+                      s) != hipSuccess)
     return E3_ERR_HIP;
   return E3_OK;
 }
@@ -1228,6 +1296,16 @@ int e3_msg_forward_pbc(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, c
   if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
   return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, accumulate,
                      tiles_per_block, stream, box);
+}
+
+int e3_msg_forward_cell(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
+                        const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
+                        float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block, const float cell[9],
+                        void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, accumulate,
+                     tiles_per_block, stream, nullptr, &c);
 }
 
 #if E3_MSG_STAMP

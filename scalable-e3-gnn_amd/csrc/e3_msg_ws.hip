@@ -43,6 +43,7 @@
 #include "e3_msg_ws.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #ifndef E3_WS_STAMP
 #define E3_WS_STAMP 0   // 1: per-wave cycle counters (phase A work / barrier / phase B work / barrier) -- development builds only
@@ -485,16 +486,18 @@ __device__ __forceinline__ void ws_tp(const RoleW<Own<LMAX, TT, ROLE>::NW>& w, c
 // ------------------------------------------------------------------------------------------------------------------
 // kernel
 // ------------------------------------------------------------------------------------------------------------------
-struct WsArgs {
+template <class BOX>
+struct WsArgsT {
   const void* h; int64_t ldh;
   const float4* pos4; const int32_t* src; const int32_t* dst; int64_t E;
   const float* packed; const float* U; const float* hmax; const float* in_scale; float* out; int64_t ldo;
   int chunk;  // edges per chunk (multiple of 16)
-  PbcBox box;  // periodic instantiations only (the open kernel never reads it)
+  BOX box;  // periodic instantiations only (the open kernel never reads it); PbcCell for the cell instantiations
 };
+using WsArgs = WsArgsT<PbcBox>;
 
-template <int LMAX, int TT, bool IO16, int W, bool PBC>
-__device__ __forceinline__ void ws_run(const WsArgs& A, unsigned char* smem) {
+template <int LMAX, int TT, bool IO16, int W, int PBC>
+__device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>& A, unsigned char* smem) {
   using G = MsgGeom<LMAX, TT>;
   using L = Ws<LMAX, TT, IO16>;
   constexpr int H = G::H, D = G::D, ES = L::ES;
@@ -1062,10 +1065,11 @@ __device__ __forceinline__ void ws_run(const WsArgs& A, unsigned char* smem) {
 #undef WS_STAMP
 }
 
-template <int LMAX, int TT, bool IO16, bool PBC>
+template <int LMAX, int TT, bool IO16, int PBC>
 // (waves per SIMD fixed from both sides: the LDS image admits one workgroup per CU = 2 waves per SIMD; with the minimum alone
 // hipcc schedules for a third wave -- it held the kernel at 167 registers by issuing every LDS read right in front of its use)
-__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void msg_ws_kernel(const WsArgs A) {
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void msg_ws_kernel(
+    const WsArgsT<typename PbcArg<PBC>::type> A) {
   using G = MsgGeom<LMAX, TT>;
   using L = Ws<LMAX, TT, IO16>;
   extern __shared__ __align__(16) unsigned char ws_smem[];
@@ -1103,30 +1107,35 @@ bool msg_ws_supported(int lmax, int hidden, int dtype) {
 
 int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, int64_t N, const float* pos4, const int32_t* src,
                   const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix, float* out,
-                  int64_t ldo, int chunk_edges, hipStream_t stream, const float* box) {
+                  int64_t ldo, int chunk_edges, hipStream_t stream, const float* box, const PbcCell* cell) {
   if (!msg_ws_supported(lmax, hidden, dtype)) return E3_ERR_UNSUPPORTED;
-  const int pb = box ? 1 : 0;
+  const int pb = cell ? kCell : (box ? kBox : kOpen);
   if (E > 0x7fffffffLL - 65536) return E3_ERR_UNSUPPORTED;  // 32-bit edge arithmetic with chunk head room
   const int io = dtype == E3_BF16 ? 1 : 0;
   const int li = lmax == 2 ? 1 : 0;
 #if WS_LMAX1
   const void* kern =
-      pb ? (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, true> : (const void*)msg_ws_kernel<2, 2, false, true>)
-               : (io ? (const void*)msg_ws_kernel<1, 2, true, true> : (const void*)msg_ws_kernel<1, 2, false, true>))
-         : (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, false> : (const void*)msg_ws_kernel<2, 2, false, false>)
-               : (io ? (const void*)msg_ws_kernel<1, 2, true, false> : (const void*)msg_ws_kernel<1, 2, false, false>));
+      pb == kCell
+          ? (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, kCell> : (const void*)msg_ws_kernel<2, 2, false, kCell>)
+                : (io ? (const void*)msg_ws_kernel<1, 2, true, kCell> : (const void*)msg_ws_kernel<1, 2, false, kCell>))
+      : pb ? (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, kBox> : (const void*)msg_ws_kernel<2, 2, false, kBox>)
+                 : (io ? (const void*)msg_ws_kernel<1, 2, true, kBox> : (const void*)msg_ws_kernel<1, 2, false, kBox>))
+           : (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, kOpen> : (const void*)msg_ws_kernel<2, 2, false, kOpen>)
+                 : (io ? (const void*)msg_ws_kernel<1, 2, true, kOpen> : (const void*)msg_ws_kernel<1, 2, false, kOpen>));
   const int lds = li ? (io ? Ws<2, 2, true>::total : Ws<2, 2, false>::total) : (io ? Ws<1, 2, true>::total : Ws<1, 2, false>::total);
   const int ud = li ? MsgGeom<2, 2>::UD : MsgGeom<1, 2>::UD;
 #else
-  const void* kern = pb ? (io ? (const void*)msg_ws_kernel<2, 2, true, true> : (const void*)msg_ws_kernel<2, 2, false, true>)
-                        : (io ? (const void*)msg_ws_kernel<2, 2, true, false> : (const void*)msg_ws_kernel<2, 2, false, false>);
+  const void* kern =
+      pb == kCell ? (io ? (const void*)msg_ws_kernel<2, 2, true, kCell> : (const void*)msg_ws_kernel<2, 2, false, kCell>)
+      : pb        ? (io ? (const void*)msg_ws_kernel<2, 2, true, kBox> : (const void*)msg_ws_kernel<2, 2, false, kBox>)
+                  : (io ? (const void*)msg_ws_kernel<2, 2, true, kOpen> : (const void*)msg_ws_kernel<2, 2, false, kOpen>);
   const int lds = io ? Ws<2, 2, true>::total : Ws<2, 2, false>::total;
   const int ud = MsgGeom<2, 2>::UD;
 #endif
   int dev = 0;
   E3_HIP_CHECK(hipGetDevice(&dev));
   static std::mutex mu;
-  static int cus_of[64][2][2][2];
+  static int cus_of[64][2][2][3];
   int cus = 0;
   {
     std::lock_guard<std::mutex> lock(mu);
@@ -1144,11 +1153,14 @@ int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, i
   int nwg = (int)std::min<int64_t>(cus, nchunks);  // one workgroup of 8 waves per CU
   nwg = std::max(8, (nwg + 7) / 8 * 8);
   const float* hmax = premix + (size_t)N * ud;  // per-node row maxima behind the table (e3_msg_premix)
-  WsArgs a = {h, ldh, reinterpret_cast<const float4*>(pos4), src, dst, E, static_cast<const float*>(packed), premix, hmax,
-              in_scale, out, ldo, chunk, make_box(box)};
-  void* args[] = {&a};
-  if (hipLaunchKernel(kern, dim3(nwg), dim3(512), args, lds, stream) != hipSuccess) return E3_ERR_HIP;
-  return E3_OK;
+  // the argument block of the mode: the box / cell sits behind the common fields (kernel-argument segment: SGPRs)
+  auto launch = [&](const auto& pbc) {
+    WsArgsT<std::decay_t<decltype(pbc)>> a = {h, ldh, reinterpret_cast<const float4*>(pos4), src, dst, E,
+                                              static_cast<const float*>(packed), premix, hmax, in_scale, out, ldo, chunk, pbc};
+    void* args[] = {&a};
+    return hipLaunchKernel(kern, dim3(nwg), dim3(512), args, lds, stream) == hipSuccess ? E3_OK : E3_ERR_HIP;
+  };
+  return cell ? launch(*cell) : launch(make_box(box));
 }
 
 }  // namespace e3

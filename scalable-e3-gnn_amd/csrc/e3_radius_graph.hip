@@ -35,10 +35,47 @@ struct RgPbc {
   int periodic;
 };
 
-template <bool PBC>
-__device__ __forceinline__ float3 load_pos(const float* __restrict__ pos, const int64_t o, const RgDev& g, const RgPbc& pb) {
+// general cell (the *_cell entries; include/e3gnn.h): lattice vectors and their inverse, the origin, and the perpendicular
+// heights (the grid is the open grid of q_a = s_a h_a in [0, h_a): g.lo = 0, 1 / g.inv = h_a / n_a)
+struct RgCell {
+  PbcCell c;
+  float o[3], hgt[3];
+};
+// the periodic argument of a mode's kernels (the open kernels carry an unread RgPbc)
+template <int MODE> struct RgArg { using type = RgPbc; };
+template <> struct RgArg<kCell> { using type = RgCell; };
+
+// fractional coordinates of p relative to the origin
+__device__ __forceinline__ void cell_s(const RgCell& rc, const float3 p, float (&s)[3]) {
+  const float x = __fsub_rn(p.x, rc.o[0]), y = __fsub_rn(p.y, rc.o[1]), z = __fsub_rn(p.z, rc.o[2]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) s[a] = cell_frac(rc.c, a, x, y, z);
+}
+// p wrapped into the cell: w = p - floor(s(p)) h, then one correction step per lattice direction from s(w)
+__device__ __forceinline__ float3 wrap_cell(const RgCell& rc, float3 p) {
+  float s[3];
+  cell_s(rc, p, s);
+  cell_shift(rc.c, floorf(s[0]), floorf(s[1]), floorf(s[2]), p.x, p.y, p.z);
+  cell_s(rc, p, s);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float n = s[a] >= 1.0f ? 1.0f : (s[a] < 0.0f ? -1.0f : 0.0f);
+    if (n != 0.0f) {
+      p.x = __fsub_rn(p.x, __fmul_rn(n, rc.c.h[3 * a + 0]));
+      p.y = __fsub_rn(p.y, __fmul_rn(n, rc.c.h[3 * a + 1]));
+      p.z = __fsub_rn(p.z, __fmul_rn(n, rc.c.h[3 * a + 2]));
+    }
+  }
+  return p;
+}
+
+template <int PBC>
+__device__ __forceinline__ float3 load_pos(const float* __restrict__ pos, const int64_t o, const RgDev& g,
+                                           const typename RgArg<PBC>::type& pb) {
   float3 p = make_float3(pos[3 * o + 0], pos[3 * o + 1], pos[3 * o + 2]);
-  if constexpr (PBC) {
+  if constexpr (PBC == kCell) {
+    p = wrap_cell(pb, p);
+  } else if constexpr (PBC == kBox) {
     if (pb.periodic & 1) p.x = wrap_coord(p.x, g.lo[0], pb.hi[0], pb.L[0], pb.invL[0]);
     if (pb.periodic & 2) p.y = wrap_coord(p.y, g.lo[1], pb.hi[1], pb.L[1], pb.invL[1]);
     if (pb.periodic & 4) p.z = wrap_coord(p.z, g.lo[2], pb.hi[2], pb.L[2], pb.invL[2]);
@@ -46,12 +83,17 @@ __device__ __forceinline__ float3 load_pos(const float* __restrict__ pos, const 
   return p;
 }
 
-template <bool PBC>
+template <int PBC>
 __global__ void rg_keys_kernel(const float* __restrict__ pos, int64_t N, RgDev g, uint32_t* __restrict__ keys,
-                               int32_t* __restrict__ idx, const RgPbc pb) {
+                               int32_t* __restrict__ idx, const typename RgArg<PBC>::type pb) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const float3 p = load_pos<PBC>(pos, i, g, pb);
+  float3 p = load_pos<PBC>(pos, i, g, pb);
+  if constexpr (PBC == kCell) {  // the grid coordinate q_a = s_a(w) h_a
+    float s[3];
+    cell_s(pb, p, s);
+    p = make_float3(__fmul_rn(s[0], pb.hgt[0]), __fmul_rn(s[1], pb.hgt[1]), __fmul_rn(s[2], pb.hgt[2]));
+  }
   int cx = cell_of(p.x, g.lo[0], g.inv[0], g.n[0]);
   int cy = cell_of(p.y, g.lo[1], g.inv[1], g.n[1]);
   int cz = cell_of(p.z, g.lo[2], g.inv[2], g.n[2]);
@@ -60,15 +102,16 @@ __global__ void rg_keys_kernel(const float* __restrict__ pos, int64_t N, RgDev g
 }
 
 // sorted positions (x,y,z,0; PBC: wrapped), cell table [begin,end) per Morton code, list of non-empty cells
-template <bool PBC>
+template <int PBC>
 __global__ void rg_cells_kernel(const float* __restrict__ pos, int64_t N, const uint32_t* __restrict__ skeys,
                                 const int32_t* __restrict__ perm, float4* __restrict__ spos,
                                 int32_t* __restrict__ cbegin, int32_t* __restrict__ cend,
-                                int32_t* __restrict__ heads, int32_t* __restrict__ nheads, const RgDev g, const RgPbc pb) {
+                                int32_t* __restrict__ heads, int32_t* __restrict__ nheads, const RgDev g,
+                                const typename RgArg<PBC>::type pb) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
   const int32_t o = perm[i];
-  if constexpr (PBC) {
+  if constexpr (PBC != kOpen) {
     const float3 p = load_pos<PBC>(pos, o, g, pb);
     spos[i] = make_float4(p.x, p.y, p.z, 0.0f);
   } else {
@@ -85,14 +128,16 @@ __global__ void rg_cells_kernel(const float* __restrict__ pos, int64_t N, const 
 // One wave per non-empty cell.  FILL=false: deg[i] = #neighbours.  FILL=true: src[rowptr[i]..] = ids.
 // PBC: neighbour cells modulo n on periodic axes (duplicates dropped: n <= 2 names a cell more than once) and the one-step
 // minimum image in the edge test -- skipped by the cells whose 3x3x3 neighbourhood stays inside the box (wave-uniform).
-template <bool FILL, bool PBC>
+// kCell: the same on the grid of q (every direction periodic), with the rint minimum image of the cell in the edge test.
+template <bool FILL, int PBC>
 __global__ __launch_bounds__(64) void rg_scan_kernel(const float4* __restrict__ spos, const uint32_t* __restrict__ skeys,
                                                      const int32_t* __restrict__ cbegin,
                                                      const int32_t* __restrict__ cend,
                                                      const int32_t* __restrict__ heads,
                                                      const int32_t* __restrict__ nheads_p, RgDev g,
                                                      int32_t* __restrict__ deg, const int32_t* __restrict__ rowptr,
-                                                     int32_t* __restrict__ src, const RgPbc pb) {
+                                                     int32_t* __restrict__ src,
+                                                     const typename RgArg<PBC>::type pb) {
   __shared__ float4 cand[kCandCap];   // x,y,z, id (bit pattern)
   __shared__ int rb[28], re[28], pre[29];
   const int lane = threadIdx.x;
@@ -108,7 +153,11 @@ __global__ __launch_bounds__(64) void rg_scan_kernel(const float4* __restrict__ 
     if (lane < 27) {
       int dx = lane % 3 - 1, dy = (lane / 3) % 3 - 1, dz = lane / 9 - 1;
       int x = cx + dx, y = cy + dy, z = cz + dz;
-      if constexpr (PBC) {
+      if constexpr (PBC == kCell) {
+        x = x < 0 ? x + g.n[0] : (x >= g.n[0] ? x - g.n[0] : x);
+        y = y < 0 ? y + g.n[1] : (y >= g.n[1] ? y - g.n[1] : y);
+        z = z < 0 ? z + g.n[2] : (z >= g.n[2] ? z - g.n[2] : z);
+      } else if constexpr (PBC == kBox) {
         if (pb.periodic & 1) x = x < 0 ? x + g.n[0] : (x >= g.n[0] ? x - g.n[0] : x);
         if (pb.periodic & 2) y = y < 0 ? y + g.n[1] : (y >= g.n[1] ? y - g.n[1] : y);
         if (pb.periodic & 4) z = z < 0 ? z + g.n[2] : (z >= g.n[2] ? z - g.n[2] : z);
@@ -121,14 +170,17 @@ __global__ __launch_bounds__(64) void rg_scan_kernel(const float4* __restrict__ 
       }
     }
     bool shift = false;  // some candidate may sit across a periodic face
-    if constexpr (PBC) {
+    if constexpr (PBC != kOpen) {
       bool dup = false;  // the same cell under a lower offset (n <= 2 on a periodic axis)
       for (int m = 0; m < 27; ++m) dup |= (__shfl(ncode, m) == ncode) && (m < lane);
       if (dup) ncode = 0xFFFFFFFFu;
       // n >= 5 and a cell away from both faces: |x_i - x_j| < 2 cell widths + rounding < L / 2, the shift never fires
       const int c[3] = {cx, cy, cz};
-      for (int a = 0; a < 3; ++a)
-        if ((pb.periodic >> a) & 1) shift |= g.n[a] < 5 || c[a] < 1 || c[a] > g.n[a] - 2;
+      for (int a = 0; a < 3; ++a) {
+        bool on = true;
+        if constexpr (PBC == kBox) on = (pb.periodic >> a) & 1;
+        if (on) shift |= g.n[a] < 5 || c[a] < 1 || c[a] > g.n[a] - 2;
+      }
     }
     int rank = 0;
     for (int m = 0; m < 27; ++m) {
@@ -174,7 +226,9 @@ __global__ __launch_bounds__(64) void rg_scan_kernel(const float4* __restrict__ 
             const float4 pc = cand[c];
             id = __float_as_int(pc.w);
             float dx = __fsub_rn(pi.x, pc.x), dy = __fsub_rn(pi.y, pc.y), dz = __fsub_rn(pi.z, pc.z);
-            if (PBC && shift) {
+            if constexpr (PBC == kCell) {
+              if (shift) min_image(pb.c, dx, dy, dz);
+            } else if (PBC == kBox && shift) {
               dx = dx > pb.hL[0] ? __fsub_rn(dx, pb.L[0]) : (dx < -pb.hL[0] ? __fadd_rn(dx, pb.L[0]) : dx);
               dy = dy > pb.hL[1] ? __fsub_rn(dy, pb.L[1]) : (dy < -pb.hL[1] ? __fadd_rn(dy, pb.L[1]) : dy);
               dz = dz > pb.hL[2] ? __fsub_rn(dz, pb.L[2]) : (dz < -pb.hL[2] ? __fadd_rn(dz, pb.L[2]) : dz);
@@ -269,9 +323,21 @@ static int rg_pbc(const e3_rg_params* p, int periodic, RgPbc* pb) {
   return E3_OK;
 }
 
-template <bool PBC>
-static int rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, const RgPbc& pb, int32_t* perm,
-                         float* sorted_pos4, int32_t* rowptr, void* workspace, int64_t workspace_bytes, void* stream) {
+// host: the device cell of a *_cell entry (validated: a derivable cell, finite origin, 2 r < every height, and prm = the grid
+// of e3_rg_grid over lo = 0, hi = the heights)
+static int rg_cell(const e3_rg_params* p, const float* cell, const float* origin, RgCell* rc) {
+  if (!p || !cell || !origin || !make_cell(cell, p->r, &rc->c, rc->hgt)) return E3_ERR_INVALID_ARG;
+  for (int a = 0; a < 3; ++a) {
+    if (!(fabsf(origin[a]) < 3.0e38f) || p->lo[a] != 0.0f || p->hi[a] != rc->hgt[a]) return E3_ERR_INVALID_ARG;
+    rc->o[a] = origin[a];
+  }
+  return E3_OK;
+}
+
+template <int PBC>
+static int rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, const typename RgArg<PBC>::type& pb,
+                         int32_t* perm, float* sorted_pos4, int32_t* rowptr, void* workspace, int64_t workspace_bytes,
+                         void* stream) {
   if (!p || N < 0 || !rowptr || p->bits < 1 || p->bits > 8) return E3_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (N == 0) { E3_HIP_CHECK(hipMemsetAsync(rowptr, 0, 4, s)); return E3_OK; }
@@ -308,9 +374,9 @@ static int rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, con
   return E3_OK;
 }
 
-template <bool PBC>
-static int rg_fill(int64_t N, const e3_rg_params* p, const RgPbc& pb, const float* sorted_pos4, const int32_t* rowptr,
-                   int32_t* src, void* workspace, int64_t workspace_bytes, void* stream) {
+template <int PBC>
+static int rg_fill(int64_t N, const e3_rg_params* p, const typename RgArg<PBC>::type& pb, const float* sorted_pos4,
+                   const int32_t* rowptr, int32_t* src, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!p || N < 0 || p->bits < 1 || p->bits > 8) return E3_ERR_INVALID_ARG;
   if (N == 0) return E3_OK;
   if (!sorted_pos4 || !rowptr || !workspace) return E3_ERR_INVALID_ARG;
@@ -332,12 +398,12 @@ extern "C" {
 
 int e3_rg_sort_count(const float* pos, int64_t N, const e3_rg_params* p, int32_t* perm, float* sorted_pos4,
                      int32_t* rowptr, void* workspace, int64_t workspace_bytes, void* stream) {
-  return rg_sort_count<false>(pos, N, p, RgPbc{}, perm, sorted_pos4, rowptr, workspace, workspace_bytes, stream);
+  return rg_sort_count<kOpen>(pos, N, p, RgPbc{}, perm, sorted_pos4, rowptr, workspace, workspace_bytes, stream);
 }
 
 int e3_rg_fill(int64_t N, const e3_rg_params* p, const float* sorted_pos4, const int32_t* rowptr, int32_t* src,
                void* workspace, int64_t workspace_bytes, void* stream) {
-  return rg_fill<false>(N, p, RgPbc{}, sorted_pos4, rowptr, src, workspace, workspace_bytes, stream);
+  return rg_fill<kOpen>(N, p, RgPbc{}, sorted_pos4, rowptr, src, workspace, workspace_bytes, stream);
 }
 
 int e3_rg_sort_count_pbc(const float* pos, int64_t N, const e3_rg_params* p, int32_t periodic, int32_t* perm,
@@ -345,7 +411,7 @@ int e3_rg_sort_count_pbc(const float* pos, int64_t N, const e3_rg_params* p, int
   RgPbc pb;
   const int st = rg_pbc(p, periodic, &pb);
   if (st != E3_OK) return st;
-  return rg_sort_count<true>(pos, N, p, pb, perm, sorted_pos4, rowptr, workspace, workspace_bytes, stream);
+  return rg_sort_count<kBox>(pos, N, p, pb, perm, sorted_pos4, rowptr, workspace, workspace_bytes, stream);
 }
 
 int e3_rg_fill_pbc(int64_t N, const e3_rg_params* p, int32_t periodic, const float* sorted_pos4, const int32_t* rowptr,
@@ -353,7 +419,24 @@ int e3_rg_fill_pbc(int64_t N, const e3_rg_params* p, int32_t periodic, const flo
   RgPbc pb;
   const int st = rg_pbc(p, periodic, &pb);
   if (st != E3_OK) return st;
-  return rg_fill<true>(N, p, pb, sorted_pos4, rowptr, src, workspace, workspace_bytes, stream);
+  return rg_fill<kBox>(N, p, pb, sorted_pos4, rowptr, src, workspace, workspace_bytes, stream);
+}
+
+int e3_rg_sort_count_cell(const float* pos, int64_t N, const e3_rg_params* p, const float cell[9], const float origin[3],
+                          int32_t* perm, float* sorted_pos4, int32_t* rowptr, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+  RgCell rc;
+  const int st = rg_cell(p, cell, origin, &rc);
+  if (st != E3_OK) return st;
+  return rg_sort_count<kCell>(pos, N, p, rc, perm, sorted_pos4, rowptr, workspace, workspace_bytes, stream);
+}
+
+int e3_rg_fill_cell(int64_t N, const e3_rg_params* p, const float cell[9], const float origin[3], const float* sorted_pos4,
+                    const int32_t* rowptr, int32_t* src, void* workspace, int64_t workspace_bytes, void* stream) {
+  RgCell rc;
+  const int st = rg_cell(p, cell, origin, &rc);
+  if (st != E3_OK) return st;
+  return rg_fill<kCell>(N, p, rc, sorted_pos4, rowptr, src, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

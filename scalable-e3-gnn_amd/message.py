@@ -193,7 +193,9 @@ class FusedMessage:
             args = (hd, h.data_ptr(), h.stride(0), N, g.pos4.data_ptr(), src.data_ptr(), dst.data_ptr(), E,
                     packed.data_ptr(), sc, premix.data_ptr(), out.data_ptr(), out.stride(0), code,
                     0 if cont is None else 1, int(self.tiles_per_block))
-            if g.box is not None:  # periodic box: harmonics of the minimum-image edge vectors
+            if g.cell is not None:  # general cell: harmonics of the minimum image by lattice vectors
+                _lib.check(lib.e3_msg_forward_cell(*args, g.cell_arg, stream), "e3_msg_forward_cell")
+            elif g.box is not None:  # periodic box: harmonics of the minimum-image edge vectors
                 _lib.check(lib.e3_msg_forward_pbc(*args, g.box_arg, stream), "e3_msg_forward_pbc")
             else:
                 _lib.check(lib.e3_msg_forward(*args, stream), "e3_msg_forward")

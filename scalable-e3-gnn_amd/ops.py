@@ -35,11 +35,19 @@ def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True,
     outs = (Y.data_ptr() if Y is not None else None, d.data_ptr() if d is not None else None,
             A.data_ptr() if A is not None else None, _stream(pos4))
     with torch.cuda.device(dev):
-        if strain is not None:  # [S,3,3] contiguous fp32, structure [N] int32 | None (checked by _strain_args)
+        if strain is not None and g.cell is not None:  # general cell: the cell's minimum image, then the strain
+            _lib.check(_lib.load().e3_edge_geometry_strained_cell(
+                pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, g.cell_arg, strain.data_ptr(),
+                structure.data_ptr() if structure is not None else None, strain.shape[0], *outs),
+                "e3_edge_geometry_strained_cell")
+        elif strain is not None:  # [S,3,3] contiguous fp32, structure [N] int32 | None (checked by _strain_args)
             _lib.check(_lib.load().e3_edge_geometry_strained(
                 pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, g.box_arg, strain.data_ptr(),
                 structure.data_ptr() if structure is not None else None, strain.shape[0], *outs),
                 "e3_edge_geometry_strained")
+        elif g.cell is not None:  # general cell: minimum-image edge vectors by lattice vectors
+            _lib.check(getattr(_lib.load(), fn + "_cell")(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
+                                                          g.cell_arg, *outs), fn + "_cell")
         elif g.box is not None:  # periodic box: minimum-image edge vectors
             _lib.check(getattr(_lib.load(), fn + "_pbc")(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
                                                          g.box_arg, *outs), fn + "_pbc")
@@ -100,10 +108,16 @@ class _EdgeGeometryFn(torch.autograd.Function):
                 gstrain = torch.empty_like(strain)
                 ws = torch.empty(max(1, lib.e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
                                  device=pos4.device)
-                _lib.check(lib.e3_edge_geometry_backward_strained(
-                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.box_arg, strain.data_ptr(),
+                name = "e3_edge_geometry_backward_strained" + ("_cell" if g.cell is not None else "")
+                _lib.check(getattr(lib, name)(
+                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax,
+                    g.cell_arg if g.cell is not None else g.box_arg, strain.data_ptr(),
                     p(ctx.structure), strain.shape[0], p(gY), p(gd), p(gA), gpos.data_ptr(), gstrain.data_ptr(),
-                    ws.data_ptr(), ws.numel(), _stream(pos4)), "e3_edge_geometry_backward_strained")
+                    ws.data_ptr(), ws.numel(), _stream(pos4)), name)
+            elif g.cell is not None:
+                _lib.check(lib.e3_edge_geometry_backward_cell(
+                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.cell_arg, p(gY), p(gd), p(gA),
+                    gpos.data_ptr(), _stream(pos4)), "e3_edge_geometry_backward_cell")
             elif g.box is not None:
                 _lib.check(lib.e3_edge_geometry_backward_pbc(
                     pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.box_arg, p(gY), p(gd), p(gA),
@@ -122,7 +136,8 @@ def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int
 
     ``pos`` [N,3] (graph order, i.e. ``original_pos[g.perm]``): when given and it requires grad, the three outputs are
     differentiable w.r.t. it (forces = -dE/dpos); otherwise the graph's own ``pos4`` is used.  A periodic graph
-    (``g.box``) takes the minimum image of every edge vector, so ``pos`` may be the unwrapped coordinates.
+    (``g.box``, or a general cell ``g.cell``) takes the minimum image of every edge vector, so ``pos`` may be the
+    unwrapped coordinates (moved by whole periods / lattice vectors).
 
     ``strain`` [S,3,3] (or [3,3]: one structure), fp32 on the device, and ``structure`` [N] integer structure id of every
     row (graph order; None = every row is structure 0): every edge vector r of structure s (the structure of its dst row)

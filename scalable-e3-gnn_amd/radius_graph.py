@@ -7,6 +7,10 @@ explicitly rounded fp32, and the result is CSR-by-dst with ascending ``src``.
 Periodic boxes (``periodic=``, per axis): coordinates are wrapped into ``[lo, hi)`` and the edge test takes the minimum
 image (definitions in include/e3gnn.h, ``e3_rg_sort_count_pbc``); the graph then carries ``box`` and every edge stage
 downstream (geometry, message kernels, forces) uses the minimum-image edge vector.
+
+General (triclinic) cells (``cell=``, rows = lattice vectors, periodic on all three): coordinates are wrapped into the cell
+and the grid runs over the fractional coordinates scaled by the perpendicular heights (``e3_rg_sort_count_cell``); the
+graph then carries ``cell`` / ``origin`` / ``volume`` instead of ``box`` and every edge stage selects its ``*_cell`` entry.
 """
 from __future__ import annotations
 
@@ -31,7 +35,15 @@ class RadiusGraph:
     src: torch.Tensor       # [E] int32   ascending inside each row
     num_edges: int
     grid: tuple
-    box: tuple | None = None  # (L_x, L_y, L_z), 0.0 on an open axis; None = open box
+    box: tuple | None = None  # (L_x, L_y, L_z), 0.0 on an open axis; None = open box (and on a cell graph)
+    cell: tuple | None = None    # 9 fp32-exact floats, row-major, rows = lattice vectors; None = no general cell
+    origin: tuple | None = None  # 3 fp32-exact floats: the corner of the cell (None without a cell)
+    volume: float | None = None  # |det cell| (fp32-exact; None without a cell)
+
+    @property
+    def cell_arg(self):
+        """The ``cell`` as the ``float[9]`` argument of the ``*_cell`` entries (None without a cell)."""
+        return None if self.cell is None else _lib.Float9(*self.cell)
 
     @property
     def box_arg(self):
@@ -85,17 +97,127 @@ def periodic_mask(periodic, r, lo, hi) -> int:
     return mask
 
 
-def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False) -> RadiusGraph:
-    """pos [N,3] fp32 on a ROCm device.  ``lo``/``hi``: bounding box (computed from pos when omitted).
+def cell_from_lengths_angles(a, b, c, alpha, beta, gamma):
+    """The cell (3 rows = lattice vectors, lower-triangular) of lengths ``a, b, c`` and angles ``alpha`` (between b and
+    c), ``beta`` (a, c), ``gamma`` (a, b) in degrees: a_0 along x, a_1 in the xy plane, a_2 with a positive z.
+    ``ValueError`` when the angles do not span a volume."""
+    import math
+    try:
+        a, b, c, alpha, beta, gamma = (float(v) for v in (a, b, c, alpha, beta, gamma))
+    except (TypeError, ValueError):
+        raise ValueError(f"lengths and angles must be numbers, got {a, b, c} and {alpha, beta, gamma}") from None
+    # a residue of cos() below 5e-16 is cut off, which makes the cosines of 60, 90 and 120 degrees exactly 0 and +-1/2;
+    # every other angle moves by at most that much
+    ca, cb, cg = (round(math.cos(math.radians(v)), 15) for v in (alpha, beta, gamma))
+    sg = math.sqrt(max(0.0, 1.0 - cg * cg))
+    if not (min(a, b, c) > 0.0) or not sg > 0.0:
+        raise ValueError(f"lengths must be positive and gamma inside (0, 180), got {a, b, c} and gamma = {gamma}")
+    cx = cb
+    cy = (ca - cb * cg) / sg
+    cz2 = 1.0 - cx * cx - cy * cy
+    if not cz2 > 0.0:
+        raise ValueError(f"angles {alpha, beta, gamma} do not span a cell (the three vectors would be coplanar)")
+    return [[a, 0.0, 0.0], [b * cg, b * sg, 0.0], [c * cx, c * cy, c * math.sqrt(cz2)]]
 
-    ``periodic``: bool or 3 bools; periodic axes wrap at ``[lo, hi)`` (then ``lo`` / ``hi`` are required and
-    ``2 r < hi - lo``).  Positions may lie outside the box on those axes; ``pos4`` holds them wrapped."""
-    mask = periodic_mask(periodic, r, lo, hi)
+
+def cell_params(cell, origin=None):
+    """``cell`` (3x3 nested sequence or CPU tensor; rows = lattice vectors) and ``origin`` as fp32-exact floats, with what
+    the library derives from them -> (cell9, origin3, heights3, volume).  ``ValueError`` for a wrong shape or a cell that is
+    singular or not finite."""
+    if isinstance(cell, torch.Tensor):
+        if cell.is_cuda:
+            raise ValueError("cell must be a nested sequence or a CPU tensor (it is a host argument of the kernels)")
+        cell = cell.detach().tolist()
+    rows = [list(row) if hasattr(row, "__len__") else None for row in cell] if hasattr(cell, "__len__") else None
+    if rows is None or len(rows) != 3 or any(row is None or len(row) != 3 for row in rows):
+        raise ValueError("cell must be 3 x 3: one lattice vector per row")
+    if isinstance(origin, torch.Tensor):
+        origin = origin.detach().cpu().tolist()
+    origin = [0.0, 0.0, 0.0] if origin is None else list(origin)
+    if len(origin) != 3:
+        raise ValueError("origin must have 3 entries")
+    c9 = _lib.Float9(*[float(v) for row in rows for v in row])
+    o3 = _lib.Float3(*[float(v) for v in origin])
+    ginv, hgt, vol = _lib.Float9(), _lib.Float3(), ctypes.c_float()
+    if _lib.load().e3_cell_derive(c9, ginv, hgt, ctypes.byref(vol)) != _lib.E3_OK or \
+            not all(abs(v) < 3.0e38 for v in o3):
+        raise ValueError(f"cell {[list(row) for row in rows]} is singular or not finite (or the origin is not finite)")
+    return tuple(c9), tuple(o3), tuple(hgt), vol.value
+
+
+def cell_check_cutoff(heights, r):
+    """``ValueError`` unless ``0 < 2 r < min height`` in fp32 (the unique-image condition of the ``*_cell`` entries)."""
+    r32 = ctypes.c_float(r).value
+    if not r32 > 0.0 or not all(ctypes.c_float(2.0 * r32).value < h for h in heights):
+        raise ValueError(f"cell: need 0 < 2 r < the smallest perpendicular height, got r = {r}, heights = "
+                         f"{tuple(heights)}")
+
+
+def _check_pos(pos):
     if not pos.is_cuda:
         raise RuntimeError("radius_graph runs on ROCm tensors only; there is no CPU path")
     if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
         raise RuntimeError(f"pos must be [N,3] float32, got {tuple(pos.shape)} {pos.dtype}")
-    pos = pos.contiguous()
+    return pos.contiguous()
+
+
+def _edge_count(rowptr, N) -> int:
+    """E = rowptr[N], read together with the smallest degree: the count / scan run in int32 (indices are int32 end to end),
+    so a graph with >= 2^31 edges wraps the running sum, which shows as a negative or decreasing rowptr."""
+    if N > 0:
+        E, mindeg = torch.stack([rowptr[-1], (rowptr[1:] - rowptr[:-1]).min()]).tolist()
+    else:
+        E, mindeg = int(rowptr[-1].item()), 0
+    if E < 0 or mindeg < 0:
+        raise RuntimeError("radius_graph: the edge count does not fit int32 (>= 2^31 edges); shard the cloud "
+                           "(sharding.SlabHalo) or reduce the cutoff")
+    return int(E)
+
+
+def _radius_graph_cell(pos, r, cell, origin) -> RadiusGraph:
+    c9, o3, hgt, vol = cell_params(cell, origin)
+    cell_check_cutoff(hgt, r)
+    pos = _check_pos(pos)
+    N, dev = pos.shape[0], pos.device
+    lib = _lib.load()
+    p = grid_params([0.0, 0.0, 0.0], hgt, r)  # the open grid of q = s * heights in [0, h)
+    ca, oa = _lib.Float9(*c9), _lib.Float3(*o3)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        wbytes = lib.e3_rg_workspace_bytes(N, ctypes.byref(p))
+        if wbytes < 0:
+            raise RuntimeError("e3_rg_workspace_bytes: invalid arguments")
+        ws = torch.empty(max(int(wbytes), 16), dtype=torch.uint8, device=dev)
+        perm = torch.empty(N, dtype=torch.int32, device=dev)
+        pos4 = torch.empty((N, 4), dtype=torch.float32, device=dev)
+        rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        _lib.check(lib.e3_rg_sort_count_cell(pos.data_ptr(), N, ctypes.byref(p), ca, oa, perm.data_ptr(), pos4.data_ptr(),
+                                             rowptr.data_ptr(), ws.data_ptr(), wbytes, stream), "e3_rg_sort_count_cell")
+        E = _edge_count(rowptr, N)
+        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+        _lib.check(lib.e3_rg_fill_cell(N, ctypes.byref(p), ca, oa, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
+                                       ws.data_ptr(), wbytes, stream), "e3_rg_fill_cell")
+    return RadiusGraph(perm, pos4, rowptr, src[:E], E, (tuple(p.n), p.bits), None, c9, o3, vol)
+
+
+def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, cell=None, origin=None) -> RadiusGraph:
+    """pos [N,3] fp32 on a ROCm device.  ``lo``/``hi``: bounding box (computed from pos when omitted).
+
+    ``periodic``: bool or 3 bools; periodic axes wrap at ``[lo, hi)`` (then ``lo`` / ``hi`` are required and
+    ``2 r < hi - lo``).  Positions may lie outside the box on those axes; ``pos4`` holds them wrapped.
+
+    ``cell`` (3x3 nested sequence or CPU tensor, rows = lattice vectors, the ASE convention) with ``origin`` (default
+    (0,0,0)): a general cell, periodic on all three directions; needs ``2 r <`` every perpendicular height and excludes
+    ``lo`` / ``hi`` / ``periodic`` (``ValueError``).  The graph carries ``cell`` / ``origin`` / ``volume``; ``box`` stays
+    None."""
+    if cell is not None:
+        if lo is not None or hi is not None or not (periodic is False or periodic is None):
+            raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
+        return _radius_graph_cell(pos, r, cell, origin)
+    if origin is not None:
+        raise ValueError("origin= is the corner of a cell=; it needs cell=")
+    mask = periodic_mask(periodic, r, lo, hi)
+    pos = _check_pos(pos)
     N = pos.shape[0]
     if lo is None or hi is None:
         lo = pos.min(0).values.tolist() if N else [0.0, 0.0, 0.0]
@@ -121,16 +243,7 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False) 
         else:
             _lib.check(lib.e3_rg_sort_count(pos.data_ptr(), N, ctypes.byref(p), perm.data_ptr(), pos4.data_ptr(),
                                             rowptr.data_ptr(), ws.data_ptr(), wbytes, stream), "e3_rg_sort_count")
-        # the count / scan run in int32 (indices are int32 end to end): a graph with >= 2^31 edges wraps the running sum,
-        # which shows as a negative or decreasing rowptr -- checked here with the same host read that fetches E
-        if N > 0:
-            E, mindeg = torch.stack([rowptr[-1], (rowptr[1:] - rowptr[:-1]).min()]).tolist()
-        else:
-            E, mindeg = int(rowptr[-1].item()), 0
-        if E < 0 or mindeg < 0:
-            raise RuntimeError("radius_graph: the edge count does not fit int32 (>= 2^31 edges); shard the cloud "
-                               "(sharding.SlabHalo) or reduce the cutoff")
-        E = int(E)
+        E = _edge_count(rowptr, N)
         src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
         if mask:
             _lib.check(lib.e3_rg_fill_pbc(N, ctypes.byref(p), mask, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),

@@ -87,7 +87,7 @@ class SEGNNLayer(nn.Module):
     def forward(self, h, g: RadiusGraph, Y, d, A, h_scale=None, halo=None, split=None):
         """-> (h_next, operand scale of h_next | None).  ``halo`` / ``split`` (sharding.Halo / SplitGraph): the layer
         refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges."""
-        if (halo is not None or split is not None) and g.box is not None:
+        if (halo is not None or split is not None) and (g.box is not None or g.cell is not None):
             raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
                                       "ghost images of GridHalo(..., periodic=...)")
         inference = not (torch.is_grad_enabled() and _needs_grad(self, h))
@@ -205,7 +205,7 @@ class SEGNN(nn.Module):
         refreshed from their owners before every message-passing layer; only owned rows of the result
         are meaningful.  ``split`` (``halo.split_graph(g)``): edges into ghost rows dropped and the rest split into
         interior / boundary lists so that the refresh overlaps the interior edges."""
-        if (halo is not None or split is not None) and g.box is not None:
+        if (halo is not None or split is not None) and (g.box is not None or g.cell is not None):
             raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
                                       "ghost images of GridHalo(..., periodic=...)")
         if split is not None:
