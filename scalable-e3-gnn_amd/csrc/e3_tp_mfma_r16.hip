@@ -189,6 +189,51 @@ constexpr int r16_max(std::initializer_list<int> v) {
   for (int x : v) m = x > m ? x : m;
   return m;
 }
+constexpr int kR16YTile = 160;  // per-wave Y tile after the chunk buffer (dwords): 16 rows x 9, padded
+
+// ---- pieces shared by tp_fwd_mfma_r16_kernel and tp_update_pair_r16_kernel ----
+
+// Every path (L1, l2, l3) of one staged chunk of degree L1 into the accumulators of its output degree (Slots::nt(l3)
+// 32-channel tiles = twice as many 16-channel MFMA tiles).  `ch`: the chunk's plan entry; `gw`: the k group whose weights
+// this lane reads (its own when `live`); `j` = lane & 15.
+template <class Slots, int L1, bool IO16, int T0, int T1, int T2>
+__device__ __forceinline__ void run_paths(const float (&x)[8][2 * L1 + 1], const bool live, const int gw, const int j,
+                                          const FChunk& ch, const uint4* __restrict__ whi_base,
+                                          const uint4* __restrict__ wlo_base, const int (&cBfoff)[3], const int (&cMpad)[3],
+                                          const float (&y)[9], f32x4 (&a0)[T0][1], f32x4 (&a1)[T1][3], f32x4 (&a2)[T2][5]) {
+  auto path = [&](auto l2tag, auto l3tag, auto& acc) {
+    constexpr int L2 = decltype(l2tag)::value, L3 = decltype(l3tag)::value;
+    if constexpr (Slots::valid(L1, L2, L3)) {
+      static_assert(CG<L1, L2, L3>::valid, "path bookkeeping");
+      const size_t o = (size_t)(cBfoff[L3] >> 3) + (size_t)(2 * ch.wblk[L2][L3] + gw) * cMpad[L3] + j;
+      run16<L1, L2, L3, 2 * Slots::nt(L3), IO16>(x, live, whi_base + o, wlo_base + o, y, acc);
+    }
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+  path(I0{}, I0{}, a0); path(I1{}, I0{}, a0); path(I2{}, I0{}, a0);
+  path(I0{}, I1{}, a1); path(I1{}, I1{}, a1); path(I2{}, I1{}, a1);
+  path(I0{}, I2{}, a2); path(I1{}, I2{}, a2); path(I2{}, I2{}, a2);
+}
+
+// this lane's 8 channels of a 32-channel tile: q = 4 * (16-tile) + r  ->  channel 16 * (q >> 2) + 4 * g + (q & 3)
+__device__ __forceinline__ int chan_of(const int g, const int q) { return 16 * (q >> 2) + 4 * g + (q & 3); }
+
+// the vector store of an output tile needs 16-byte aligned rows of the output and of the residual
+__device__ __forceinline__ bool out_vec_ok(const void* outv, const int64_t ldo, const SegArgs& segs) {
+  return !(ldo & 3) && ((reinterpret_cast<uintptr_t>(outv) & 15) == 0) &&
+         (!segs.residual || (!(segs.ldr & 3) && (reinterpret_cast<uintptr_t>(segs.residual) & 15) == 0));
+}
+
+// the wave's max over the finite values only, filtered per element in the store loops (as e3_pow2_scale does), into segs.amax
+__device__ __forceinline__ void amax_finish(const SegArgs& segs, float amax, const int lane) {
+  if (segs.amax) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (lane == 0 && amax > 0.f) atomicMax(segs.amax, __builtin_bit_cast(uint32_t, amax));
+  }
+}
 
 template <int LSH, int NT0, int NT1, int NT2, bool GATE, int MODE, bool SCAT, int... L1S>
 __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd_mfma_r16_kernel(SegArgs segs, const float* __restrict__ in2, int64_t ld2,
@@ -217,7 +262,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
   float* nrm = lds;
   int* ocl = reinterpret_cast<int*>(nrm + ((Dout + 4 + 15) & ~15));
   float* wbase = reinterpret_cast<float*>(ocl + ((ntab + 15) & ~15));
-  float* cbuf = wbase + (size_t)wave * (CHUNK + 160);
+  float* cbuf = wbase + (size_t)wave * (CHUNK + kR16YTile);
   float* ybuf = cbuf + CHUNK;
   // operand scales (powers of two): the weights were packed as w * sw, the input features are multiplied by xs on the way
   // into the B operands; both leave through the per-column norm table
@@ -374,16 +419,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
       const float* xrl = live ? xr : cbuf;     // and its x reads inside the buffer
       float x[8][2 * L1 + 1];
       load_x16<L1, IO16>(xrl, live ? g : 0, xs, x);
-#define E3_RUN(L2v, L3v, ACC, NTv)                                                                             \
-  if constexpr (Slots::valid(L1, L2v, L3v)) {                                                                  \
-    static_assert(CG<L1, L2v, L3v>::valid, "path bookkeeping");                                                \
-    const size_t o = (size_t)(cBfoff[L3v] >> 3) + (size_t)(2 * ch.wblk[L2v][L3v] + gw) * cMpad[L3v] + j;       \
-    run16<L1, L2v, L3v, 2 * NTv, IO16>(x, live, whi_base + o, wlo_base + o, y, ACC);                            \
-  }
-      E3_RUN(0, 0, a0, NT0) E3_RUN(1, 0, a0, NT0) E3_RUN(2, 0, a0, NT0)
-      E3_RUN(0, 1, a1, NT1) E3_RUN(1, 1, a1, NT1) E3_RUN(2, 1, a1, NT1)
-      E3_RUN(0, 2, a2, NT2) E3_RUN(1, 2, a2, NT2) E3_RUN(2, 2, a2, NT2)
-#undef E3_RUN
+      run_paths<Slots, L1, IO16>(x, live, gw, j, ch, whi_base, wlo_base, cBfoff, cMpad, y, a0, a1, a2);
       wave_sync_lds();
       if (ci + 1 < nchunks) stage(ci + 1, cbuf);
       ++ci;
@@ -394,10 +430,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
     wait_vm0();
     wave_sync_lds();
     float* ot = cbuf;
-    // this lane's 8 channels of a 32-channel tile: q = 4 * (16-tile) + r  ->  channel 16 * (q >> 2) + 4 * g + (q & 3)
-    auto chan_of = [&](int q) { return 16 * (q >> 2) + 4 * g + (q & 3); };
-    const bool out_vec = !(ldo & 3) && ((reinterpret_cast<uintptr_t>(outv) & 15) == 0) &&
-                         (!segs.residual || (!(segs.ldr & 3) && (reinterpret_cast<uintptr_t>(segs.residual) & 15) == 0));
+    const bool out_vec = out_vec_ok(outv, ldo, segs);
     auto emit = [&](auto dtag, auto val, auto col, auto ncol, const int width, const bool affine) {
       constexpr int D = decltype(dtag)::value;
       constexpr int TS = 32 * D + 4;
@@ -407,7 +440,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
 #pragma unroll
       for (int q = 0; q < 8; ++q)
 #pragma unroll
-        for (int c = 0; c < D; ++c) ot[j * TS + D * chan_of(q) + c] = val(q, c);
+        for (int c = 0; c < D; ++c) ot[j * TS + D * chan_of(g, q) + c] = val(q, c);
       wave_sync_lds();
       if constexpr (SCAT) {
         for (int cb = 0; cb < 32 * D; cb += 64) {
@@ -525,7 +558,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
         constexpr int W = Hh - 32 * T32 < 32 ? Hh - 32 * T32 : 32;   // channels of this tile that exist
         using B0 = std::integral_constant<int, 0>;
         emit(I1{}, [&](int q, int) {
-               const float s = a0_of(B0{}, ttag, q) * nrm0[32 * T32 + chan_of(q)];
+               const float s = a0_of(B0{}, ttag, q) * nrm0[32 * T32 + chan_of(g, q)];
                return s * sigmoid_(s);
              },
              [&](int lc) { return 32 * T32 + lc; }, [&](int) { return -1; }, W, true);
@@ -533,7 +566,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
           using B1 = std::integral_constant<int, 1>;
           float gq[8];
 #pragma unroll
-          for (int q = 0; q < 8; ++q) gq[q] = sigmoid_(a0_of(B1{}, ttag, q) * nrm0[Hh + 32 * T32 + chan_of(q)]);
+          for (int q = 0; q < 8; ++q) gq[q] = sigmoid_(a0_of(B1{}, ttag, q) * nrm0[Hh + 32 * T32 + chan_of(g, q)]);
           const int nb = ocl[cOoff[1]] + 96 * T32;
           emit(I3{}, [&](int q, int c) { return gq[q] * a1[2 * T32 + (q >> 2)][c][q & 3]; },
                [&](int lc) { return Hh + 96 * T32 + lc; }, [&](int lc) { return nb + lc; }, 3 * W, true);
@@ -542,7 +575,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
           using B2 = std::integral_constant<int, (NT1 > 0) ? 2 : 1>;
           float gq[8];
 #pragma unroll
-          for (int q = 0; q < 8; ++q) gq[q] = sigmoid_(a0_of(B2{}, ttag, q) * nrm0[B2::value * Hh + 32 * T32 + chan_of(q)]);
+          for (int q = 0; q < 8; ++q) gq[q] = sigmoid_(a0_of(B2{}, ttag, q) * nrm0[B2::value * Hh + 32 * T32 + chan_of(g, q)]);
           const int nb = ocl[cOoff[2]] + 160 * T32;
           emit(I5{}, [&](int q, int c) { return gq[q] * a2[2 * T32 + (q >> 2)][c][q & 3]; },
                [&](int lc) { return Hh * (NT1 > 0 ? 4 : 1) + 160 * T32 + lc; }, [&](int lc) { return nb + lc; }, 5 * W, true);
@@ -567,13 +600,7 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
       for (int t = 0; t < NT2; ++t) tile(I5{}, 2, t, [&](int q, int c) { return a2[2 * t + (q >> 2)][c][q & 3]; });
     }
   }
-  if constexpr (!SCAT) {
-    if (segs.amax) {  // max over the finite values only, filtered per element above (as e3_pow2_scale does)
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-      if (lane == 0 && amax > 0.f) atomicMax(segs.amax, __builtin_bit_cast(uint32_t, amax));
-    }
-  }
+  if constexpr (!SCAT) amax_finish(segs, amax, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -625,7 +652,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
   int* ocl = reinterpret_cast<int*>(nrm + ((Dout + 15) & ~15));
   float* nrm2 = reinterpret_cast<float*>(ocl + ((ntab + 15) & ~15));
   int* ocl2 = reinterpret_cast<int*>(nrm2 + ((Dout2 + 15) & ~15));
-  float* cbuf = reinterpret_cast<float*>(ocl2 + ((ntab2 + 15) & ~15)) + (size_t)wave * (CHUNK + 160);
+  float* cbuf = reinterpret_cast<float*>(ocl2 + ((ntab2 + 15) & ~15)) + (size_t)wave * (CHUNK + kR16YTile);
   float* ybuf = cbuf + CHUNK;
   // plan 1's operand scales as in tp_fwd_mfma_r16_kernel; plan 2's norms carry its weight scale only (u's scale is per row)
   const float* hdr = packed + ((Dout + 3) & ~3);
@@ -654,10 +681,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
   using I2 = std::integral_constant<int, 2>;
   using I3 = std::integral_constant<int, 3>;
   using I5 = std::integral_constant<int, 5>;
-  // this lane's 8 channels of a 32-channel tile: q = 4 * (16-tile) + r  ->  channel 16 * (q >> 2) + 4 * g + (q & 3)
-  auto chan_of = [&](int q) { return 16 * (q >> 2) + 4 * g + (q & 3); };
-  const bool out_vec = !(ldo & 3) && ((reinterpret_cast<uintptr_t>(outv) & 15) == 0) &&
-                       (!segs.residual || (!(segs.ldr & 3) && (reinterpret_cast<uintptr_t>(segs.residual) & 15) == 0));
+  const bool out_vec = out_vec_ok(outv, ldo, segs);
   float amax = 0.f;  // running max |h'| of this lane's stores
 
   for (int64_t tile = (int64_t)blockIdx.x * nwaves + wave; tile < ntiles; tile += tstride) {
@@ -732,15 +756,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
       const FChunk ch = chunks[ci];
       float x[8][2 * L1 + 1];
       load_x16<L1, IO16>(cbuf + j * (((32 * (2 * L1 + 1) / (IO16 ? 8 : 4)) | 1) * 4), g, xs, x);
-#define E3_RUN(L2v, L3v, ACC, NTv)                                                                             \
-  if constexpr (Slots::valid(L1, L2v, L3v)) {                                                                  \
-    const size_t o = (size_t)(cBfoff[L3v] >> 3) + (size_t)(2 * ch.wblk[L2v][L3v] + g) * cMpad[L3v] + j;        \
-    run16<L1, L2v, L3v, 2 * NTv, IO16>(x, true, whi_base + o, wlo_base + o, y, ACC);                            \
-  }
-      E3_RUN(0, 0, a0, NT0) E3_RUN(1, 0, a0, NT0) E3_RUN(2, 0, a0, NT0)
-      E3_RUN(0, 1, a1, NT1) E3_RUN(1, 1, a1, NT1) E3_RUN(2, 1, a1, NT1)
-      E3_RUN(0, 2, a2, NT2) E3_RUN(1, 2, a2, NT2) E3_RUN(2, 2, a2, NT2)
-#undef E3_RUN
+      run_paths<Slots, L1, IO16>(x, true, g, j, ch, whi_base, wlo_base, cBfoff, cMpad, y, a0, a1, a2);
       wave_sync_lds();
       if (ci + 1 < nchunks) stage(ci + 1);
       ++ci;
@@ -756,23 +772,23 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
       const float* nrm0 = nrm + ocl[cOoff[0]];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float s = a0[q >> 2][0][q & 3] * nrm0[chan_of(q)];
+        const float s = a0[q >> 2][0][q & 3] * nrm0[chan_of(g, q)];
         a0[q >> 2][0][q & 3] = s * sigmoid_(s);
       }
       const float* nv1 = nrm + ocl[cOoff[1]];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float gq = sigmoid_(a0[2 + (q >> 2)][0][q & 3] * nrm0[32 + chan_of(q)]);
+        const float gq = sigmoid_(a0[2 + (q >> 2)][0][q & 3] * nrm0[32 + chan_of(g, q)]);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) a1[q >> 2][c][q & 3] = (gq * a1[q >> 2][c][q & 3]) * nv1[3 * chan_of(q) + c];
+        for (int c = 0; c < 3; ++c) a1[q >> 2][c][q & 3] = (gq * a1[q >> 2][c][q & 3]) * nv1[3 * chan_of(g, q) + c];
       }
       if constexpr (NT2 > 0) {
         const float* nv2 = nrm + ocl[cOoff[2]];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          const float gq = sigmoid_(a0[4 + (q >> 2)][0][q & 3] * nrm0[64 + chan_of(q)]);
+          const float gq = sigmoid_(a0[4 + (q >> 2)][0][q & 3] * nrm0[64 + chan_of(g, q)]);
 #pragma unroll
-          for (int c = 0; c < 5; ++c) a2[q >> 2][c][q & 3] = (gq * a2[q >> 2][c][q & 3]) * nv2[5 * chan_of(q) + c];
+          for (int c = 0; c < 5; ++c) a2[q >> 2][c][q & 3] = (gq * a2[q >> 2][c][q & 3]) * nv2[5 * chan_of(g, q) + c];
         }
       }
     }
@@ -817,12 +833,12 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
 #pragma unroll
         for (int q = 0; q < 8; ++q)
 #pragma unroll
-          for (int c = 0; c < D; ++c) o16[D * chan_of(q) + c] = __builtin_bit_cast(uint16_t, (__bf16)val(q, c));
+          for (int c = 0; c < D; ++c) o16[D * chan_of(g, q) + c] = __builtin_bit_cast(uint16_t, (__bf16)val(q, c));
       } else {
 #pragma unroll
         for (int q = 0; q < 8; ++q)
 #pragma unroll
-          for (int c = 0; c < D; ++c) cbuf[j * (32 * D + 4) + D * chan_of(q) + c] = val(q, c) * srow;
+          for (int c = 0; c < D; ++c) cbuf[j * (32 * D + 4) + D * chan_of(g, q) + c] = val(q, c) * srow;
       }
       wave_sync_lds();
     };
@@ -832,15 +848,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
       const FChunk ch = pr.chunks[L1];
       float x[8][2 * L1 + 1];
       load_x16<L1, IO16>(cbuf + j * (((32 * (2 * L1 + 1) / (IO16 ? 8 : 4)) | 1) * 4), g, 1.0f, x);
-#define E3_RUN2(L2v, L3v, ACC, NTv)                                                                            \
-  if constexpr (Slots2::valid(L1, L2v, L3v)) {                                                                 \
-    const size_t o = (size_t)(cBfoff2[L3v] >> 3) + (size_t)(2 * ch.wblk[L2v][L3v] + g) * cMpad2[L3v] + j;      \
-    run16<L1, L2v, L3v, 2 * NTv, IO16>(x, true, whi2_base + o, wlo2_base + o, y, ACC);                          \
-  }
-      E3_RUN2(0, 0, b0, 1) E3_RUN2(1, 0, b0, 1) E3_RUN2(2, 0, b0, 1)
-      E3_RUN2(0, 1, b1, NT1) E3_RUN2(1, 1, b1, NT1) E3_RUN2(2, 1, b1, NT1)
-      E3_RUN2(0, 2, b2, NT2) E3_RUN2(1, 2, b2, NT2) E3_RUN2(2, 2, b2, NT2)
-#undef E3_RUN2
+      run_paths<Slots2, L1, IO16>(x, true, g, j, ch, whi2_base, wlo2_base, cBfoff2, cMpad2, y, b0, b1, b2);
       wave_sync_lds();
     };
     put(I1{}, [&](int q, int) { return a0[q >> 2][0][q & 3]; });
@@ -867,7 +875,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
 #pragma unroll
       for (int q = 0; q < 8; ++q)
 #pragma unroll
-        for (int c = 0; c < D; ++c) ot[j * TS + D * chan_of(q) + c] = val(q, c);
+        for (int c = 0; c < D; ++c) ot[j * TS + D * chan_of(g, q) + c] = val(q, c);
       wave_sync_lds();
       if (vec) {
         constexpr uint32_t INV = (65536 + UPR - 1) / UPR;
@@ -936,11 +944,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
     emit(I3{}, 1, [&](int q, int c) { return b1[q >> 2][c][q & 3] * isrow; });
     if constexpr (NT2 > 0) emit(I5{}, 2, [&](int q, int c) { return b2[q >> 2][c][q & 3] * isrow; });
   }
-  if (segs.amax) {  // max over the finite values only, filtered per element above (as e3_pow2_scale does)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    if (lane == 0 && amax > 0.f) atomicMax(segs.amax, __builtin_bit_cast(uint32_t, amax));
-  }
+  amax_finish(segs, amax, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -999,15 +1003,49 @@ static const R16KernelEntry* r16_find(const TpFast* F) {
     if (k.lsh == d.lsh && k.nt0 == d.NT[0] && k.nt1 == d.NT[1] && k.nt2 == d.NT[2] && k.l1s == l1s) return &k;
   return nullptr;
 }
+// per-wave LDS: the chunk buffer for the plan's staged chunks and out tiles of degree <= lout, and the Y tile
+static size_t r16_wave_bytes(const TpFast* F, int lout) {
+  int lin = 0;
+  for (auto& c : F->h_chunks) lin = std::max(lin, c.l1);
+  return (size_t)(r16_chunk(lin, lout) + kR16YTile) * 4;
+}
 static size_t r16_lds_bytes(const TpFast* F, int nwaves) {
   const FDev& d = F->dev;
   const size_t tables = (size_t)(((d.Dout + 4 + 15) & ~15) + ((d.ntab + 15) & ~15)) * 4;
-  int lin = 0;
-  for (auto& c : F->h_chunks) lin = std::max(lin, c.l1);
-  const size_t per_wave = (size_t)(r16_chunk(lin, d.NT[2] > 0 ? 2 : (d.NT[1] > 0 ? 1 : 0)) + 160) * 4;
-  return tables + nwaves * per_wave;
+  return tables + nwaves * r16_wave_bytes(F, d.NT[2] > 0 ? 2 : (d.NT[1] > 0 ? 1 : 0));
 }
 constexpr int kR16Waves = 4;  // per workgroup; two or three workgroups per CU
+
+// Launch `fn` (either kernel: `pair` is the fused node update's extra argument, null for one product) on plan F's tables.
+// 1 = launched, 0 = the LDS of `waves_per_simd` workgroups per CU does not fit, < 0 = -status
+static int r16_launch(const void* fn, const char* name, size_t lds_bytes, int waves_per_simd, const TpFast* F, const void* sa_,
+                      const void* in2, int64_t ld2, const void* packed, void* out, int64_t ldo, int64_t B,
+                      const int32_t* ocol_tab, const float* in_scale, const PairArgs* pair, hipStream_t s) {
+  if ((size_t)waves_per_simd * lds_bytes > (size_t)kFastLds) return 0;
+  {  // the dynamic-LDS limit is a per-device attribute of the function
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -E3_ERR_HIP;
+    static std::mutex mu;
+    static std::vector<std::pair<const void*, int>> configured;
+    std::lock_guard<std::mutex> lock(mu);
+    if (std::find(configured.begin(), configured.end(), std::make_pair(fn, dev)) == configured.end()) {
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return -E3_ERR_HIP;
+      configured.emplace_back(fn, dev);
+    }
+  }
+  const int64_t ntiles = (B + 15) / 16;
+  const int grid = (int)std::min<int64_t>((ntiles + kR16Waves - 1) / kR16Waves, 256 * waves_per_simd);
+  const float* in2f = (const float*)in2;
+  const float* pk = (const float*)packed;
+  const FDev* dd = F->d_dev;
+  const FChunk* dc = F->d_chunks;
+  // the pair kernel's parameter list is the generic kernel's plus a trailing PairArgs
+  std::vector<void*> args = {const_cast<void*>(sa_), &in2f, &ld2, &pk, &out, &ldo, &B, &dd, &dc, &ocol_tab, &in_scale};
+  if (pair) args.push_back(const_cast<PairArgs*>(pair));
+  if (hipLaunchKernel(fn, dim3(grid), dim3(64 * kR16Waves), args.data(), lds_bytes, s) != hipSuccess) return -E3_ERR_HIP;
+  fast_note_kernel(name);
+  return 1;
+}
 
 bool r16_supported(const TpFast* F) {
   return r16_find(F) != nullptr &&
@@ -1025,30 +1063,8 @@ int fast_forward_r16(const TpFast* F, const void* sa_, const void* in2, int64_t 
   if (scat && (io16 || !gate || !e->fn_scat)) return 0;
   if (scat && (static_cast<const SegArgs*>(sa_)->residual || static_cast<const SegArgs*>(sa_)->amax)) return 0;
   const void* fn = scat ? e->fn_scat : e->fn[io16 ? 1 : 0][gate ? 1 : 0];
-  const size_t lds_bytes = r16_lds_bytes(F, kR16Waves);
-  if ((size_t)r16_waves_per_simd(d.NT[0], d.NT[1], d.NT[2]) * lds_bytes > (size_t)kFastLds) return 0;
-  {  // the dynamic-LDS limit is a per-device attribute of the function
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -E3_ERR_HIP;
-    static std::mutex mu;
-    static std::vector<std::pair<const void*, int>> configured;
-    std::lock_guard<std::mutex> lock(mu);
-    if (std::find(configured.begin(), configured.end(), std::make_pair(fn, dev)) == configured.end()) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return -E3_ERR_HIP;
-      configured.emplace_back(fn, dev);
-    }
-  }
-  const int64_t ntiles = (B + 15) / 16;
-  const int grid = (int)std::min<int64_t>((ntiles + kR16Waves - 1) / kR16Waves, 256 * r16_waves_per_simd(d.NT[0], d.NT[1], d.NT[2]));
-  const float* in2f = (const float*)in2;
-  const float* pk = (const float*)packed;
-  void* outf = out;
-  const FDev* dd = F->d_dev;
-  const FChunk* dc = F->d_chunks;
-  void* args[] = {const_cast<void*>(sa_), &in2f, &ld2, &pk, &outf, &ldo, &B, &dd, &dc, &ocol_tab, &in_scale};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(64 * kR16Waves), args, lds_bytes, s) != hipSuccess) return -E3_ERR_HIP;
-  fast_note_kernel("e3::tp_fwd_mfma_r16_kernel");
-  return 1;
+  return r16_launch(fn, "e3::tp_fwd_mfma_r16_kernel", r16_lds_bytes(F, kR16Waves), r16_waves_per_simd(d.NT[0], d.NT[1], d.NT[2]),
+                    F, sa_, in2, ld2, packed, out, ldo, B, ocol_tab, in_scale, nullptr, s);
 }
 
 // fused node update: plan 1 = update #1 (the r16 entry's chunk sequence), plan 2 = update #2
@@ -1088,9 +1104,7 @@ static size_t r16_pair_lds_bytes(const TpFast* F1, const TpFast* F2, int nwaves)
   const FDev& d2 = F2->dev;
   const size_t tables =
       (size_t)(((d.Dout + 15) & ~15) + ((d.ntab + 15) & ~15) + ((d2.Dout + 15) & ~15) + ((d2.ntab + 15) & ~15)) * 4;
-  int lin = 0;
-  for (auto& c : F1->h_chunks) lin = std::max(lin, c.l1);
-  return tables + nwaves * (size_t)(r16_chunk(lin, d.NT[2] > 0 ? 2 : 1) + 160) * 4;
+  return tables + nwaves * r16_wave_bytes(F1, d.NT[2] > 0 ? 2 : 1);
 }
 
 bool r16_pair_supported(const TpFast* F1, const TpFast* F2) {
@@ -1109,32 +1123,9 @@ int fast_forward_pair_r16(const TpFast* F1, const TpFast* F2, const void* sa_, c
     if (sa.index[i] || (sa.ld[i] % epu) || ((sa.col0[i + 1] - sa.col0[i]) % epu) ||
         (reinterpret_cast<uintptr_t>(sa.base[i]) & 15))
       return 0;
-  const void* fn = e->fn[io16 ? 1 : 0];
-  const size_t lds_bytes = r16_pair_lds_bytes(F1, F2, kR16Waves);
-  if (2 * lds_bytes > (size_t)kFastLds) return 0;
-  {  // the dynamic-LDS limit is a per-device attribute of the function
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -E3_ERR_HIP;
-    static std::mutex mu;
-    static std::vector<std::pair<const void*, int>> configured;
-    std::lock_guard<std::mutex> lock(mu);
-    if (std::find(configured.begin(), configured.end(), std::make_pair(fn, dev)) == configured.end()) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return -E3_ERR_HIP;
-      configured.emplace_back(fn, dev);
-    }
-  }
-  const int64_t ntiles = (B + 15) / 16;
-  const int grid = (int)std::min<int64_t>((ntiles + kR16Waves - 1) / kR16Waves, 256 * 2);
-  const float* in2f = (const float*)in2;
-  const float* pk = (const float*)packed1;
-  void* outf = out;
-  const FDev* dd = F1->d_dev;
-  const FChunk* dc = F1->d_chunks;
-  PairArgs pa{(const float*)packed2, F2->d_dev, F2->d_chunks, ocol2};
-  void* args[] = {const_cast<void*>(sa_), &in2f, &ld2, &pk, &outf, &ldo, &B, &dd, &dc, &ocol1, &in_scale, &pa};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(64 * kR16Waves), args, lds_bytes, s) != hipSuccess) return -E3_ERR_HIP;
-  fast_note_kernel("e3::tp_update_pair_r16_kernel");
-  return 1;
+  const PairArgs pa{(const float*)packed2, F2->d_dev, F2->d_chunks, ocol2};
+  return r16_launch(e->fn[io16 ? 1 : 0], "e3::tp_update_pair_r16_kernel", r16_pair_lds_bytes(F1, F2, kR16Waves), 2, F1, sa_, in2,
+                    ld2, packed1, out, ldo, B, ocol1, in_scale, &pa, s);
 }
 
 }  // namespace e3

@@ -97,6 +97,34 @@ def test_bf16_bit_identical_to_two_launch():
     assert got is not None and torch.equal(got, ref)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B", [1, 17])
+def test_unaligned_residual_takes_the_scalar_store(B, dtype):
+    """A residual that is a column slice of a wider tensor (contiguous rows, odd leading dimension, misaligned base) rules
+    out the vector store: the kernel's element-wise store loop must give what the aligned call gives."""
+    upd1, upd2 = _pair(32, seed=8, dtype=dtype)
+    h, a, A = _inputs(B, seed=20 + B, dtype=dtype, spread=False)
+    wide = torch.zeros(B, 290, dtype=dtype, device=DEV)
+    res = wide[:, 1:289]
+    res.copy_(h)
+    assert res.stride(0) == 290 and res.data_ptr() % 16 != 0 and torch.equal(res, h)
+    scale = {"out_scale": 10} if dtype == torch.float32 else {}
+    with torch.no_grad():
+        got = upd1.forward_update_pair(upd2, [(h, None), (a, None)], A, residual=res, **scale)
+        assert _lib.load().e3_tp_last_fused_kernel() == b"e3::tp_update_pair_r16_kernel"
+        ref = upd1.forward_update_pair(upd2, [(h, None), (a, None)], A, residual=h.clone(), **scale)
+    if dtype == torch.float32:
+        (got, sc), (ref, _) = got, ref
+    err = float(np.abs(_np(got) - _np(ref)).max() / np.abs(_np(ref)).max())
+    print(f"\nB={B} {dtype}: unaligned vs aligned residual {err:.2e}")
+    if dtype == torch.float32:
+        assert err <= 1e-5
+        s, inv, _ = expected_scale([got.cpu().numpy()], 10)
+        assert (float(sc[0]), float(sc[1])) == (s, inv)
+    else:
+        assert err <= 2.0 ** -7   # one rounding of the fp32 sum, as tests/test_scale_gpu.py
+
+
 @pytest.mark.parametrize("kind", ["nan", "inf"])
 def test_nonfinite_rows_stay_in_their_row(kind):
     """A bad value in one row of h or a stays in that row of h' and leaves the scale and every other row alone (the row
