@@ -50,6 +50,28 @@ __device__ __forceinline__ void mma_group(const uint4 (&ah)[NT16], const uint4 (
   }
 }
 
+// the fp16-split group with `mid()` between its second and third product: from there on `ah` is dead, so whatever mid
+// loads (the next path's A operands) takes the registers of `ah` instead of coming on top of them
+template <int NT16, int STRIDE, class Mid>
+__device__ __forceinline__ void mma_group_mid(const uint4 (&ah)[NT16], const uint4 (&al)[NT16], const uint4 bh, const uint4 bl,
+                                              f32x4* acc, Mid&& mid) {
+#pragma unroll
+  for (int t = 0; t < NT16; ++t)
+    acc[t * STRIDE] = mfma16h(__builtin_bit_cast(f16x8, ah[t]), __builtin_bit_cast(f16x8, bh), acc[t * STRIDE]);
+#pragma unroll
+  for (int t = 0; t < NT16; ++t)
+    acc[t * STRIDE] = mfma16h(__builtin_bit_cast(f16x8, ah[t]), __builtin_bit_cast(f16x8, bl), acc[t * STRIDE]);
+  __builtin_amdgcn_sched_barrier(0);
+  mid();
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < NT16; ++t)
+    acc[t * STRIDE] = mfma16h(__builtin_bit_cast(f16x8, al[t]), __builtin_bit_cast(f16x8, bh), acc[t * STRIDE]);
+}
+struct NoMid {
+  __device__ __forceinline__ void operator()() const {}
+};
+
 // 8 fp32 features -> B operand(s): bf16 (rounded once) or fp16 (hi, lo)
 template <bool IO16>
 __device__ __forceinline__ void pack_b(const float (&f)[8], uint4& bh, uint4& bl) {
@@ -98,19 +120,24 @@ __device__ __forceinline__ void load_x16(const float* __restrict__ xr, const int
 // One input chunk (degree L1, <= 32 channels = one K = 32 step) into NT16 16-channel tiles of output degree L3.
 // `x`: the lane's operand slice (load_x16); `whi`/`wlo`: packed weights at (block 2*wblk + g', channel lane & 15) of
 // tile 0; `live`: this lane's k group lies inside the (16-padded) chunk -- otherwise its features are zero.
-template <int L1, int L2, int L3, int NT16, bool IO16>
-__device__ __forceinline__ void run16(const float (&x)[8][2 * L1 + 1], const bool live,
-                                      const uint4* __restrict__ whi, const uint4* __restrict__ wlo,
-                                      const float (&y)[9], f32x4 (&acc)[NT16][2 * L3 + 1]) {
-  constexpr int D1 = 2 * L1 + 1, D2 = 2 * L2 + 1, D3 = 2 * L3 + 1;
-  using C = CG<L1, L2, L3>;
-  __builtin_amdgcn_sched_barrier(0);
-  uint4 ah[NT16], al[IO16 ? 1 : NT16];
+// A path is a request (its A operands: one 16-byte load per 16-channel tile, two with the fp16 split) and a compute
+// (couplings, B operands, MFMAs).  run16 does both at once; run_paths_ahead requests a path while the one before computes.
+template <int NT16, bool IO16>
+__device__ __forceinline__ void request16(const uint4* __restrict__ whi, const uint4* __restrict__ wlo, uint4 (&ah)[NT16],
+                                          uint4 (&al)[IO16 ? 1 : NT16]) {
 #pragma unroll
   for (int t = 0; t < NT16; ++t) {
     ah[t] = whi[16 * t];
     if constexpr (!IO16) al[t] = wlo[16 * t];
   }
+}
+
+template <int L1, int L2, int L3, int NT16, bool IO16, class Mid = NoMid>
+__device__ __forceinline__ void compute16(const float (&x)[8][2 * L1 + 1], const bool live, const uint4 (&ah)[NT16],
+                                          const uint4 (&al)[IO16 ? 1 : NT16], const float (&y)[9],
+                                          f32x4 (&acc)[NT16][2 * L3 + 1], Mid&& mid = Mid{}) {
+  constexpr int D1 = 2 * L1 + 1, D2 = 2 * L2 + 1, D3 = 2 * L3 + 1;
+  using C = CG<L1, L2, L3>;
   // z[a][c] = sum_b C[a][b][c] Y_l2[b] of THIS lane's row (features and accumulator columns both belong to row lane & 15)
   float z[D1][D3];
 #pragma unroll
@@ -167,9 +194,24 @@ __device__ __forceinline__ void run16(const float (&x)[8][2 * L1 + 1], const boo
     }
     uint4 bh, bl;
     pack_b<IO16>(f, bh, bl);
-    mma_group<NT16, IO16, D3>(ah, al, bh, bl, &acc[0][c]);
+    if constexpr (std::is_same<std::decay_t<Mid>, NoMid>::value) {
+      mma_group<NT16, IO16, D3>(ah, al, bh, bl, &acc[0][c]);
+    } else {
+      static_assert(!IO16 && D3 == 1, "the hook runs once: scalar outputs with the fp16 split");
+      mma_group_mid<NT16, D3>(ah, al, bh, bl, &acc[0][c], mid);
+    }
   }
   __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int L1, int L2, int L3, int NT16, bool IO16>
+__device__ __forceinline__ void run16(const float (&x)[8][2 * L1 + 1], const bool live,
+                                      const uint4* __restrict__ whi, const uint4* __restrict__ wlo,
+                                      const float (&y)[9], f32x4 (&acc)[NT16][2 * L3 + 1]) {
+  __builtin_amdgcn_sched_barrier(0);
+  uint4 ah[NT16], al[IO16 ? 1 : NT16];
+  request16<NT16, IO16>(whi, wlo, ah, al);
+  compute16<L1, L2, L3, NT16, IO16>(x, live, ah, al, y, acc);
 }
 
 // NT0/NT1/NT2 = 32-channel tile counts per output degree as in the other kernels (each = two 16-channel MFMA tiles)
@@ -215,6 +257,100 @@ __device__ __forceinline__ void run_paths(const float (&x)[8][2 * L1 + 1], const
   path(I0{}, I0{}, a0); path(I1{}, I0{}, a0); path(I2{}, I0{}, a0);
   path(I0{}, I1{}, a1); path(I1{}, I1{}, a1); path(I2{}, I1{}, a1);
   path(I0{}, I2{}, a2); path(I1{}, I2{}, a2); path(I2{}, I2{}, a2);
+}
+
+// ---- the same paths with their weights one path ahead (tp_update_pair_r16_kernel) ----
+// run_paths exposes one L2 round trip per path: run16 loads its A operands and multiplies with them at once.  Here the
+// A operands of path p + 1 are requested before path p computes -- also across a chunk boundary and from product #1 into
+// product #2 -- so a path waits only for loads that had a whole path's compute to return.  The order of paths, of chunks
+// and of the MFMAs inside a path is run_paths' order: the sums are bit-identical.
+
+// the valid paths (L1, l2, l3) of Slots in run_paths' order: l3 major, l2 minor
+template <class Slots, int L1>
+struct PathList {
+  static constexpr int code(int i) {
+    for (int l3 = 0; l3 < 3; ++l3)
+      for (int l2 = 0; l2 < 3; ++l2)
+        if (Slots::valid(L1, l2, l3) && i-- == 0) return 3 * l3 + l2;
+    return -1;
+  }
+  static constexpr int n() {
+    int c = 0;
+    while (code(c) >= 0) ++c;
+    return c;
+  }
+  static constexpr int l2(int i) { return code(i) % 3; }
+  static constexpr int l3(int i) { return code(i) / 3; }
+};
+// the A operands in flight: up to MAXT 16-channel tiles (only the tiles of the requested path are ever live)
+template <int MAXT, bool IO16>
+struct PathW {
+  uint4 hi[MAXT], lo[IO16 ? 1 : MAXT];
+};
+// Where a plan's packed weights are.  A path's address is a wave-uniform part (the class matrix and the chunk's block: scalar
+// registers) plus this lane's place in a block, `voff` bytes, one value per output degree.  The caller derives voff from an
+// opaque copy of the lane id inside its tile loop: as plain loop invariants the 33 per-lane 64-bit addresses of the two
+// products are hoisted out of the loop, spilled, and reloaded from scratch in front of every path's loads.
+struct PathSrc {
+  const uint4 *whi, *wlo;
+  int bfoff[3], mpad[3];
+  uint32_t voff[3];
+};
+__device__ __forceinline__ PathSrc path_src(const uint4* whi, const uint4* wlo, const int (&bfoff)[3], const int (&mpad)[3],
+                                            const int gw, const int j) {
+  return PathSrc{whi, wlo, {bfoff[0], bfoff[1], bfoff[2]}, {mpad[0], mpad[1], mpad[2]},
+                 {(uint32_t)(gw * mpad[0] + j) * 16u, (uint32_t)(gw * mpad[1] + j) * 16u, (uint32_t)(gw * mpad[2] + j) * 16u}};
+}
+// request path I of the chunk `ch` of degree L1 (nothing if the chunk has no such path)
+template <class Slots, int L1, int I, bool IO16, int MAXT>
+__device__ __forceinline__ void request_path(const PathSrc& s, const FChunk& ch, PathW<MAXT, IO16>& w) {
+  using P = PathList<Slots, L1>;
+  if constexpr (I < P::n()) {
+    constexpr int L2 = P::l2(I), L3 = P::l3(I), NT16 = 2 * Slots::nt(L3);
+    static_assert(NT16 <= MAXT && CG<L1, L2, L3>::valid, "path bookkeeping");
+    const size_t o = (size_t)(s.bfoff[L3] >> 3) + (size_t)(2 * ch.wblk[L2][L3]) * s.mpad[L3];  // wave-uniform
+    const char* const ph = reinterpret_cast<const char*>(s.whi + o);
+    const char* const pl = reinterpret_cast<const char*>(s.wlo + o);
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) {
+      w.hi[t] = *reinterpret_cast<const uint4*>(ph + 256 * t + s.voff[L3]);
+      if constexpr (!IO16) w.lo[t] = *reinterpret_cast<const uint4*>(pl + 256 * t + s.voff[L3]);
+    }
+  }
+}
+// Every path of one staged chunk.  On entry `w` holds the chunk's first path (requested by the caller); before the last
+// path computes, `next(w)` requests whatever follows the chunk (the first path of the next chunk, or nothing).
+template <class Slots, int L1, bool IO16, int MAXT, int T0, int T1, int T2, class Next>
+__device__ __forceinline__ void run_paths_ahead(const float (&x)[8][2 * L1 + 1], const bool live, const PathSrc& s,
+                                                const FChunk& ch, const float (&y)[9], f32x4 (&a0)[T0][1],
+                                                f32x4 (&a1)[T1][3], f32x4 (&a2)[T2][5], PathW<MAXT, IO16>& w,
+                                                Next&& next) {
+  using P = PathList<Slots, L1>;
+  auto step = [&](auto itag) {
+    constexpr int I = decltype(itag)::value;
+    constexpr int L2 = P::l2(I), L3 = P::l3(I), NT16 = 2 * Slots::nt(L3);
+    uint4 ah[NT16], al[IO16 ? 1 : NT16];
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) {
+      ah[t] = w.hi[t];
+      if constexpr (!IO16) al[t] = w.lo[t];
+    }
+    // A six-tile path with the fp16 split holds 48 registers of A operands: the next request waits until half of them
+    // are dead (mma_group_mid) -- still a product group and the next path's B operands ahead of its first use.
+    constexpr bool SPLIT = !IO16 && L3 == 0 && NT16 > 2 && I + 1 < P::n();
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (SPLIT) {
+      compute16<L1, L2, 0, NT16, IO16>(x, live, ah, al, y, a0, [&]() { request_path<Slots, L1, I + 1, IO16>(s, ch, w); });
+      return;
+    }
+    if constexpr (I + 1 < P::n()) request_path<Slots, L1, I + 1, IO16>(s, ch, w);
+    else next(w);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (L3 == 0) compute16<L1, L2, 0, NT16, IO16>(x, live, ah, al, y, a0);
+    else if constexpr (L3 == 1) compute16<L1, L2, 1, NT16, IO16>(x, live, ah, al, y, a1);
+    else compute16<L1, L2, 2, NT16, IO16>(x, live, ah, al, y, a2);
+  };
+  for_each_index(step, std::make_index_sequence<P::n()>{});
 }
 
 // this lane's 8 channels of a 32-channel tile: q = 4 * (16-tile) + r  ->  channel 16 * (q >> 2) + 4 * g + (q & 3)
@@ -605,9 +741,10 @@ __global__ __launch_bounds__(256, r16_waves_per_simd(NT0, NT1, NT2)) void tp_fwd
 
 // ---------------------------------------------------------------------------------------------------
 // Fused node update (e3_tp_forward_update_pair): update #1 (plan 1: [h | a] x A, gated) and update #2 (plan 2: u x A, plus the
-// residual h and the scale of the result) in one launch.  u never leaves the wave: after product #1 it is written one degree
-// at a time into the chunk buffer, laid out as a staged chunk of that degree, and product #2's chunk of that degree runs off
-// it.  fp32 storage: u gets a power-of-two operand scale PER ROW -- lane & 15 is the row both in the accumulators and in the
+// residual h and the scale of the result) in one launch.  u never leaves the wave: after product #1 it is written into the
+// chunk buffer (degrees 0 and 1 side by side, then degree 2), each degree laid out as a staged chunk of that degree, and
+// product #2's chunk of that degree runs off it.  The A operands of both products travel one path ahead of the MFMAs
+// (run_paths_ahead).  fp32 storage: u gets a power-of-two operand scale PER ROW -- lane & 15 is the row both in the accumulators and in the
 // B operand, so a row's scale is one value per lane, with no pass over u and no agreement between waves -- and product #2's
 // accumulators are multiplied by its exact inverse.  bf16 storage: u is rounded to bf16 as the two-launch path stores it and
 // the chunks run in the same order, so the result is bit-identical.  Hidden 32: one 32-channel tile per degree of u.
@@ -634,10 +771,9 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
   constexpr int CHUNK = r16_chunk(r16_max({L1S...}), NL);
   extern __shared__ __align__(16) unsigned char smem_raw[];
   float* lds = reinterpret_cast<float*>(smem_raw);
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;  // (the lane id is regenerated where it is needed: see the tile loop)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nwaves = blockDim.x >> 6;
-  const int j = lane & 15, g = lane >> 4;
   const int Dout = dp->Dout, Dy = dp->Dy, nchunks = dp->nchunks, ntab = dp->ntab;
   const int Dout2 = pr.dp->Dout, ntab2 = pr.dp->ntab;
   int cMpad[3], cOoff[3], cBfoff[3], cM2[3], cMpad2[3], cOoff2[3], cBfoff2[3];
@@ -683,10 +819,25 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
   using I5 = std::integral_constant<int, 5>;
   const bool out_vec = out_vec_ok(outv, ldo, segs);
   float amax = 0.f;  // running max |h'| of this lane's stores
+  // the A operands travel one path ahead of the MFMAs (run_paths_ahead), through both products
+  constexpr int NU = 2 + (NT2 > 0 ? 1 : 0);  // degrees of u = chunks of plan 2
+  PathW<2 * NT0, IO16> wq;
 
   for (int64_t tile = (int64_t)blockIdx.x * nwaves + wave; tile < ntiles; tile += tstride) {
     const int64_t row0 = tile * 16;
     const int nrows = (int)((B - row0) < 16 ? (B - row0) : 16);
+    // the lane id, regenerated per tile (all 64 lanes are active here) and opaque to the optimiser: what the staging, the
+    // weight addresses and the LDS offsets of the tile writes derive from it is recomputed in a few instructions per tile
+    // instead of being hoisted out of the loop and spilled (see PathSrc)
+    int lj;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lj));
+    const int j = lj & 15, g = lj >> 4;  // row, k group
+    // the tile's first path: ahead of the staging copies, under the wait they need anyway.  (Weights only: the prefetch
+    // never reads a row, so nothing lies behind the last tile.)
+    const PathSrc ws1 = path_src(whi_base, wlo_base, cBfoff, cMpad, g, j);
+    const PathSrc ws2 = path_src(whi2_base, wlo2_base, cBfoff2, cMpad2, g, j);
+    request_path<Slots, Seq::at(0), 0, IO16>(ws1, chunks[0], wq);
+    __builtin_amdgcn_sched_barrier(0);
 
     // chunk ci of [h | a] -> chunk buffer: rows row0 .. row0 + 15 of its segment, one 16-byte LDS-DMA unit per lane (rows of
     // S units, the odd pad unit unused), zeros for the tail rows
@@ -707,19 +858,19 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
       constexpr int ESZ = IO16 ? 2 : 4, EPU = 16 / ESZ, MI = IO16 ? 1 : 0;
       const int cw = ch.count * (2 * ch.l1 + 1);  // whole 32-channel chunks: no padding columns
       const int S = ch.S[MI], rows_per = ch.rows_per[MI];
-      const int rl = (lane * ch.inv[MI]) >> 16, u = lane - rl * S;
+      const int rl = (lj * ch.inv[MI]) >> 16, u = lj - rl * S;
       const bool lane_ok = rl < rows_per && u < cw / EPU;
       const char* lsrc = base + ((row0 + rl) * ld + segcol) * ESZ + u * 16;
       for (int r0 = 0; r0 < 16; r0 += rows_per)
         if (lane_ok && r0 + rl < nrows)
           __builtin_amdgcn_global_load_lds((glb_void_t*)(lsrc + (int64_t)r0 * ld * ESZ), (lds_void_t*)(cbuf + r0 * S * 4), 16,
                                            0, 0);
-      for (int e = nrows * S * 4 + lane; e < 16 * S * 4; e += 64) cbuf[e] = 0.f;
+      for (int e = nrows * S * 4 + lj; e < 16 * S * 4; e += 64) cbuf[e] = 0.f;
     };
 
     // Y tile [16][Dy]
     for (int h = 0; h * 64 < 16 * Dy; ++h) {
-      const int e = h * 64 + lane;
+      const int e = h * 64 + lj;
       const int yr = (e * inv_dy) >> 16, yc = e - yr * Dy;
       if (e < 16 * Dy) {
         if (yr < nrows)
@@ -744,27 +895,44 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
 #pragma unroll
       for (int c = 0; c < 5; ++c) a2[t][c] = f32x4{0, 0, 0, 0};
     float y[9];
-    int ci = 0;
     auto process = [&](auto itag) {
-      constexpr int L1 = Seq::at(decltype(itag)::value);
+      constexpr int CI = decltype(itag)::value, L1 = Seq::at(CI);
       wait_vm0();
       wave_sync_lds();
-      if (ci == 0) {
+      if constexpr (CI == 0) {
 #pragma unroll
         for (int q = 0; q < 9; ++q) y[q] = (q < Dy) ? ybuf[j * Dy + q] : 0.f;
       }
-      const FChunk ch = chunks[ci];
+      const FChunk ch = chunks[CI];
       float x[8][2 * L1 + 1];
       load_x16<L1, IO16>(cbuf + j * (((32 * (2 * L1 + 1) / (IO16 ? 8 : 4)) | 1) * 4), g, xs, x);
-      run_paths<Slots, L1, IO16>(x, true, g, j, ch, whi_base, wlo_base, cBfoff, cMpad, y, a0, a1, a2);
+      // The first path of the next chunk (six tiles: 48 registers with the fp16 split) is requested behind this chunk's last
+      // compute and ahead of the staging copies: the wait the copies need anyway covers it, and it never shares the
+      // register file with a path at work.  Behind the last chunk: the first path of product #2 (two tiles; its weights do
+      // not depend on u), before the last compute.
+      constexpr bool LAST = CI + 1 == (int)sizeof...(L1S);
+      run_paths_ahead<Slots, L1, IO16>(x, true, ws1, ch, y, a0, a1, a2, wq, [&](auto& w) {
+        if constexpr (LAST) request_path<Slots2, 0, 0, IO16>(ws2, pr.chunks[0], w);
+      });
+      if constexpr (!LAST) {
+        request_path<Slots, Seq::at(CI + 1), 0, IO16>(ws1, chunks[CI + 1], wq);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       wave_sync_lds();
-      if (ci + 1 < nchunks) stage(ci + 1);
-      ++ci;
+      if constexpr (!LAST) {
+        if (CI + 1 < nchunks) stage(CI + 1);
+      }
     };
     for_each_index(process, std::make_index_sequence<sizeof...(L1S)>{});
     wait_vm0();
     wave_sync_lds();
 
+    // and again for the second half of the tile: the offsets derived from the first one would otherwise be kept (in scratch)
+    // across product #1 for the few places below that share them
+    int l2;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l2));
+    const int j2 = l2 & 15, g2 = l2 >> 4;
+    const PathSrc ws2b = path_src(whi2_base, wlo2_base, cBfoff2, cMpad2, g2, j2);
     // ---- u = gate(product #1) in place (the values the two-launch path stores), and the row scale ----
     // out irreps of plan 1: [32 scalars | 32 gates per gated degree | 32 x1o (| 32 x2e)]; the gate of channel c of degree l
     // is scalar channel 32 l + c: same lane and register of a0
@@ -772,23 +940,23 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
       const float* nrm0 = nrm + ocl[cOoff[0]];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float s = a0[q >> 2][0][q & 3] * nrm0[chan_of(g, q)];
+        const float s = a0[q >> 2][0][q & 3] * nrm0[chan_of(g2, q)];
         a0[q >> 2][0][q & 3] = s * sigmoid_(s);
       }
       const float* nv1 = nrm + ocl[cOoff[1]];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float gq = sigmoid_(a0[2 + (q >> 2)][0][q & 3] * nrm0[32 + chan_of(g, q)]);
+        const float gq = sigmoid_(a0[2 + (q >> 2)][0][q & 3] * nrm0[32 + chan_of(g2, q)]);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) a1[q >> 2][c][q & 3] = (gq * a1[q >> 2][c][q & 3]) * nv1[3 * chan_of(g, q) + c];
+        for (int c = 0; c < 3; ++c) a1[q >> 2][c][q & 3] = (gq * a1[q >> 2][c][q & 3]) * nv1[3 * chan_of(g2, q) + c];
       }
       if constexpr (NT2 > 0) {
         const float* nv2 = nrm + ocl[cOoff[2]];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          const float gq = sigmoid_(a0[4 + (q >> 2)][0][q & 3] * nrm0[64 + chan_of(g, q)]);
+          const float gq = sigmoid_(a0[4 + (q >> 2)][0][q & 3] * nrm0[64 + chan_of(g2, q)]);
 #pragma unroll
-          for (int c = 0; c < 5; ++c) a2[q >> 2][c][q & 3] = (gq * a2[q >> 2][c][q & 3]) * nv2[5 * chan_of(g, q) + c];
+          for (int c = 0; c < 5; ++c) a2[q >> 2][c][q & 3] = (gq * a2[q >> 2][c][q & 3]) * nv2[5 * chan_of(g2, q) + c];
         }
       }
     }
@@ -805,9 +973,9 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
           for (int c = 0; c < 5; ++c) m = fmax_finite(m, a2[q >> 2][c][q & 3]);
         }
       }
-      // the row's four k groups (lanes j, j + 16, j + 32, j + 48)
-      m = fmaxf(m, __shfl_xor(m, 16, 64));
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      // the row's four k groups (lanes j2, j2 + 16, j2 + 32, j2 + 48)
+      m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((l2 ^ 16) << 2, __builtin_bit_cast(int, m))));
+      m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((l2 ^ 32) << 2, __builtin_bit_cast(int, m))));
       srow = pow2_scale_from_bits(__builtin_bit_cast(uint32_t, m), kPairTarget);
       isrow = 1.0f / srow;
     }
@@ -824,40 +992,48 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
     for (int t = 0; t < (NT2 > 0 ? 2 : 1); ++t)
 #pragma unroll
       for (int c = 0; c < 5; ++c) b2[t][c] = f32x4{0, 0, 0, 0};
-    // degree L of u into the chunk buffer in the layout of a staged chunk of that degree: row j, channel-major, the row
+    // degree L of u into the chunk buffer in the layout of a staged chunk of that degree: row j2, channel-major, the row
     // stride load_x16 expects (fp32: 32 D + 4 floats; bf16: 8 ((32 D / 8) | 1) halves)
-    auto put = [&](auto dtag, auto val) {
+    auto put = [&](auto dtag, float* ub, auto val) {
       constexpr int D = decltype(dtag)::value;
       if constexpr (IO16) {
-        uint16_t* o16 = reinterpret_cast<uint16_t*>(cbuf) + j * (8 * (((32 * D) / 8) | 1));
+        uint16_t* o16 = reinterpret_cast<uint16_t*>(ub) + j2 * (8 * (((32 * D) / 8) | 1));
 #pragma unroll
         for (int q = 0; q < 8; ++q)
 #pragma unroll
-          for (int c = 0; c < D; ++c) o16[D * chan_of(g, q) + c] = __builtin_bit_cast(uint16_t, (__bf16)val(q, c));
+          for (int c = 0; c < D; ++c) o16[D * chan_of(g2, q) + c] = __builtin_bit_cast(uint16_t, (__bf16)val(q, c));
       } else {
 #pragma unroll
         for (int q = 0; q < 8; ++q)
 #pragma unroll
-          for (int c = 0; c < D; ++c) cbuf[j * (32 * D + 4) + D * chan_of(g, q) + c] = val(q, c) * srow;
+          for (int c = 0; c < D; ++c) ub[j2 * (32 * D + 4) + D * chan_of(g2, q) + c] = val(q, c) * srow;
       }
-      wave_sync_lds();
     };
     // plan 2's chunk of degree L1 (same path order as tp_fwd_mfma_r16_kernel: bit-identical sums in bf16)
-    auto mul2 = [&](auto ltag) {
+    auto mul2 = [&](auto ltag, const float* ub) {
       constexpr int L1 = decltype(ltag)::value;
       const FChunk ch = pr.chunks[L1];
       float x[8][2 * L1 + 1];
-      load_x16<L1, IO16>(cbuf + j * (((32 * (2 * L1 + 1) / (IO16 ? 8 : 4)) | 1) * 4), g, 1.0f, x);
-      run_paths<Slots2, L1, IO16>(x, true, g, j, ch, whi2_base, wlo2_base, cBfoff2, cMpad2, y, b0, b1, b2);
+      load_x16<L1, IO16>(ub + j2 * (((32 * (2 * L1 + 1) / (IO16 ? 8 : 4)) | 1) * 4), g2, 1.0f, x);
+      run_paths_ahead<Slots2, L1, IO16>(x, true, ws2b, ch, y, b0, b1, b2, wq, [&](auto& w) {
+        if constexpr (L1 + 1 < NU) request_path<Slots2, L1 + 1, 0, IO16>(ws2b, pr.chunks[L1 + 1], w);
+      });
       wave_sync_lds();
     };
-    put(I1{}, [&](int q, int) { return a0[q >> 2][0][q & 3]; });
-    mul2(I0{});
-    put(I3{}, [&](int q, int c) { return a1[q >> 2][c][q & 3]; });
-    mul2(I1{});
+    // degrees 0 and 1 of u are parked side by side (16 x 36 + 16 x 100 dwords of the chunk buffer's 16 x 164) as soon as
+    // they are gated, so that their 32 registers are free while product #2's 72 accumulators fill; degree 2 takes the
+    // buffer when both have been read.  Product #2 consumes the degrees in the order 0, 1, 2 as before.
+    float* const u1buf = cbuf + 16 * (32 + 4);
+    static_assert(16 * (32 + 4) + 16 * (96 + 4) <= CHUNK && (16 * (32 + 4)) % 4 == 0, "u degrees 0 and 1 share the chunk buffer");
+    put(I1{}, cbuf, [&](int q, int) { return a0[q >> 2][0][q & 3]; });
+    put(I3{}, u1buf, [&](int q, int c) { return a1[q >> 2][c][q & 3]; });
+    wave_sync_lds();
+    mul2(I0{}, cbuf);
+    mul2(I1{}, u1buf);
     if constexpr (NT2 > 0) {
-      put(I5{}, [&](int q, int c) { return a2[q >> 2][c][q & 3]; });
-      mul2(I2{});
+      put(I5{}, cbuf, [&](int q, int c) { return a2[q >> 2][c][q & 3]; });
+      wave_sync_lds();
+      mul2(I2{}, cbuf);
     }
 
     // ---- epilogue of product #2: transpose through the chunk buffer, norm, residual, store, running max ----
@@ -875,7 +1051,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
 #pragma unroll
       for (int q = 0; q < 8; ++q)
 #pragma unroll
-        for (int c = 0; c < D; ++c) ot[j * TS + D * chan_of(g, q) + c] = val(q, c);
+        for (int c = 0; c < D; ++c) ot[j2 * TS + D * chan_of(g2, q) + c] = val(q, c);
       wave_sync_lds();
       if (vec) {
         constexpr uint32_t INV = (65536 + UPR - 1) / UPR;
@@ -884,7 +1060,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
         const uint32_t ldo32 = (uint32_t)ldo;
 #pragma unroll 2
         for (int it = 0; it < UPR / 4; ++it) {   // 16 * UPR units / 64 lanes
-          const uint32_t u = it * 64 + lane;
+          const uint32_t u = it * 64 + l2;
           const uint32_t row = __umul24(u, INV) >> 16, un = u - __umul24(row, UPR);
           const uint32_t lc0 = un * 4;
           float4 v = *reinterpret_cast<const float4*>(ot + __umul24(row, TS) + un * 4);
@@ -916,7 +1092,7 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
           }
         }
       } else {
-        for (int lc = lane; lc < 32 * D; lc += 64) {
+        for (int lc = l2; lc < 32 * D; lc += 64) {
           if (lc >= width) continue;
           const int64_t c0 = row0 * ldo + col(lc);
           const float nv = nrm2[col(lc)];
@@ -944,7 +1120,9 @@ __global__ __launch_bounds__(256, 2) void tp_update_pair_r16_kernel(SegArgs segs
     emit(I3{}, 1, [&](int q, int c) { return b1[q >> 2][c][q & 3] * isrow; });
     if constexpr (NT2 > 0) emit(I5{}, 2, [&](int q, int c) { return b2[q >> 2][c][q & 3] * isrow; });
   }
-  amax_finish(segs, amax, lane);
+  int le;  // regenerated: the kernel-level lane id would be carried through the tile loop in scratch
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(le));
+  amax_finish(segs, amax, le);
 }
 
 // ---------------------------------------------------------------------------------------------------
