@@ -612,6 +612,45 @@ int e3_gate_blocks_backward(const float* in, int64_t ld_in, const float* g_out, 
 int e3_segment_sum_backward(const float* g_agg, int64_t ld_gagg, const int32_t* rowptr, int64_t N, int D, float* g_msg,
                             int64_t ld_gmsg, void* stream);
 
+/* =================================================================================================
+ * Smooth cutoff envelope (fp32): the weight of an edge in the aggregation of an energy model, so that the energy is a
+ * twice continuously differentiable function of the positions when a pair crosses the cutoff r_c.  Polynomial envelope with
+ * an integer 2 <= p <= 16 (6 is the usual choice):
+ *   x        = min(fl(d * fl(1 / r_c)), 1)
+ *   u_p(x)   = (1 - x)^3 * sum_{k=0}^{p-1} C(k+2, 2) x^k          (the sum by Horner from k = p-1 down)
+ *   du/dd    = -(p (p+1) (p+2) / 2) * x^(p-1) * (1 - x)^2 / r_c
+ * This is the DimeNet polynomial 1 - (p+1)(p+2)/2 x^p + p(p+2) x^(p+1) - p(p+1)/2 x^(p+2) in a form without cancellation
+ * (the expanded form loses most of its digits near x = 1 and is not evaluated).  u(0) = 1; u = u' = u'' = 0 at x = 1;
+ * du/dd = 0 at d = 0.  Every d >= r_c gives w = 0 and g_d = 0 EXACTLY (a compare on d, not the rounding of x), so a graph
+ * built with a skin (r_c + skin) gives the energy of the graph built at r_c.  A NaN d gives a NaN w.
+ *   e3_cutoff_envelope          : w[e] = u_p(x(edge_d[e]))
+ *   e3_cutoff_envelope_backward : g_d[e] = g_w[e] * du/dd(edge_d[e])
+ * E3_ERR_INVALID_ARG before any launch for p outside [2, 16], r_c not finite or <= 0 (or 1 / r_c not finite) and E < 0;
+ * E = 0 returns E3_OK.
+ *
+ * Weighted segment sum: the aggregation with the envelope, and its backward.  Rows = CSR rows of the graph (dst nodes),
+ * D columns, row strides in elements.
+ *   e3_segment_sum_weighted          : agg[i] = sum over CSR row i of w[e] * msg[e], edges in row order, one
+ *                                      fmaf(w, m, acc) per element and edge from acc = 0.  Bit-equal from run to run; with
+ *                                      every w = 1 bit-equal to e3_segment_sum.  Rows without edges are zero.
+ *   e3_segment_sum_weighted_backward : g_msg[e] = w[e] * g_agg[dst(e)] (one rounding per element);
+ *                                      g_w[e] = <msg[e], g_agg[dst(e)]> over the D columns (g_w may be NULL: msg is then
+ *                                      not read and may be NULL): per lane over its columns in column order, then a
+ *                                      shuffle butterfly over the 64 lanes -- a fixed order, no atomics: bit-equal from
+ *                                      run to run.
+ * 16-byte loads and stores per lane when D, every stride and every base pointer is a multiple of 4 elements / 16 bytes,
+ * 4-byte ones otherwise (same sums, same order).  E3_ERR_INVALID_ARG before any launch for N < 0, D <= 0 or a stride
+ * below D; N = 0 returns E3_OK.
+ * ================================================================================================= */
+int e3_cutoff_envelope(const float* edge_d, int64_t E, float r_c, int p, float* w, void* stream);
+int e3_cutoff_envelope_backward(const float* edge_d, const float* g_w, int64_t E, float r_c, int p, float* g_d,
+                                void* stream);
+int e3_segment_sum_weighted(const float* msg, int64_t ld_msg, const float* w, const int32_t* rowptr, int64_t N, int D,
+                            float* agg, int64_t ld_agg, void* stream);
+int e3_segment_sum_weighted_backward(const float* g_agg, int64_t ld_gagg, const float* msg, int64_t ld_msg, const float* w,
+                                     const int32_t* rowptr, int64_t N, int D, float* g_msg, int64_t ld_gmsg, float* g_w,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,13 @@ SIGNATURES = {
     "e3_edge_geometry_backward_strained": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ctypes.c_float),
                                                    c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_void_p, c_int64, c_void_p]),
+    # smooth cutoff envelope (r_c = float, p = int) and the weighted segment-sum pair
+    "e3_cutoff_envelope": (c_int, [c_void_p, c_int64, ctypes.c_float, c_int, c_void_p, c_void_p]),
+    "e3_cutoff_envelope_backward": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_float, c_int, c_void_p, c_void_p]),
+    "e3_segment_sum_weighted": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                        c_void_p]),
+    "e3_segment_sum_weighted_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
+                                                 c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

@@ -54,7 +54,23 @@ def batched_radius_graph(pos: torch.Tensor, batch: torch.Tensor, r: float):
     return dataclasses.replace(g, pos4=pos4), batch[perm]
 
 
-def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure):
+def _skin_radius(net, r: float, skin: float) -> float:
+    """The graph radius r + skin of a forward.  A skin needs the envelope (ValueError without one): only an enveloped model
+    gives an edge beyond r no share in the energy."""
+    if skin != 0.0 and net.envelope is None:
+        raise ValueError("skin= needs a model built with envelope=: without the envelope the edges between r and r + skin "
+                         "would change the energy")
+    if not skin >= 0.0:
+        raise ValueError(f"skin must be >= 0, got {skin}")
+    return r if skin == 0.0 else float(r) + float(skin)
+
+
+def _cutoff_kw(net, r: float) -> dict:
+    """cutoff= of the net's forward: the envelope's radius r of an enveloped model, nothing otherwise."""
+    return {} if net.envelope is None else {"cutoff": float(r)}
+
+
+def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure, cutoff_kw=None):
     """Energy of ``net``'s scalar node readout summed per segment (``seg`` [N] graph order, ``n_seg`` segments; ``seg``
     None: the 0-d total), and from ONE backward pass through the differentiable chain dE/dpos_g [N,3] (``forces``) and
     dE/deps [n_strain,3,3] at a zero per-structure strain (``n_strain`` > 0; ``structure`` [N] graph order, None = one
@@ -64,7 +80,7 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
         p = pos_g.detach().float().requires_grad_(forces)
         eps = torch.zeros((n_strain, 3, 3), dtype=torch.float32, device=p.device, requires_grad=True) if n_strain else None
         geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p, strain=eps, structure=structure)  # differentiable Y, d, A
-        e_node = net(x_g, g, geometry=geometry)
+        e_node = net(x_g, g, geometry=geometry, **(cutoff_kw or {}))
         if seg is None:
             energy = e_node[:, 0].sum()
         else:
@@ -77,25 +93,32 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
 
 
 class BatchedEnergyModel(nn.Module):
-    """SEGNN with a scalar node readout summed per molecule: energies [n_mol]."""
+    """SEGNN with a scalar node readout summed per molecule: energies [n_mol].  ``envelope`` (the exponent p, e.g. 6;
+    ``SEGNN(envelope=)``): every pair is weighted by a smooth cutoff envelope of radius ``r``, so the energy is a smooth
+    function of the positions and forces / virials are its derivatives also where a pair crosses the cutoff."""
 
-    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2):
+    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2,
+                 envelope: int | None = None):
         super().__init__()
-        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax)
+        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, forces: bool = False,
-                virial: bool = False):
+                virial: bool = False, skin: float = 0.0):
         """-> energies [n_mol]; with ``forces=True``: (energies, forces [N,3] = -dE/dpos in the caller's atom order);
         with ``virial=True`` the per-molecule virials W [n_mol,3,3] = -dE/deps (zero strain per molecule, not
-        symmetrised) come last: (energies, forces, W) or (energies, W)."""
-        g, mol = batched_radius_graph(pos, batch, r)
+        symmetrised) come last: (energies, forces, W) or (energies, W).
+
+        ``skin`` (enveloped models only): the graph is built at ``r + skin`` while the envelope's radius stays ``r``; the
+        outputs are those of ``skin = 0`` up to rounding."""
+        g, mol = batched_radius_graph(pos, batch, _skin_radius(self.net, r, skin))
+        cut = _cutoff_kw(self.net, r)
         n_mol = int(batch.max().item()) + 1 if batch.numel() else 0
         perm = g.perm.long()
         if not forces and not virial:
-            e_node = self.net(x[perm], g)
+            e_node = self.net(x[perm], g, **cut)
             return torch.zeros(n_mol, dtype=e_node.dtype, device=e_node.device).index_add_(0, mol, e_node[:, 0])
         energy, gpos, geps = _energy_and_gradients(self.net, x[perm], g, pos[perm], mol, n_mol, forces,
-                                                   n_mol if virial else 0, mol if virial else None)
+                                                   n_mol if virial else 0, mol if virial else None, cut)
         out = [energy]
         if forces:
             f = torch.empty_like(gpos)
@@ -110,22 +133,30 @@ class PeriodicEnergyModel(nn.Module):
     """SEGNN with a scalar node readout summed over a periodic (or partly periodic) orthorhombic box, or over a general
     (triclinic) cell: the energy, and on request forces, the virial and the stress of the box (conventions:
     include/e3gnn.h, e3_edge_geometry_strained).  The graph is built inside ``forward`` (``radius_graph(..., periodic=)``
-    or ``radius_graph(..., cell=)``)."""
+    or ``radius_graph(..., cell=)``).  ``envelope`` (the exponent p, e.g. 6; ``SEGNN(envelope=)``): every pair is weighted
+    by a smooth cutoff envelope of radius ``r``; the energy is then a smooth function of the positions and of the strain, and
+    forces and stress are its derivatives also where a pair crosses the cutoff (what a relaxation or an MD run needs)."""
 
-    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2):
+    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2,
+                 envelope: int | None = None):
         super().__init__()
-        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax)
+        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, forces: bool = False,
-                virial: bool = False, stress: bool = False, cell=None, origin=None):
+                virial: bool = False, stress: bool = False, cell=None, origin=None, skin: float = 0.0):
         """x [N, in_dim], pos [N,3] (caller order; coordinates on periodic axes may be unwrapped).  -> the 0-d energy,
         then whichever of forces [N,3] (= -dE/dpos, caller order), virial W [3,3] (= -dE/deps at eps = 0, not
         symmetrised) and stress [3,3] (= (1/V) dE/deps = -W/V, V = L_x L_y L_z) were requested, in that order; the
         energy alone when none was.  ``stress=True`` needs all three axes periodic (ValueError otherwise).
 
         ``cell`` (3x3, rows = lattice vectors) with ``origin``: a general cell instead of ``lo`` / ``hi`` / ``periodic``
-        (``radius_graph(cell=)``; always periodic on all three directions); the stress uses V = |det cell|."""
+        (``radius_graph(cell=)``; always periodic on all three directions); the stress uses V = |det cell|.
+
+        ``skin`` (enveloped models only): the graph is built at ``r + skin`` -- the periodic and cell cutoff checks apply
+        to that radius -- while the envelope's radius stays ``r``; the outputs are those of ``skin = 0`` up to rounding."""
         from .radius_graph import periodic_mask
+        r_env, r = r, _skin_radius(self.net, r, skin)
+        cut = _cutoff_kw(self.net, r_env)
         if cell is not None:
             if lo is not None or hi is not None or periodic is not True:
                 raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
@@ -136,9 +167,9 @@ class PeriodicEnergyModel(nn.Module):
             g = radius_graph(pos, r, lo, hi, periodic=periodic)
         perm = g.perm.long()
         if not (forces or virial or stress):
-            return self.net(x[perm], g)[:, 0].sum()
+            return self.net(x[perm], g, **cut)[:, 0].sum()
         energy, gpos, geps = _energy_and_gradients(self.net, x[perm], g, pos[perm], None, 1, forces,
-                                                   1 if (virial or stress) else 0, None)
+                                                   1 if (virial or stress) else 0, None, cut)
         out = [energy]
         if forces:
             f = torch.empty_like(gpos)

@@ -291,16 +291,128 @@ def _segment_sum_raw(msg, g):
     return agg
 
 
-def segment_sum(msg: torch.Tensor, g: RadiusGraph) -> torch.Tensor:
+def _segment_sum_weighted_raw(msg, w, g):
+    N, D = g.rowptr.numel() - 1, msg.shape[1]
+    agg = torch.empty((N, D), dtype=torch.float32, device=msg.device)
+    with torch.cuda.device(msg.device):
+        _lib.check(_lib.load().e3_segment_sum_weighted(msg.data_ptr(), msg.stride(0), w.data_ptr(), g.rowptr.data_ptr(), N,
+                                                       D, agg.data_ptr(), agg.stride(0), _stream(msg)),
+                   "e3_segment_sum_weighted")
+    return agg
+
+
+class _SegmentSumWeightedFn(torch.autograd.Function):
+    """agg = sum_e w_e msg_e per CSR row; backward = e3_segment_sum_weighted_backward (g_msg, and g_w when w needs it)."""
+
+    @staticmethod
+    def forward(ctx, msg, w, g):
+        ctx.g = g
+        ctx.save_for_backward(msg, w)
+        return _segment_sum_weighted_raw(msg, w, g)
+
+    @staticmethod
+    def backward(ctx, ga):
+        msg, w = ctx.saved_tensors
+        g = ctx.g
+        ga = ga.contiguous()
+        N, D = ga.shape
+        gm = torch.empty((g.num_edges, D), dtype=torch.float32, device=ga.device)
+        gw = torch.empty(g.num_edges, dtype=torch.float32, device=ga.device) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(ga.device):
+            _lib.check(_lib.load().e3_segment_sum_weighted_backward(
+                ga.data_ptr(), ga.stride(0), msg.data_ptr(), msg.stride(0), w.data_ptr(), g.rowptr.data_ptr(), N, D,
+                gm.data_ptr(), max(gm.stride(0), D), gw.data_ptr() if gw is not None else None, _stream(ga)),
+                "e3_segment_sum_weighted_backward")
+        return gm, gw, None
+
+
+def segment_sum(msg: torch.Tensor, g: RadiusGraph, weight: torch.Tensor | None = None) -> torch.Tensor:
     """agg[i] = sum of msg rows of CSR row i (fixed order, reproducible); fp32 (differentiable), or bf16 storage with fp32
-    accumulation"""
+    accumulation.  ``weight`` [E] fp32 (an edge envelope, ``cutoff_envelope``): agg[i] = sum_e weight_e msg_e, in the same
+    fixed order (bit-equal to the unweighted sum at weight = 1), differentiable w.r.t. ``msg`` and ``weight``; fp32 only."""
     if not msg.is_cuda:
         raise RuntimeError("msg: ROCm tensor required (no CPU path)")
     if msg.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"segment_sum: float32 / bfloat16 required, got {msg.dtype}")
+    if weight is not None:
+        if msg.dtype != torch.float32:
+            raise RuntimeError("segment_sum(weight=): the envelope is fp32; bf16 storage has no weighted sum")
+        _check(weight, "weight")
+        if weight.dim() != 1 or weight.shape[0] != g.num_edges or msg.dim() != 2 or msg.shape[0] != g.num_edges:
+            raise ValueError(f"segment_sum(weight=): msg [E, D] and weight [E] with E = {g.num_edges} required, got "
+                             f"{tuple(msg.shape)} and {tuple(weight.shape)}")
+        if g.num_edges == 0:  # nothing to launch on: every row is empty
+            return torch.zeros((g.rowptr.numel() - 1, msg.shape[1]), dtype=torch.float32, device=msg.device)
+        if msg.stride(-1) != 1:
+            msg = msg.contiguous()
+        weight = weight.contiguous()
+        if _wants_grad(msg, weight):
+            return _SegmentSumWeightedFn.apply(msg, weight, g)
+        return _segment_sum_weighted_raw(msg, weight, g)
     if msg.dtype == torch.float32 and _wants_grad(msg):
         return _SegmentSumFn.apply(msg, g)
     return _segment_sum_raw(msg, g)
+
+
+ENVELOPE_P_RANGE = (2, 16)
+
+
+def _envelope_args(r_c, p):
+    """-> (float r_c, int p); ValueError for p outside [2, 16] or an r_c that is not a finite positive number."""
+    import math
+    if isinstance(p, bool) or int(p) != p or not ENVELOPE_P_RANGE[0] <= int(p) <= ENVELOPE_P_RANGE[1]:
+        raise ValueError(f"envelope exponent p must be an integer in [{ENVELOPE_P_RANGE[0]}, {ENVELOPE_P_RANGE[1]}], got {p!r}")
+    r_c = float(r_c)
+    if not (math.isfinite(r_c) and r_c > 0.0):
+        raise ValueError(f"envelope cutoff must be finite and > 0, got {r_c}")
+    return r_c, int(p)
+
+
+class _CutoffEnvelopeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d, r_c, p):
+        ctx.r_c, ctx.p = r_c, p
+        ctx.save_for_backward(d)
+        return _cutoff_envelope_raw(d, r_c, p)
+
+    @staticmethod
+    def backward(ctx, gw):
+        (d,) = ctx.saved_tensors
+        gw = gw.contiguous()
+        gd = torch.empty_like(d)
+        with torch.cuda.device(d.device):
+            _lib.check(_lib.load().e3_cutoff_envelope_backward(d.data_ptr(), gw.data_ptr(), d.numel(), ctx.r_c, ctx.p,
+                                                               gd.data_ptr(), _stream(d)), "e3_cutoff_envelope_backward")
+        return gd, None, None
+
+
+def _cutoff_envelope_raw(d, r_c, p):
+    w = torch.empty_like(d)
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().e3_cutoff_envelope(d.data_ptr(), d.numel(), r_c, p, w.data_ptr(), _stream(d)),
+                   "e3_cutoff_envelope")
+    return w
+
+
+def cutoff_envelope(d: torch.Tensor, r_c: float, p: int = 6) -> torch.Tensor:
+    """Edge weights w [E] = u_p(d / r_c): the polynomial envelope of include/e3gnn.h (e3_cutoff_envelope), 1 at d = 0 and
+    exactly 0 for every d >= r_c, with two vanishing derivatives at r_c.  Differentiable w.r.t. ``d``."""
+    r_c, p = _envelope_args(r_c, p)
+    _check(d, "d")
+    if d.dim() != 1:
+        raise ValueError(f"cutoff_envelope: d must be [E], got {tuple(d.shape)}")
+    d = d.contiguous()
+    if _wants_grad(d):
+        return _CutoffEnvelopeFn.apply(d, r_c, p)
+    return _cutoff_envelope_raw(d, r_c, p)
+
+
+def enveloped_node_attr(Y: torch.Tensor, w: torch.Tensor, g: RadiusGraph) -> torch.Tensor:
+    """Node attribute of an enveloped model, A [N, (lmax+1)^2] = [1, S_1.. / (1 + S_0)] with S = sum_e w_e Y_e per row
+    (Y_e[0] = 1, so S_0 = sum_e w_e): a smooth, bounded stand-in for the mean of Y -- an edge at the cutoff has no share in
+    it, an isolated node has [1, 0, ...].  Differentiable w.r.t. ``Y`` and ``w``."""
+    S = segment_sum(Y, g, weight=w)
+    return torch.cat([torch.ones_like(S[:, :1]), S[:, 1:] / (1.0 + S[:, :1])], 1)
 
 
 def _gate_blocks_raw(x, ns, blocks):

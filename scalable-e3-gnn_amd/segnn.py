@@ -84,9 +84,18 @@ class SEGNNLayer(nn.Module):
             f = self._fused_upd_ok = bool(self.upd1.fused_supported(True))
         return f
 
-    def forward(self, h, g: RadiusGraph, Y, d, A, h_scale=None, halo=None, split=None):
+    def forward(self, h, g: RadiusGraph, Y, d, A, h_scale=None, halo=None, split=None, w=None):
         """-> (h_next, operand scale of h_next | None).  ``halo`` / ``split`` (sharding.Halo / SplitGraph): the layer
-        refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges."""
+        refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges.
+
+        ``w`` [E] (``ops.cutoff_envelope``): the messages are summed with these edge weights, a_i = sum_e w_e m_e
+        (``ops.segment_sum(weight=)``).  The one-launch message kernel and the scatter epilogue of message TP #2 sum with
+        weight 1 and are not used; fp32 only, not sharded."""
+        if w is not None:
+            if halo is not None or split is not None:
+                raise NotImplementedError("the cutoff envelope is not implemented on the sharded path (halo / split)")
+            if h.dtype != torch.float32:
+                raise RuntimeError("the cutoff envelope is fp32: bf16 storage has no weighted aggregation")
         if (halo is not None or split is not None) and (g.box is not None or g.cell is not None):
             raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
                                       "ghost images of GridHalo(..., periodic=...)")
@@ -104,7 +113,7 @@ class SEGNNLayer(nn.Module):
         r16 = self.fused and inference and self.fused_available()   # per-TP fused kernels (gather + TP + gate)
         # ---- message function -> aggregated messages a [N, width] ----
         one_launch = (self.fused and inference and self.fuse_message and self.fuse_scatter and self._msg is not None and
-                      self._msg.supports(h.dtype))
+                      self._msg.supports(h.dtype) and w is None)
         r16u = self.fused and inference and (r16 or (one_launch and self.fused_update_available()))   # update product
         if h.dtype == torch.bfloat16 and not ((one_launch or r16) and r16u):
             raise RuntimeError("bf16 storage needs the fused MFMA kernels (inference; hidden 32, or 64 at l_max = 2)")
@@ -143,16 +152,16 @@ class SEGNNLayer(nn.Module):
             m = self.msg1.forward_fused([(h, g.dst), (h, g.src), (d, None)], Y, gate=True,
                                         in_scale=ops.pow2_scale([h, d]) if f32 else None)
             a = None
-            if self.fuse_scatter:  # segment-sum in the epilogue of message TP #2 where the library has that kernel
+            if self.fuse_scatter and w is None:  # segment-sum in the epilogue of message TP #2 where the library has that kernel
                 a = self.msg2.forward_fused([(m, None)], Y, gate=True, scatter=(g.dst, g.rowptr.numel() - 1))
             if a is None:
                 m = self.msg2.forward_fused([(m, None)], Y, gate=True)
-                a = ops.segment_sum(m, g)
+                a = ops.segment_sum(m, g, weight=w)
         else:
             m = ops.gather_concat(h, g, d)
             m = self._gate(self.msg1(m, Y))
             m = self._gate(self.msg2(m, Y))
-            a = ops.segment_sum(m, g)
+            a = ops.segment_sum(m, g, weight=w)
         # ---- node update ----
         if r16u:
             # operand scale of [h | a]: h's is known (the previous layer returned it), so only `a` is scanned
@@ -188,18 +197,28 @@ def _needs_grad(mod: nn.Module, *tensors) -> bool:
 
 
 class SEGNN(nn.Module):
-    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, out_irreps="1x1o", num_layers: int = 4, lmax: int = 1):
+    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, out_irreps="1x1o", num_layers: int = 4, lmax: int = 1,
+                 envelope: int | None = None):
+        """``envelope``: the exponent p of the polynomial cutoff envelope (``ops.cutoff_envelope``; 6 is the usual choice),
+        None = no envelope.  With it every message is weighted by u_p(d / cutoff) in the aggregation and the node attribute
+        is the enveloped one (``ops.enveloped_node_attr``), so the output is a smooth function of the positions across the
+        cutoff; ``forward`` then needs ``cutoff=``.  It adds no parameter and no buffer."""
         super().__init__()
         assert lmax in (1, 2)
         self.hidden, self.lmax = hidden, lmax
+        self.envelope = None if envelope is None else ops._envelope_args(1.0, envelope)[1]
         hid, _ = _hidden_irreps(hidden, lmax)
         self.in_irreps, self.out_irreps = Irreps(in_irreps), Irreps(out_irreps)
         self.embed = _make_tp(self.in_irreps, hid, lmax)
         self.layers = nn.ModuleList([SEGNNLayer(hidden, lmax) for _ in range(num_layers)])
         self.readout = _make_tp(hid, self.out_irreps, lmax)
 
-    def forward(self, x: torch.Tensor, g: RadiusGraph, geometry=None, halo=None, split=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, g: RadiusGraph, geometry=None, halo=None, split=None,
+                cutoff: float | None = None) -> torch.Tensor:
         """x [N, in_dim] node features in the graph's (Morton) order -> [N, out_dim] in the same order.
+
+        ``cutoff``: the envelope's radius r_c of a model built with ``envelope=`` (required then, a ValueError without
+        one).  The graph may be built at a larger radius (a skin): an edge with d >= cutoff contributes exactly zero.
 
         ``halo`` (a ``sharding.Halo``): when the cloud is spatially sharded, ghost rows of ``h`` are
         refreshed from their owners before every message-passing layer; only owned rows of the result
@@ -208,6 +227,11 @@ class SEGNN(nn.Module):
         if (halo is not None or split is not None) and (g.box is not None or g.cell is not None):
             raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
                                       "ghost images of GridHalo(..., periodic=...)")
+        if (cutoff is None) != (self.envelope is None):
+            raise ValueError("cutoff= is the radius of the envelope: a model built with envelope= needs it, and a model "
+                             "without an envelope takes none")
+        if self.envelope is not None:
+            return self._forward_enveloped(x, g, geometry, halo, split, cutoff)
         if split is not None:
             g = split.graph
         if geometry is not None:
@@ -234,3 +258,22 @@ class SEGNN(nn.Module):
                                "when the layer's operand scale was fixed (fp16-split operands would overflow); run the layer "
                                "without `split` (blocking exchange) for such inputs")
         return out
+
+    def _forward_enveloped(self, x, g, geometry, halo, split, cutoff):
+        """The forward with the cutoff envelope: w = u_p(d / cutoff) once from the edge lengths, the enveloped node
+        attribute in place of the mean, and w on every layer's aggregation."""
+        if halo is not None or split is not None:
+            raise NotImplementedError("the cutoff envelope is not implemented on the sharded path (halo / split)")
+        if x.dtype != torch.float32:
+            raise RuntimeError("the cutoff envelope is fp32: bf16 storage has no weighted aggregation")
+        if geometry is not None:
+            Y, d, _ = geometry
+        else:
+            Y, d, _ = ops.edge_geometry(g, lmax=self.lmax, want_node_attr=False, want_edge=True)
+        w = ops.cutoff_envelope(d, cutoff, self.envelope)
+        A = ops.enveloped_node_attr(Y, w, g)
+        h = self.embed(x, A)
+        sc = None
+        for layer in self.layers:
+            h, sc = layer(h, g, Y, d, A, sc, w=w)
+        return self.readout(h, A)
