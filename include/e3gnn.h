@@ -651,6 +651,51 @@ int e3_segment_sum_weighted_backward(const float* g_agg, int64_t ld_gagg, const 
                                      const int32_t* rowptr, int64_t N, int D, float* g_msg, int64_t ld_gmsg, float* g_w,
                                      void* stream);
 
+/* =================================================================================================
+ * Verlet neighbour list (neighbor_list.NeighborList): a graph of e3_rg_* built once at the radius r + skin is cut down, on
+ * the device, to the pairs within r at the current positions -- an ordinary CSR graph at radius r in the stored graph's node
+ * order -- and the largest displacement since the build comes back with it.  One entry per periodicity mode (box[3] as in
+ * e3_edge_geometry_pbc, cell[9] as in e3_rg_sort_count_cell).
+ *   inputs  : pos [N,3] fp32, the CURRENT positions in the caller's order (periodic coordinates may be unwrapped);
+ *             perm [N], ref_pos4 [N,4], rowptr [N+1], src [E]: the stored graph (ref_pos4 = its sorted_pos4).
+ *   outputs : pos4_out [N,4] = (pos[perm[i]], 0);  rowptr_out [N+1], src_out / dst_out (room for E each: the pruned count
+ *             can only be smaller, so no host read sizes them);  stats [2] uint32 (device):
+ *             stats[0] = the fp32 bits, sign cleared, of max_i d2_i;  stats[1] = rowptr_out[N], the pruned edge count.
+ * Every fp32 operation is rounded on its own (no FMA contraction):
+ *   displacement : D_i = the minimum image of fl(pos[perm[i]] - ref_i) in the rint form of `rel` above (per periodic axis
+ *             fl(d - fl(L rintf(fl(d invL)))); in a cell shift(d, rintf(frac(d))); the identity on an open axis or box), so
+ *             re-wrapping the positions between two calls moves nothing.  d2_i = fl(fl(fl(Dx Dx) + fl(Dy Dy)) + fl(Dz Dz)).
+ *             Non-negative floats order as their unsigned bits and a NaN pattern orders above +inf: the maximum is taken on
+ *             the bits (per wave, per block, then one atomic max per block), and a non-finite position reads as larger
+ *             than every threshold.  stats is zeroed on the stream inside the entry.
+ *   edge    : edge e = (src_e -> row i) of the stored graph is kept iff d2 <= fl(r r), with rel = the edge vector of the
+ *             geometry kernels at pos4_out[src_e], pos4_out[i] and d2 = fl(fl(fl(rx rx) + fl(ry ry)) + fl(rz rz)): the
+ *             builder's sum order.  In an open box at unchanged positions this is the builder's test as written (rel is
+ *             its dx negated, which is exact) and bit for bit its restatement; the builder's file is compiled with FMA
+ *             contraction and this one without, so the two compiled d2 may differ by an ulp for a pair that close to the
+ *             cutoff -- which the 2^-10 below covers.
+ *   order   : rows in the stored order; the kept src of a row keep their order (ascending); dst_out[e] = the row of e.
+ * The caller decides from stats[0] whether the stored graph still covers the cutoff.  With skin the margin the graph was
+ * built with and h = 0.5 skin (1 - 2^-10): while every d2_i < fl(h h), every pair within r now was within r + skin at the
+ * build, hence is in the stored graph, and the pruned graph is the radius graph at r.  The 2^-10 pays for the roundings of
+ * D_i, of rel and of the builder's dx -- together below 64 * 2^-24 X for coordinates (and box / cell extents) of magnitude
+ * at most X -- so the argument holds for X <= 2^8 skin.
+ * E3_ERR_INVALID_ARG before any launch for a NULL pointer (the node arrays may be NULL when N = 0, the edge arrays when
+ * E = 0), N + 1 or E outside int32, r not finite or <= 0, and a box / cell that e3_edge_geometry_pbc / _cell reject.
+ * N = 0 launches nothing and writes stats = {0, 0} and rowptr_out[0] = 0.  workspace = e3_nl_workspace_bytes(N) bytes
+ * (-1 for N outside int32).
+ * ================================================================================================= */
+int64_t e3_nl_workspace_bytes(int64_t N);
+int e3_nl_update(const float* pos, const int32_t* perm, const float* ref_pos4, const int32_t* rowptr, const int32_t* src,
+                 int64_t N, int64_t E, float r, float* pos4_out, int32_t* rowptr_out, int32_t* src_out, int32_t* dst_out,
+                 uint32_t* stats, void* workspace, void* stream);
+int e3_nl_update_pbc(const float* pos, const int32_t* perm, const float* ref_pos4, const int32_t* rowptr, const int32_t* src,
+                     int64_t N, int64_t E, float r, const float box[3], float* pos4_out, int32_t* rowptr_out,
+                     int32_t* src_out, int32_t* dst_out, uint32_t* stats, void* workspace, void* stream);
+int e3_nl_update_cell(const float* pos, const int32_t* perm, const float* ref_pos4, const int32_t* rowptr, const int32_t* src,
+                      int64_t N, int64_t E, float r, const float cell[9], float* pos4_out, int32_t* rowptr_out,
+                      int32_t* src_out, int32_t* dst_out, uint32_t* stats, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

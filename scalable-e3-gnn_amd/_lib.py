@@ -175,6 +175,14 @@ SIGNATURES = {
                                         c_void_p]),
     "e3_segment_sum_weighted_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
                                                  c_void_p, c_int64, c_void_p, c_void_p]),
+    # Verlet neighbour list: the stored graph pruned to r at the current positions (r = float)
+    "e3_nl_workspace_bytes": (c_int64, [c_int64]),
+    "e3_nl_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_float, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e3_nl_update_pbc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_float, Float3,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e3_nl_update_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_float, Float9,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

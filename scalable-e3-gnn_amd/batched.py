@@ -70,6 +70,20 @@ def _cutoff_kw(net, r: float) -> dict:
     return {} if net.envelope is None else {"cutoff": float(r)}
 
 
+def _neighbors_graph(neighbors, pos, r, skin, defaults: dict):
+    """The graph of a forward with ``neighbors=`` (a ``neighbor_list.NeighborList``): ``neighbors.update(pos)``.  The list
+    owns the radius, the skin and the box, so ``r`` must be the list's and every argument of ``defaults`` (name -> (value,
+    default)) must be left alone -- ``ValueError`` naming the argument otherwise."""
+    if float(r) != neighbors.r:
+        raise ValueError(f"r = {r} is not the radius of neighbors= ({neighbors.r})")
+    if skin != 0.0:
+        raise ValueError("skin= must stay 0 with neighbors=: the list has a skin of its own and returns the graph at r")
+    for name, (value, default) in defaults.items():
+        if value is not default:
+            raise ValueError(f"{name}= must be left at its default with neighbors=: the list holds the box it was made with")
+    return neighbors.update(pos)
+
+
 def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure, cutoff_kw=None):
     """Energy of ``net``'s scalar node readout summed per segment (``seg`` [N] graph order, ``n_seg`` segments; ``seg``
     None: the 0-d total), and from ONE backward pass through the differentiable chain dE/dpos_g [N,3] (``forces``) and
@@ -103,14 +117,28 @@ class BatchedEnergyModel(nn.Module):
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, forces: bool = False,
-                virial: bool = False, skin: float = 0.0):
+                virial: bool = False, skin: float = 0.0, neighbors=None):
         """-> energies [n_mol]; with ``forces=True``: (energies, forces [N,3] = -dE/dpos in the caller's atom order);
         with ``virial=True`` the per-molecule virials W [n_mol,3,3] = -dE/deps (zero strain per molecule, not
         symmetrised) come last: (energies, forces, W) or (energies, W).
 
         ``skin`` (enveloped models only): the graph is built at ``r + skin`` while the envelope's radius stays ``r``; the
-        outputs are those of ``skin = 0`` up to rounding."""
-        g, mol = batched_radius_graph(pos, batch, _skin_radius(self.net, r, skin))
+        outputs are those of ``skin = 0`` up to rounding.
+
+        ``neighbors`` (a ``NeighborList(r, skin, batch=batch)``): the graph is ``neighbors.update(pos)`` -- built at the
+        list's ``r + skin`` once, pruned to ``r`` on the device while no atom has moved half the skin -- for any model,
+        enveloped or not; ``skin`` stays 0 and ``batch`` must be the tensor the list was made with (compared when the
+        list rebuilds)."""
+        if neighbors is not None:
+            if neighbors.batch is None:
+                raise ValueError("neighbors= of a batched model must be a NeighborList made with batch=")
+            g = _neighbors_graph(neighbors, pos, r, skin, {})
+            if neighbors.rebuilt and not (neighbors.batch.shape == batch.shape and
+                                          torch.equal(neighbors.batch.to(batch.device).long(), batch.long())):
+                raise ValueError("batch= is not the tensor neighbors= was made with")
+            mol = neighbors.mol_of_node
+        else:
+            g, mol = batched_radius_graph(pos, batch, _skin_radius(self.net, r, skin))
         cut = _cutoff_kw(self.net, r)
         n_mol = int(batch.max().item()) + 1 if batch.numel() else 0
         perm = g.perm.long()
@@ -143,7 +171,7 @@ class PeriodicEnergyModel(nn.Module):
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, forces: bool = False,
-                virial: bool = False, stress: bool = False, cell=None, origin=None, skin: float = 0.0):
+                virial: bool = False, stress: bool = False, cell=None, origin=None, skin: float = 0.0, neighbors=None):
         """x [N, in_dim], pos [N,3] (caller order; coordinates on periodic axes may be unwrapped).  -> the 0-d energy,
         then whichever of forces [N,3] (= -dE/dpos, caller order), virial W [3,3] (= -dE/deps at eps = 0, not
         symmetrised) and stress [3,3] (= (1/V) dE/deps = -W/V, V = L_x L_y L_z) were requested, in that order; the
@@ -153,11 +181,21 @@ class PeriodicEnergyModel(nn.Module):
         (``radius_graph(cell=)``; always periodic on all three directions); the stress uses V = |det cell|.
 
         ``skin`` (enveloped models only): the graph is built at ``r + skin`` -- the periodic and cell cutoff checks apply
-        to that radius -- while the envelope's radius stays ``r``; the outputs are those of ``skin = 0`` up to rounding."""
+        to that radius -- while the envelope's radius stays ``r``; the outputs are those of ``skin = 0`` up to rounding.
+
+        ``neighbors`` (a ``NeighborList`` holding the box or cell): the graph is ``neighbors.update(pos)`` -- built at the
+        list's ``r + skin`` once, pruned to ``r`` on the device while no particle has moved half the skin -- for any
+        model, enveloped or not; ``lo`` / ``hi`` / ``periodic`` / ``cell`` / ``origin`` / ``skin`` then stay at their
+        defaults (ValueError otherwise) and ``stress=True`` needs a list periodic on all three axes."""
         from .radius_graph import periodic_mask
         r_env, r = r, _skin_radius(self.net, r, skin)
         cut = _cutoff_kw(self.net, r_env)
-        if cell is not None:
+        if neighbors is not None:
+            if stress and not neighbors.fully_periodic:  # from the list's box: refused before the list is touched
+                raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
+            g = _neighbors_graph(neighbors, pos, r, skin, {"lo": (lo, None), "hi": (hi, None), "periodic": (periodic, True),
+                                                          "cell": (cell, None), "origin": (origin, None)})
+        elif cell is not None:
             if lo is not None or hi is not None or periodic is not True:
                 raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
             g = radius_graph(pos, r, cell=cell, origin=origin)
