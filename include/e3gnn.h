@@ -472,10 +472,24 @@ int e3_tp_forward_fused_scatter(const e3_tp_plan* plan, const e3_tp_segment* seg
  *   weights: w1[l3] / w2[l3] = the class matrices of TP1 / TP2 for output degree l3 (0e, 1o, 2e), row order and shapes
  *            as e3_tp_weight_shape reports for those irreps (e3_msg_weight_shape returns the same numbers);
  *            n1 / n2 = their norm buffers (length M, 3 M, 5 M) or NULL for 1.
- *   premix : N * e3_msg_premix_floats_per_node() floats written by e3_msg_premix (W_dst h per node: the dst half of TP1
- *            does not depend on the edge, so it is contracted once per NODE and enters the edge kernel as the MFMA
- *            accumulator's initial value; behind the N table rows: max |h[n] * in_scale| per node, from which the edge kernel
- *            bounds a row's messages); call e3_msg_premix(h) before e3_msg_forward on the same h and in_scale
+ *   premix : N * e3_msg_premix_floats_per_node() floats written by e3_msg_premix; call e3_msg_premix(h) before
+ *            e3_msg_forward on the same h and in_scale.  Three regions, in this order (e3_msg_premix_regions reports the
+ *            offsets; the entries take no size: N * e3_msg_premix_floats_per_node() floats are the caller's contract):
+ *              [N x UD floats]  the table W_dst h per node: the dst half of TP1 does not depend on the edge, so it is
+ *                               contracted once per NODE and enters the edge kernel as the MFMA accumulator's initial value
+ *              [N x S floats]   the pre-split rows, S = 32 (l_max + 1)^2 for plans whose fp32 edge kernel is the
+ *                               weights-stationary one (hidden = 32, l_max = 2), else S = 0: h[n] * in_scale as the fp16
+ *                               (hi, lo) B fragments that kernel gathers per edge instead of converting h[src].  Per node
+ *                               (l_max + 1)^2 fragments (component l^2 + a) of 128 bytes: 4 x 16 bytes of hi halves (k
+ *                               group g = 0 .. 3: 8 fp16, channels 4 g .. 4 g + 3 then 16 + 4 g .. 16 + 4 g + 3), then the
+ *                               4 x 16 bytes of lo halves; hi = rne16(x), lo = rne16(x - hi).  Written for fp32 storage only
+ *                               (bf16 storage leaves the region unused).
+ *              [N floats]       max |h[n] * in_scale| per node, from which the edge kernel bounds a row's messages
+ *            UD * 4 and S * 4 are multiples of 128, so every region of a 128-byte aligned buffer starts on a cache line
+ *            (recommended; 16-byte alignment is required).
+ *            Rows of h that change after e3_msg_premix and are only gathered as src rows afterwards (ghost rows after a halo
+ *            exchange): e3_msg_refresh_rows(rows[n_rows], int64 node ids) rewrites their pre-split row and row maximum
+ *            (maximum over the finite values); ids outside [0, N) are skipped.
  *   out    : [N, ld_out] fp32, columns [H | 3 H | 5 H]; zero-filled by the call unless accumulate != 0
  *   accumulate != 0: a second edge list for the SAME h rows of the dst nodes (e.g. the halo's boundary edges after the
  *            interior ones): out keeps its contents (premix is reused: it depends on dst rows only)
@@ -502,6 +516,10 @@ int e3_msg_pack_weights(e3_msg_plan* plan, const void* const w1[3], const void* 
                         const void* const w2[3], const void* const n2[3], int dtype, void* packed, void* stream);
 int e3_msg_premix(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const void* packed,
                   const float* in_scale, float* premix, int dtype, void* stream);
+int e3_msg_premix_regions(const e3_msg_plan* plan, int64_t N, int64_t* split_offset, int64_t* split_floats_per_node,
+                          int64_t* row_max_offset); /* offsets in floats; any output may be NULL */
+int e3_msg_refresh_rows(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const int64_t* rows, int64_t n_rows,
+                        const float* in_scale, float* premix, int dtype, void* stream);
 int e3_msg_forward(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const float* pos4,
                    const int32_t* src, const int32_t* dst, int64_t E, const void* packed, const float* in_scale,
                    const float* premix, float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block,

@@ -94,6 +94,9 @@ SIGNATURES = {
     "e3_msg_pack_weights": (c_int, [c_void_p, c_void_p * 3, c_void_p * 3, c_void_p * 3, c_void_p * 3, c_int, c_void_p,
                                     c_void_p]),
     "e3_msg_premix": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "e3_msg_premix_regions": (c_int, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "e3_msg_refresh_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                    c_void_p]),
     "e3_msg_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "e3_edge_geometry_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,

@@ -57,6 +57,26 @@ struct MsgGeom {
                                                     // transposed tile with row stride D + 4
 };
 
+// Pre-split feature rows (fp32 storage, H = 32): the B fragments of product #1 as the pre-mix launch leaves them per NODE, so
+// that the weights-stationary edge kernel gathers operands instead of converting h[src] once per edge.  A row is NC fragments
+// (component f = l * l + a) of 128 bytes = one cache line: the hi halves of the four k groups (4 x 16 bytes: k group g holds
+// the 8 fp16 of channels 4 g .. 4 g + 3, 16 + 4 g .. 16 + 4 g + 3 = kperm(g, 0 .. 7)), then their lo halves.
+template <int LMAX>
+struct MsgSplit {
+  static constexpr int NC = (LMAX + 1) * (LMAX + 1);
+  static constexpr int UNITS = NC * 8;       // 16-byte units per node
+  static constexpr int FLOATS = UNITS * 4;   // 288 at l_max = 2
+  static constexpr int BYTES = UNITS * 16;   // 1152
+  static constexpr int unit(int f, int half, int g) { return 8 * f + 4 * half + g; }
+};
+// The pre-mix buffer: [N x UD table][N x split_floats pre-split rows][N row maxima], offsets in floats.  split_floats = 0 for
+// plans that never take the weights-stationary kernel.  UD * 4 and MsgSplit::BYTES are multiples of 128: every region of a
+// 128-byte aligned buffer starts on a cache line.
+struct MsgPremixLayout { int64_t split, hmax, per_node; };
+constexpr MsgPremixLayout msg_premix_layout(int ud, int split_floats, int64_t N) {
+  return {N * ud, N * ((int64_t)ud + split_floats), (int64_t)ud + split_floats + 1};
+}
+
 // k slot jj (0..7) of k group g inside a 32-channel K step  <->  channel: the accumulator layout of the previous product
 __host__ __device__ constexpr int kperm(int g, int jj) { return 16 * (jj >> 2) + 4 * g + (jj & 3); }
 

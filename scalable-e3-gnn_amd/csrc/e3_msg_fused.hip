@@ -400,6 +400,52 @@ __device__ __forceinline__ void tp_core(const TpCtx& cx, const float (&y)[9], XL
 
 
 // ------------------------------------------------------------------------------------------------------------------
+// One lane's share of a feature row as B fragments: lane (node j, k group g) reads channels 4 g .. 4 g + 3 and 16 + 4 g ..
+// 16 + 4 g + 3 of every 32-channel K step of degree L1, scales them and splits them into (hi, lo).  rowmax joins max |x| of
+// what the lane read (FINITE: over the finite values only).  Shared by the pre-mix kernel and msg_refresh_rows_kernel.
+// ------------------------------------------------------------------------------------------------------------------
+template <int LMAX, int TT, bool IO16, int L1, bool FINITE>
+__device__ __forceinline__ void split_degree(const char* row, const int g, const float xs, float& rowmax,
+                                             uint4 (&xh)[MsgGeom<LMAX, TT>::KS][2 * L1 + 1],
+                                             uint4 (&xl)[MsgGeom<LMAX, TT>::KS][2 * L1 + 1]) {
+  using G = MsgGeom<LMAX, TT>;
+  constexpr int D1 = 2 * L1 + 1, ES = IO16 ? 2 : 4;
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) {
+    float x[8][D1];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (16 * (2 * ks + p) < G::H)
+        read_piece<D1, IO16>(row + (G::col0(L1) + (32 * ks + 16 * p + 4 * g) * D1) * ES, p, xs, x);
+      else
+        zero_piece<D1>(p, x);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int aa = 0; aa < D1; ++aa) rowmax = FINITE ? fmax_finite(rowmax, x[i][aa]) : fmaxf(rowmax, fabsf(x[i][aa]));
+#pragma unroll
+    for (int a = 0; a < D1; ++a) {
+      float f[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) f[i] = x[i][a];
+      split8<IO16>(f, xh[ks][a], xl[ks][a]);
+    }
+  }
+}
+// the lane's 16-byte units of the node's pre-split row (MsgSplit, e3_msg_common.h): plain stores -- the rows are gathered
+// ~24 times through the L2
+template <int LMAX, int L1>
+__device__ __forceinline__ void store_split_degree(uint4* noderow, const int g, const uint4 (&xh)[2 * L1 + 1],
+                                                   const uint4 (&xl)[2 * L1 + 1]) {
+#pragma unroll
+  for (int a = 0; a < 2 * L1 + 1; ++a) {
+    noderow[MsgSplit<LMAX>::unit(L1 * L1 + a, 0, g)] = xh[a];
+    noderow[MsgSplit<LMAX>::unit(L1 * L1 + a, 1, g)] = xl[a];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // pre-mix: U[n] = (W_dst * sw) (h[n] * xs) for every path of TP #1, in the layout the edge kernel reads as accumulator
 // initial values.  One wave per 16 nodes; inputs straight from global memory (each lane reads its own k slots).
 // ------------------------------------------------------------------------------------------------------------------
@@ -407,7 +453,7 @@ template <int LMAX, int TT, bool IO16>
 __global__ __launch_bounds__(256) void msg_premix_kernel(const void* __restrict__ hv, int64_t ldh, int64_t N,
                                                          const float* __restrict__ packed,
                                                          const float* __restrict__ in_scale, float* __restrict__ U,
-                                                         float* __restrict__ hmax) {
+                                                         uint4* __restrict__ split, float* __restrict__ hmax) {
   using G = MsgGeom<LMAX, TT>;
   constexpr int ES = IO16 ? 2 : 4;
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
@@ -431,27 +477,9 @@ __global__ __launch_bounds__(256) void msg_premix_kernel(const void* __restrict_
     auto per_l1 = [&](auto l1tag) {
       constexpr int L1 = decltype(l1tag)::value, D1 = 2 * L1 + 1;
       uint4 xh[G::KS][D1], xl[G::KS][D1];
-#pragma unroll
-      for (int ks = 0; ks < G::KS; ++ks) {
-        float x[8][D1];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          if (16 * (2 * ks + p) < G::H)
-            read_piece<D1, IO16>(row + (G::col0(L1) + (32 * ks + 16 * p + 4 * g) * D1) * ES, p, xs, x);
-          else
-            zero_piece<D1>(p, x);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int aa = 0; aa < D1; ++aa) rowmax = fmaxf(rowmax, fabsf(x[i][aa]));
-#pragma unroll
-        for (int a = 0; a < D1; ++a) {
-          float f[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) f[i] = x[i][a];
-          split8<IO16>(f, xh[ks][a], xl[ks][a]);
-        }
+      split_degree<LMAX, TT, IO16, L1, false>(row, g, xs, rowmax, xh, xl);
+      if constexpr (!IO16 && G::KS == 1) {  // the B fragments of the weights-stationary edge kernel: it gathers them as they are
+        if (split && ok) store_split_degree<LMAX, L1>(split + n * MsgSplit<LMAX>::UNITS, g, xh[0], xl[0]);
       }
       auto per_path = [&](auto l2tag, auto l3tag) {
         constexpr int L2 = decltype(l2tag)::value, L3 = decltype(l3tag)::value;
@@ -523,6 +551,40 @@ __global__ __launch_bounds__(256) void msg_premix_kernel(const void* __restrict_
     rowmax = fmaxf(rowmax, __shfl_xor(rowmax, 32));
     if (hmax && ok && lane < 16) hmax[n] = rowmax;
   }
+}
+
+// Rows of h that changed after the pre-mix launch (ghost rows after a halo exchange) and are only GATHERED as src rows: their
+// pre-split row and row maximum again (the table rows belong to dst nodes and are not touched).  One wave per 16 listed nodes;
+// the maxima are over the finite values (the operand-scale contract: a NaN / inf ghost row does not trip the overflow guard).
+template <int LMAX, int TT, bool IO16>
+__global__ __launch_bounds__(256) void msg_refresh_rows_kernel(const void* __restrict__ hv, int64_t ldh, int64_t N,
+                                                               const int64_t* __restrict__ rows, int64_t n_rows,
+                                                               const float* __restrict__ in_scale, uint4* __restrict__ split,
+                                                               float* __restrict__ hmax) {
+  constexpr int ES = IO16 ? 2 : 4;
+  const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+  const int64_t tile = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t idx = tile * 16 + j;
+  if (tile * 16 >= n_rows) return;
+  const int64_t n = rows[idx < n_rows ? idx : n_rows - 1];
+  const bool ok = idx < n_rows && n >= 0 && n < N;
+  const float xs = (!IO16 && in_scale) ? in_scale[0] : 1.0f;
+  const char* row = reinterpret_cast<const char*>(hv) + (ok ? n : 0) * ldh * ES;
+  float rowmax = 0.f;
+  auto per_l1 = [&](auto l1tag) {
+    constexpr int L1 = decltype(l1tag)::value, D1 = 2 * L1 + 1;
+    uint4 xh[MsgGeom<LMAX, TT>::KS][D1], xl[MsgGeom<LMAX, TT>::KS][D1];
+    split_degree<LMAX, TT, IO16, L1, true>(row, g, xs, rowmax, xh, xl);
+    if constexpr (!IO16 && MsgGeom<LMAX, TT>::KS == 1) {
+      if (split && ok) store_split_degree<LMAX, L1>(split + n * MsgSplit<LMAX>::UNITS, g, xh[0], xl[0]);
+    }
+  };
+  per_l1(std::integral_constant<int, 0>{});
+  per_l1(std::integral_constant<int, 1>{});
+  if constexpr (LMAX == 2) per_l1(std::integral_constant<int, 2>{});
+  rowmax = fmaxf(rowmax, __shfl_xor(rowmax, 16));
+  rowmax = fmaxf(rowmax, __shfl_xor(rowmax, 32));
+  if (ok && lane < 16) hmax[n] = rowmax;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1013,6 +1075,7 @@ struct MsgKernels {
   const void* premix[2];
   int64_t total_floats;
   int UD, D, lds_tab, lds_wave, nblk, NS, WD, o_norm1, o_norm2, o_wd, o_w, waves_per_simd;
+  const void* refresh[2];
 };
 template <int LMAX, int TT>
 static MsgKernels make_entry() {
@@ -1022,12 +1085,14 @@ static MsgKernels make_entry() {
                   {(const void*)msg_fused_kernel<LMAX, TT, false, kCell>, nullptr},
                   {(const void*)msg_premix_kernel<LMAX, TT, false>, nullptr}, G::total_floats,
                   G::UD, G::D, G::lds_tab, G::lds_wave, G::nblk(), G::NS, G::WD, G::o_norm1, G::o_norm2, G::o_wd, G::o_w,
-                  msg_waves_per_simd(LMAX, TT)};
+                  msg_waves_per_simd(LMAX, TT),
+                  {(const void*)msg_refresh_rows_kernel<LMAX, TT, false>, nullptr}};
   if constexpr (TT >= 2) {  // bf16 storage: the [0e] region of a staged row must be at least 4 units of 16 bytes (H >= 32)
     k.fused[1] = (const void*)msg_fused_kernel<LMAX, TT, true, kOpen>;
     k.fused_pbc[1] = (const void*)msg_fused_kernel<LMAX, TT, true, kBox>;
     k.fused_cell[1] = (const void*)msg_fused_kernel<LMAX, TT, true, kCell>;
     k.premix[1] = (const void*)msg_premix_kernel<LMAX, TT, true>;
+    k.refresh[1] = (const void*)msg_refresh_rows_kernel<LMAX, TT, true>;
   }
   return k;
 }
@@ -1166,8 +1231,20 @@ int e3_msg_plan_destroy(e3_msg_plan* P) {
 }
 
 int64_t e3_msg_packed_bytes(const e3_msg_plan* P) { return P ? (P->k->total_floats * 4 + 255) / 256 * 256 : -1; }
-// the table row (UD floats) + one float of the per-node row maxima, stored behind the N table rows
-int64_t e3_msg_premix_floats_per_node(const e3_msg_plan* P) { return P ? P->k->UD + 1 : -1; }
+// the table row (UD floats) + the pre-split row (plans of the weights-stationary kernel) + one float of the row maxima
+static MsgPremixLayout premix_layout(const e3_msg_plan* P, int64_t N) {
+  return msg_premix_layout(P->k->UD, msg_ws_split_floats(P->lmax, P->H), N);
+}
+int64_t e3_msg_premix_floats_per_node(const e3_msg_plan* P) { return P ? premix_layout(P, 0).per_node : -1; }
+int e3_msg_premix_regions(const e3_msg_plan* P, int64_t N, int64_t* split_offset, int64_t* split_floats_per_node,
+                          int64_t* row_max_offset) {
+  if (!P || N < 0) return E3_ERR_INVALID_ARG;
+  const MsgPremixLayout L = premix_layout(P, N);
+  if (split_offset) *split_offset = L.split;
+  if (split_floats_per_node) *split_floats_per_node = msg_ws_split_floats(P->lmax, P->H);
+  if (row_max_offset) *row_max_offset = L.hmax;
+  return E3_OK;
+}
 int e3_msg_weight_shape(const e3_msg_plan* P, int tp, int l3, int* rows, int* cols) {
   if (!P || !rows || !cols || l3 < 0 || l3 > 2 || (tp != 1 && tp != 2)) return E3_ERR_INVALID_ARG;
   *rows = tp == 1 ? P->K1[l3] : P->K2[l3];
@@ -1226,9 +1303,34 @@ int e3_msg_premix(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const 
   if (st != E3_OK) return st;
   const int64_t ntiles = (N + 15) / 16;
   const int grid = (int)std::min<int64_t>((ntiles + 3) / 4, 2048);
-  float* hmax = premix + (size_t)N * k.UD;
-  void* args[] = {&h, &ld_h, &N, &packed, &in_scale, &premix, &hmax};
+  const MsgPremixLayout L = premix_layout(P, N);
+  float* hmax = premix + L.hmax;
+  // the pre-split rows: written for the storage type whose edge kernel gathers them (fp32); the region stays unused otherwise
+  uint4* split = (L.hmax > L.split && msg_ws_supported(P->lmax, P->H, dtype) && !io) ? reinterpret_cast<uint4*>(premix + L.split)
+                                                                                  : nullptr;
+  void* args[] = {&h, &ld_h, &N, &packed, &in_scale, &premix, &split, &hmax};
   if (hipLaunchKernel(k.premix[io], dim3(grid), dim3(256), args, 0, (hipStream_t)stream) != hipSuccess) return E3_ERR_HIP;
+  return E3_OK;
+}
+
+int e3_msg_refresh_rows(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const int64_t* rows, int64_t n_rows,
+                        const float* in_scale, float* premix, int dtype, void* stream) {
+  if (!P || N < 0 || n_rows < 0) return E3_ERR_INVALID_ARG;
+  if (!e3_msg_supports(P, dtype)) return E3_ERR_UNSUPPORTED;
+  const MsgKernels& k = *P->k;
+  const int io = dtype == E3_BF16 ? 1 : 0, es = io ? 2 : 4;
+  if (N == 0 || n_rows == 0) return E3_OK;
+  if (!h || !rows || !premix || ld_h < k.D) return E3_ERR_INVALID_ARG;
+  if ((ld_h * es & 15) || ((uintptr_t)h & 15) || ((uintptr_t)premix & 15)) return E3_ERR_INVALID_ARG;
+  const int64_t nblocks = ((n_rows + 15) / 16 + 3) / 4;
+  if (nblocks > 0x7fffffffLL) return E3_ERR_INVALID_ARG;
+  const MsgPremixLayout L = premix_layout(P, N);
+  float* hmax = premix + L.hmax;
+  uint4* split = (L.hmax > L.split && msg_ws_supported(P->lmax, P->H, dtype) && !io) ? reinterpret_cast<uint4*>(premix + L.split)
+                                                                                  : nullptr;
+  void* args[] = {&h, &ld_h, &N, &rows, &n_rows, &in_scale, &split, &hmax};
+  if (hipLaunchKernel(k.refresh[io], dim3((int)nblocks), dim3(256), args, 0, (hipStream_t)stream) != hipSuccess)
+    return E3_ERR_HIP;
   return E3_OK;
 }
 

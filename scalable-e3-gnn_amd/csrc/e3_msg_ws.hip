@@ -19,13 +19,16 @@
 // does vector / copy work, so every SIMD holds one matrix-heavy and one light wave (with both teams in the same kind of phase
 // the two waves of a SIMD competed for the same pipe and a step took the SUM of their issue times):
 //
-//   phase X(s)   waves 0-1: gathered rows of tile s -> B fragments of product #1 (wave p: rows 8 p .. 8 p + 7), harmonics
+//   phase X(s)   fp32 storage: the gathered rows are PRE-SPLIT (the pre-mix launch writes the fragments once per node) and
+//                the image is product #1's operand image; one wave forms the feature-first operands from it
+//                bf16 storage: waves 0-1: gathered rows of tile s -> B fragments of product #1 (wave p: rows 8 p .. 8 p + 7)
 //                wave 3   : look at the ids of tile s + 1, cut the tile (<= 16 edges, <= 2 dst runs), copy its positions, row
 //                           maxima and pre-mix rows (a row already staged for the previous tile is not copied again), ids of s + 2
 //                team 1   : product #2 + gate of tile s - 1 -> out tile
 //   phase Y(s)   team 0   : product #1 + gate of tile s -> B fragments of product #2, written directly (below)
 //                waves 4-5: run sums of tile s - 1 (fp32 atomics, one per node, column and chunk)
-//                waves 6-7: copies of the h[src] rows of tile s + 1 (9 x 1 KiB each)
+//                waves 6-7: copies of the (pre-split) h[src] rows of tile s + 1 (9 x 1 KiB each; fp32: into the image of the
+//                           tile's parity -- product #1 is reading the other one)
 //
 // Product #1 -> product #2 without a message buffer: the gated output of product #1 sits in accumulator layout, which IS the
 // B-operand layout of product #2 (k order permuted at pack time), so each wave stores its own 8-byte half of every fragment
@@ -101,14 +104,109 @@ struct Ws {
   static constexpr int z_y = 0, z_112 = 12, z_121 = 28, z_211 = 40, z_222 = 56, ZT = LMAX == 2 ? 84 : 12;
   static constexpr int o_zt = o_srow + 2 * 64;
   static constexpr int o_init = o_zt + 2 * 16 * ZT * 4;                 // initial values of the T(0) scalar-type tiles of product #1
-  static constexpr int o_g = o_init + G::T(0) * 1024;                   // gather image (copied in phase Y, read in phase X)
-  static constexpr int o_b1 = o_g + G_BYTES;
-  static constexpr int o_b2 = o_b1 + NFR * FRB;
+  // ---- fp32 storage: the gathered rows are PRE-SPLIT (MsgSplit: written once per node by the pre-mix launch) and the image
+  //      IS the B-operand image of product #1 -- no conversion.  One image per tile parity (product #1 reads tile s in phase Y
+  //      while the copies of tile s + 1 land):
+  //        region A: 16 rows x fragments 1 .. NC - 1 (one copy per row: 1 KiB at l_max = 2), row stride + 32 bytes
+  //        region Z: fragment 0 ([0e]): two copies of 8 rows x 128 bytes; lane order chosen by the SOURCE addresses (p_zpos)
+  //        region F: the LMAX feature-first fragments (written in phase X by one team-0 wave), laid out like Z
+  //      The maps below are checked at compile time (WsImageCheck): coverage, read-after-write and bank conflicts. ----
+  static constexpr bool PRE = !IO16;
+  static constexpr int P_AROW = (NC - 1) * 128;                         // bytes of a region-A row
+  static constexpr int P_ASTRIDE = P_AROW + 32;
+  static constexpr int P_ALANES = P_AROW / 16;                          // lanes of a region-A copy
+  static constexpr int o_pz = 16 * P_ASTRIDE, o_pf = o_pz + 2048;       // inside an image
+  static constexpr int P_IMG = o_pf + LMAX * 2048;
+  // copies: lane -> byte inside the node's pre-split row, and -> byte inside the image
+  static constexpr int p_asrc(int lane) { return 128 + 16 * lane; }
+  static constexpr int p_alds(int row, int lane) { return row * P_ASTRIDE + 16 * lane; }
+  static constexpr int p_zrow(int piece, int lane) { return 8 * piece + (lane & 7); }
+  static constexpr int p_zsrc(int lane) { return 64 * ((lane >> 5) & 1) + 16 * (2 * ((lane >> 4) & 1) + ((lane >> 3) & 1)); }
+  static constexpr int p_zlds(int piece, int lane) { return o_pz + 1024 * piece + 16 * lane; }
+  // reads of lane (k group g = lane >> 4, row = lane & 15): half 0 = hi, 1 = lo.  Position of (row, g) inside a Z-like region:
+  static constexpr int p_zpos(int lane) {
+    return 1024 * ((lane & 15) >> 3) + 256 * (lane >> 5) + 128 * ((lane >> 4) & 1) + 16 * (lane & 7);
+  }
+  static constexpr int p_abase(int lane) { return (lane & 15) * P_ASTRIDE + 16 * (lane >> 4); }
+  static constexpr int p_zbase(int lane) { return o_pz + p_zpos(lane); }
+  // fragment fr < NC: component; fr >= NC: feature-first operand.  Offset from p_abase (fr in 1 .. NC - 1) or p_zbase (others)
+  static constexpr bool p_on_a(int fr) { return fr >= 1 && fr < NC; }
+  static constexpr int p_off(int fr, int half) {
+    return p_on_a(fr) ? 128 * (fr - 1) + 64 * half : (fr == 0 ? 0 : 2048 * (1 + fr - NC)) + 512 * half;
+  }
+  static constexpr int p_read(int fr, int half, int lane) { return (p_on_a(fr) ? p_abase(lane) : p_zbase(lane)) + p_off(fr, half); }
+  static constexpr int o_g = o_init + G::T(0) * 1024;                   // gather image(s) (copied in phase Y)
+  static constexpr int o_b1 = o_g + (PRE ? 2 * P_IMG : G_BYTES);        // bf16 storage: converted fragments of product #1
+  static constexpr int o_b2 = o_b1 + (PRE ? 0 : NFR * FRB);
   static constexpr int o_o = o_b2 + NFR * FRB;
   static constexpr int o_u = o_o + 16 * RS * 4;                         // 4 pre-mix row slots
   static constexpr int total = o_u + 4 * U_ROW;
   static_assert(total <= 160 * 1024, "LDS image exceeds the CU");
 };
+
+// Compile-time proof of the pre-split image maps: (1) the copies write every 16-byte unit of regions A (without the row pads)
+// and Z exactly once, (2) every read of product #1 / the feature-first job lands on the unit that holds ITS row's unit
+// MsgSplit::unit(fr, half, g), (3) the 16 lanes of every ds_read_b128 conflict group ({0-3, 12-15, 20-27}, {4-11, 16-19,
+// 28-31} and the same + 32) hit 16 different 16-byte bank slots of the 256-byte bank row.
+template <int LMAX, int TT>
+struct WsImageCheck {
+  using L = Ws<LMAX, TT, false>;
+  static constexpr int NU = L::o_pf / 16;
+  static constexpr int group_lane(int grp, int i) {  // i-th lane of conflict group grp
+    const int base = 32 * (grp >> 1), odd = grp & 1;
+    const int k = odd ? (i < 8 ? 4 + i : (i < 12 ? 16 + (i - 8) : 28 + (i - 12))) : (i < 4 ? i : (i < 8 ? 12 + (i - 4) : 20 + (i - 8)));
+    return base + k;
+  }
+  static constexpr bool run() {
+    int owner_row[NU] = {}, owner_unit[NU] = {}, count[NU] = {};
+    for (int r = 0; r < 16; ++r)
+      for (int l = 0; l < L::P_ALANES; ++l) {
+        const int u = L::p_alds(r, l) / 16;
+        if (L::p_alds(r, l) % 16 || u < 0 || u >= NU) return false;
+        ++count[u]; owner_row[u] = r; owner_unit[u] = L::p_asrc(l) / 16;
+      }
+    for (int p = 0; p < 2; ++p)
+      for (int l = 0; l < 64; ++l) {
+        const int u = L::p_zlds(p, l) / 16;
+        if (u < 0 || u >= NU) return false;
+        ++count[u]; owner_row[u] = L::p_zrow(p, l); owner_unit[u] = L::p_zsrc(l) / 16;
+      }
+    int written = 0;
+    for (int u = 0; u < NU; ++u) {
+      if (count[u] > 1) return false;
+      written += count[u];
+    }
+    if (written != 16 * MsgSplit<LMAX>::UNITS) return false;  // all of the 16 rows, nothing twice
+    for (int fr = 0; fr < L::NC; ++fr)
+      for (int half = 0; half < 2; ++half) {
+        for (int lane = 0; lane < 64; ++lane) {
+          const int a = L::p_read(fr, half, lane), u = a / 16;
+          if (a % 16 || u < 0 || u >= NU || count[u] != 1) return false;
+          if (owner_row[u] != (lane & 15) || owner_unit[u] != MsgSplit<LMAX>::unit(fr, half, lane >> 4)) return false;
+        }
+      }
+    for (int fr = 0; fr < L::NFR; ++fr)  // banks: the feature-first fragments (region F) too
+      for (int half = 0; half < 2; ++half)
+        for (int grp = 0; grp < 4; ++grp) {
+          bool seen[16] = {};
+          for (int i = 0; i < 16; ++i) {
+            const int a = L::p_read(fr, half, group_lane(grp, i));
+            if (a < 0 || a + 16 > L::P_IMG) return false;
+            const int slot = (a % 256) / 16;
+            if (seen[slot]) return false;
+            seen[slot] = true;
+          }
+        }
+    // region F: 64 lanes x 2 halves x LMAX fragments, disjoint 16-byte units behind region Z
+    for (int fr = L::NC; fr < L::NFR; ++fr)
+      for (int half = 0; half < 2; ++half)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int l2 = lane + 1; l2 < 64; ++l2)
+            if (L::p_read(fr, half, lane) == L::p_read(fr, half, l2) || L::p_read(fr, half, lane) < L::o_pf) return false;
+    return true;
+  }
+};
+static_assert(WsImageCheck<2, 2>::run() && WsImageCheck<1, 2>::run(), "pre-split image: coverage, read map or bank conflicts");
 
 // tile descriptor (LDS, ring of 4): n == 0: no such tile; sl0 / sl1: pre-mix row slots of the two runs
 struct TileInfo { int e0, n, n0, node0, node1, sl0, sl1; };
@@ -177,6 +275,15 @@ __device__ __forceinline__ void ws_put4(unsigned char* dst, const float (&f)[4],
     *reinterpret_cast<uint2*>(dst + 1024) = uint2{l0, l1};
   }
 }
+// acc + z * (fp16 half HI of pair): v_fma_mix_f32 widens the f16 operand itself (no separate conversion)
+template <int HI>
+__device__ __forceinline__ float fma_mix_h(const float z, const uint32_t pair, const float acc) {
+  float d;
+  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(d) : "v"(z), "v"(pair), "v"(acc));
+  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(d) : "v"(z), "v"(pair), "v"(acc));
+  return d;
+}
+__device__ __forceinline__ uint32_t u4_word(const uint4& v, const int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 template <class F>
 __device__ __forceinline__ void sfor3(F&& f) {  // f(integral_constant<int, 0 .. 2>)
   f(std::integral_constant<int, 0>{}); f(std::integral_constant<int, 1>{}); f(std::integral_constant<int, 2>{});
@@ -305,8 +412,12 @@ struct TpRun {
   static constexpr int LV = O::LV, t = O::t, tG = O::tG, tS = O::tS;
   static constexpr bool SC = tG >= 0 || tS >= 0;  // owns scalar-type (l3 = 0) tiles
 
+  static constexpr bool PIMG = FIRST && L::PRE;  // product #1, fp32: the operands are read from the gathered image itself
   const RoleW<O::NW>& w;
-  const unsigned char* bfr;
+  const unsigned char* bfr;  // this product's B fragments + lane * 16; PIMG: image + p_abase(lane)
+  const unsigned char* bfz;  // PIMG: the image (uniform); fragment 0 and the feature-first fragments sit at + p_zbase(lane),
+  int lane;                  //       an address formed where it is used (three reads per tile): a second per-lane base held
+                             //       across the product costs the register the kernel does not have (256, two waves per SIMD)
   const float* zt;         // this lane's row of the edge table
   const float* urow;
   const float* wd;
@@ -337,9 +448,20 @@ struct TpRun {
       constexpr int L1 = IT::l1(I), a = IT::a(I), slot = I % (WS_PF + 1);
       constexpr int fr = a >= 0 ? L::frag(L1, a) : L::frag_ff(L1);
       if constexpr (a >= 0 || SC) {
-        bh[slot] = *reinterpret_cast<const uint4*>(bfr + fr * L::FRB);
-        if constexpr (!IO16) bl[slot] = *reinterpret_cast<const uint4*>(bfr + fr * L::FRB + 1024);
-        else bl[slot] = uint4{0, 0, 0, 0};
+        if constexpr (PIMG) {
+          const unsigned char* b = bfr;
+          if constexpr (!L::p_on_a(fr)) {
+            int l = lane;
+            asm volatile("" : "+v"(l));  // (keeps the address arithmetic here)
+            b = bfz + L::p_zbase(l);
+          }
+          bh[slot] = *reinterpret_cast<const uint4*>(b + L::p_off(fr, 0));
+          bl[slot] = *reinterpret_cast<const uint4*>(b + L::p_off(fr, 1));
+        } else {
+          bh[slot] = *reinterpret_cast<const uint4*>(bfr + fr * L::FRB);
+          if constexpr (!IO16) bl[slot] = *reinterpret_cast<const uint4*>(bfr + fr * L::FRB + 1024);
+          else bl[slot] = uint4{0, 0, 0, 0};
+        }
       }
       const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
       if constexpr (a >= 0) {
@@ -470,10 +592,11 @@ struct TpRun {
 };
 
 template <int LMAX, int TT, int ROLE, bool FIRST, bool IO16>
-__device__ __forceinline__ void ws_tp(const RoleW<Own<LMAX, TT, ROLE>::NW>& w, const unsigned char* bfr, const float* zt,
+__device__ __forceinline__ void ws_tp(const RoleW<Own<LMAX, TT, ROLE>::NW>& w, const unsigned char* bfr,
+                                      const unsigned char* bfz, const int lane, const float* zt,
                                       const float* urow, const float* wd, const f32x4* init,
                                       f32x4 (&accV)[5], f32x4& accG, f32x4& accS, float (&y)[10], uint32_t* tpmarks = nullptr) {
-  TpRun<LMAX, TT, ROLE, FIRST, IO16> r{w, bfr, zt, urow, wd, init, accV, accG, accS};
+  TpRun<LMAX, TT, ROLE, FIRST, IO16> r{w, bfr, bfz, lane, zt, urow, wd, init, accV, accG, accS};
 #if E3_WS_STAMP
   r.tpm = tpmarks;
   r.tpm0 = (uint32_t)__builtin_readcyclecounter();
@@ -490,7 +613,7 @@ template <class BOX>
 struct WsArgsT {
   const void* h; int64_t ldh;
   const float4* pos4; const int32_t* src; const int32_t* dst; int64_t E;
-  const float* packed; const float* U; const float* hmax; const float* in_scale; float* out; int64_t ldo;
+  const float* packed; const float* U; const void* split; const float* hmax; const float* in_scale; float* out; int64_t ldo;
   int chunk;  // edges per chunk (multiple of 16)
   BOX box;  // periodic instantiations only (the open kernel never reads it); PbcCell for the cell instantiations
 };
@@ -503,15 +626,17 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
   constexpr int H = G::H, D = G::D, ES = L::ES;
   constexpr bool TEAM1 = W >= 4;
   constexpr int ROLE = W & 3;
-  // service job of a team-0 wave in phase X: 0 / 1 conversion of rows 0-7 / 8-15 (+ initial values), 2 initial values + edge
-  // table, 3 the tile cutter.  Rotated against the product roles (WS_XROT) so that the two conversion waves -- the longest,
+  // service job of a team-0 wave in phase X: 0 / 1 conversion of rows 0-7 / 8-15 (+ initial values; fp32 storage: 0 the
+  // feature-first operands, 1 initial values), 2 initial values + edge table, 3 the tile cutter.  Rotated against the product roles (WS_XROT) so that the two conversion waves -- the longest,
   // vector-heavy jobs -- share their SIMDs with the lighter roles of product #2 (l3 = 1 tiles: waves 6, 7), not with the
   // l3 = 2 roles (waves 4, 5), which are the longest of phase X
   constexpr int SX = TEAM1 ? -1 : ((W + WS_XROT) & 3);
   // scalar-type tiles whose initial values this wave computes (two at a time): WS_INITMAP 0: two tiles on each of the jobs
   // 0-2; 1: four on the cutter's wave (the shortest job), two on the table's wave, none on the conversion waves (the longest)
-  constexpr int ITB = SX < 0 ? 0 : (WS_INITMAP ? (SX == 3 ? 0 : 4) : 2 * SX);
-  constexpr int ITE0 = SX < 0 ? 0 : (WS_INITMAP ? (SX == 3 ? 4 : (SX == 2 ? 6 : 4)) : (SX <= 2 ? 2 * SX + 2 : 2 * SX));
+  // fp32 storage (pre-split rows: job 0 = the feature-first operands, no conversion): four tiles on job 1, two on the table's wave
+  constexpr int ITB = SX < 0 ? 0 : L::PRE ? (SX == 2 ? 4 : 0) : (WS_INITMAP ? (SX == 3 ? 0 : 4) : 2 * SX);
+  constexpr int ITE0 = SX < 0 ? 0 : L::PRE ? (SX == 1 ? 4 : (SX == 2 ? 6 : 0))
+                                           : (WS_INITMAP ? (SX == 3 ? 4 : (SX == 2 ? 6 : 4)) : (SX <= 2 ? 2 * SX + 2 : 2 * SX));
   constexpr int ITE = ITE0 < G::T(0) ? ITE0 : G::T(0);
   constexpr int SY = TEAM1 ? ((W + WS_YROT) & 3) : -1;  // phase Y jobs of team 1: 0 / 1 run sums, 2 / 3 row copies
   using O = Own<LMAX, TT, ROLE>;
@@ -573,6 +698,23 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
   //      the end of the tile are the src rows of the following edges (valid rows; never summed): only the ids are needed ----
   auto gather_part = [&](const int tile, const int part) {
     const int* ids = reinterpret_cast<const int*>(smem + L::o_ids) + (tile & 3) * 32;
+    if constexpr (L::PRE) {
+      // pre-split rows -> the image of the tile's parity: 8 region-A rows (one copy each) and piece `part` of region Z
+      const uint32_t ib = lds0 + L::o_g + (tile & 1) * L::P_IMG;
+      const char* sp = reinterpret_cast<const char*>(A.split);
+      const int myid = ids[lane & 15];
+      const int zid = ids[L::p_zrow(part, lane)];
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int r = 8 * part + k;
+        const int rid = part == 0 ? __builtin_amdgcn_readlane(myid, k) : __builtin_amdgcn_readlane(myid, 8 + k);
+        const char* rowp = sp + (int64_t)rid * MsgSplit<LMAX>::BYTES;
+        if (L::P_ALANES >= 64 || lane < L::P_ALANES) dma16(rowp + L::p_asrc(lane), sgpr((int)(ib + L::p_alds(r, 0))));
+      }
+      dma16(sp + (int64_t)zid * MsgSplit<LMAX>::BYTES + L::p_zsrc(lane), sgpr((int)(ib + L::p_zlds(part, 0))));
+      return;
+    }
     const uint32_t gb = lds0 + L::o_g;
     static_assert(L::GA_ROW % 16 == 0 && L::GA_ROW <= 1024 && (L::GB_ROW == 128 || L::GB_ROW == 64), "copy shapes of the image");
     constexpr int LA = L::GA_ROW / 16;          // lanes of one region-A row copy (64 fp32, 32 bf16)
@@ -611,7 +753,9 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
     if (pok && lane < 32) {
       int e = pe0 + (lane & 15);
       e = e < Ei ? e : Ei - 1;
-      const int32_t* p = (lane < 16 ? A.src : A.dst) + e;
+      int l = lane;
+      asm volatile("" : "+v"(l));  // (the column select is formed here: hoisted out of the tile loop it holds two registers)
+      const int32_t* p = (l < 16 ? A.src : A.dst) + e;
       dma4(p, sgpr((int)(lds0 + L::o_ids + (tile & 3) * 128)));
     }
   };
@@ -731,7 +875,51 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
       // ---- gathered rows of tile s -> B fragments of product #1.  Wave p (0, 1) converts rows 8 p .. 8 p + 7 of every
       //      degree: lane = (row j8, channel group g, half pc) handles ONE piece (4 channels x all components) per degree,
       //      i.e. half of a fragment lane's 8 k slots -> 8-byte stores of the hi and the lo halves ----
-      if (SX <= 1 && t0.n > 0) {
+      if constexpr (L::PRE) {
+        // ---- fp32 storage: the gathered image already holds the component fragments of product #1 (pre-split rows).  What is
+        //      left per edge is the feature-first operand of the degrees > 0, f[k] = sum_a z_a(Y_e) x[k][a] with x = hi + lo
+        //      (scaled units: the split below uses scale 1): job 0, lane (k group g, row j) = one fragment lane per degree ----
+        if (SX == 0 && t0.n > 0) {
+          const unsigned char* img = smem + L::o_g + (s & 1) * L::P_IMG;
+          const unsigned char* ba = img + L::p_abase(lane);
+          unsigned char* bz = smem + L::o_g + (s & 1) * L::P_IMG + L::p_zbase(lane);
+          const float4* pp = reinterpret_cast<const float4*>(smem + L::o_pos + (s & 1) * 512);
+          const float4 ps = pp[j], pd = pp[16 + j];
+          uint4 xh[L::NC - 1], xl[L::NC - 1];  // components 1 .. NC - 1 (all in region A)
+#pragma unroll
+          for (int f = 1; f < L::NC; ++f) {
+            xh[f - 1] = *reinterpret_cast<const uint4*>(ba + L::p_off(f, 0));
+            xl[f - 1] = *reinterpret_cast<const uint4*>(ba + L::p_off(f, 1));
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          float y[9], dist;
+          if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, A.box); else edge_sh1<PBC>(ps, pd, y, dist, A.box);
+          auto degree = [&](auto ltag) {
+            constexpr int L1 = decltype(ltag)::value, D1 = 2 * L1 + 1, F0 = L1 * L1 - 1;
+            float zz[D1][1];
+            make_z<L1, L1, 0>(y, zz);
+            float f[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+              float sum = 0.f;
+#pragma unroll
+              for (int a = 0; a < D1; ++a) {
+                const uint32_t ph = u4_word(xh[F0 + a], k >> 1), pl = u4_word(xl[F0 + a], k >> 1);
+                if (k & 1) { sum = fma_mix_h<1>(zz[a][0], ph, sum); sum = fma_mix_h<1>(zz[a][0], pl, sum); }
+                else { sum = fma_mix_h<0>(zz[a][0], ph, sum); sum = fma_mix_h<0>(zz[a][0], pl, sum); }
+              }
+              f[k] = sum;
+            }
+            uint32_t h[4], l[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) split2_f16_scaled(f[2 * q], f[2 * q + 1], 1.0f, h[q], l[q]);
+            *reinterpret_cast<uint4*>(bz + L::p_off(L::frag_ff(L1), 0)) = uint4{h[0], h[1], h[2], h[3]};
+            *reinterpret_cast<uint4*>(bz + L::p_off(L::frag_ff(L1), 1)) = uint4{l[0], l[1], l[2], l[3]};
+          };
+          if constexpr (LMAX == 2) degree(I2{});
+          degree(I1{});
+        }
+      } else if (SX <= 1 && t0.n > 0) {  // ---- bf16 storage: the conversion waves ----
         const int j8 = lane & 7, gg = (lane >> 3) & 3, pc = lane >> 5, row = 8 * SX + j8;
         const unsigned char* gimg = smem + L::o_g;
         unsigned char* b1 = smem + L::o_b1 + (16 * gg + row) * 16 + 8 * pc;
@@ -743,13 +931,7 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
           const unsigned char* r2 = gimg + row * L::GA_STRIDE + (LMAX == 2 ? (3 * H + (16 * pc + 4 * gg) * 5) * ES : 0);
           const unsigned char* r1 = gimg + row * L::GA_STRIDE + (16 * pc + 4 * gg) * 3 * ES;
           const unsigned char* r0 = gimg + L::GA_BYTES + row * L::GB_ROW + (16 * pc + 4 * gg) * ES;
-          if constexpr (!IO16) {
-#pragma unroll
-            for (int u = 0; u < (LMAX == 2 ? 5 : 0); ++u) { const f32x4 v = reinterpret_cast<const f32x4*>(r2)[u]; q2[4 * u] = v[0]; q2[4 * u + 1] = v[1]; q2[4 * u + 2] = v[2]; q2[4 * u + 3] = v[3]; }
-#pragma unroll
-            for (int u = 0; u < 3; ++u) { const f32x4 v = reinterpret_cast<const f32x4*>(r1)[u]; q1[4 * u] = v[0]; q1[4 * u + 1] = v[1]; q1[4 * u + 2] = v[2]; q1[4 * u + 3] = v[3]; }
-            { const f32x4 v = reinterpret_cast<const f32x4*>(r0)[0]; q0[0] = v[0]; q0[1] = v[1]; q0[2] = v[2]; q0[3] = v[3]; }
-          } else {  // 4 bf16 per 8-byte read, widened (exact)
+          {  // 4 bf16 per 8-byte read, widened (exact)
             auto widen = [](const uint2 v, float* o) {
               o[0] = __builtin_bit_cast(float, v.x << 16); o[1] = __builtin_bit_cast(float, v.x & 0xffff0000u);
               o[2] = __builtin_bit_cast(float, v.y << 16); o[3] = __builtin_bit_cast(float, v.y & 0xffff0000u);
@@ -885,7 +1067,7 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         // (the product wave is the longest of its SIMD pair in either phase: it gets the vector issue slots first)
         __builtin_amdgcn_s_setprio(WS_PRIO);
         WS_PM(5)
-        ws_tp<LMAX, TT, ROLE, false, IO16>(w, smem + L::o_b2 + lane * 16, ztr, nullptr, nullptr, nullptr, accV, accG, accS, y, tpmk);
+        ws_tp<LMAX, TT, ROLE, false, IO16>(w, smem + L::o_b2 + lane * 16, nullptr, lane, ztr, nullptr, nullptr, nullptr, accV, accG, accS, y, tpmk);
         WS_PM0
         const f32x4* nt = reinterpret_cast<const f32x4*>(n2tab) + g;
         float* orow = reinterpret_cast<float*>(smem + L::o_o) + j * L::RS;
@@ -944,7 +1126,9 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         f32x4 accV[5], accG, accS;
         __builtin_amdgcn_s_setprio(WS_PRIO1);
         WS_PM(5)
-        ws_tp<LMAX, TT, ROLE, true, IO16>(w, smem + L::o_b1 + lane * 16, ztr, urow, wdtab + 4 * g,
+        const unsigned char* img = smem + L::o_g + (L::PRE ? (s & 1) * L::P_IMG : 0);
+        ws_tp<LMAX, TT, ROLE, true, IO16>(w, L::PRE ? img + L::p_abase(lane) : smem + L::o_b1 + lane * 16,
+                                          L::PRE ? img : nullptr, lane, ztr, urow, wdtab + 4 * g,
                                           reinterpret_cast<const f32x4*>(smem + L::o_init) + lane, accV, accG, accS, y, tpmk);
         WS_PM0
         const float dsc = y[9];
@@ -1105,6 +1289,11 @@ bool msg_ws_supported(int lmax, int hidden, int dtype) {
   return (lmax == 2 || (lmax == 1 && WS_LMAX1)) && hidden == 32 && (dtype == E3_F32 || dtype == E3_BF16);
 }
 
+int msg_ws_split_floats(int lmax, int hidden) {
+  return msg_ws_supported(lmax, hidden, E3_F32) ? (lmax + 1) * (lmax + 1) * 32 : 0;
+}
+static_assert(MsgSplit<2>::FLOATS == 9 * 32 && MsgSplit<1>::FLOATS == 4 * 32, "msg_ws_split_floats");
+
 int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, int64_t N, const float* pos4, const int32_t* src,
                   const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix, float* out,
                   int64_t ldo, int chunk_edges, hipStream_t stream, const float* box, const PbcCell* cell) {
@@ -1152,11 +1341,14 @@ int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, i
   const int64_t nchunks = (E + chunk - 1) / chunk;
   int nwg = (int)std::min<int64_t>(cus, nchunks);  // one workgroup of 8 waves per CU
   nwg = std::max(8, (nwg + 7) / 8 * 8);
-  const float* hmax = premix + (size_t)N * ud;  // per-node row maxima behind the table (e3_msg_premix)
+  // behind the table: the pre-split rows (gathered by the fp32 kernel) and the per-node row maxima (e3_msg_premix)
+  const MsgPremixLayout lay = msg_premix_layout(ud, msg_ws_split_floats(lmax, hidden), N);
+  const float* split = premix + lay.split;
+  const float* hmax = premix + lay.hmax;
   // the argument block of the mode: the box / cell sits behind the common fields (kernel-argument segment: SGPRs)
   auto launch = [&](const auto& pbc) {
     WsArgsT<std::decay_t<decltype(pbc)>> a = {h, ldh, reinterpret_cast<const float4*>(pos4), src, dst, E,
-                                              static_cast<const float*>(packed), premix, hmax, in_scale, out, ldo, chunk, pbc};
+                                              static_cast<const float*>(packed), premix, split, hmax, in_scale, out, ldo, chunk, pbc};
     void* args[] = {&a};
     return hipLaunchKernel(kern, dim3(nwg), dim3(512), args, lds, stream) == hipSuccess ? E3_OK : E3_ERR_HIP;
   };

@@ -106,21 +106,35 @@ class FusedMessage:
         """The pre-mix launch leaves max |h[n] in_scale| per node behind its table (the edge kernel bounds a row's messages
         with it).  After rows of ``h`` were overwritten (halo refresh of the ghost rows) their entries are recomputed here
         -- device-side, no sync -- and the largest scaled value is returned (device scalar) for the caller's overflow guard.
-        The maxima are over the finite entries (the operand-scale contract): a NaN / inf ghost row stays in the rows the
-        math sends it to and does not trip the guard."""
+        Their pre-split rows, which the fp32 edge kernel gathers instead of ``h[src]``, are rewritten by the same launch
+        (``e3_msg_refresh_rows``).  The maxima are over the finite entries (the operand-scale contract): a NaN / inf ghost row
+        stays in the rows the math sends it to and does not trip the guard."""
         premix = state[1]
         N = h.shape[0]
-        ud = premix.numel() // N - 1
-        hmax = premix[N * ud:]
-        if rows.numel():
-            a = h[rows].float().abs()
-            m = torch.where(a < float("inf"), a, 0.0).amax(1)   # NaN < inf is False: filtered too
-        else:
-            m = h.new_zeros(0, dtype=torch.float32)
-        if in_scale is not None and h.dtype == torch.float32:
-            m = m * in_scale[0]
-        hmax[rows] = m
-        return m.max() if m.numel() else torch.zeros((), device=h.device)
+        if N == 0 or rows.numel() == 0:
+            return torch.zeros((), device=h.device)
+        if h.stride(-1) != 1 or (h.stride(0) * h.element_size()) % 16 or h.data_ptr() % 16:
+            h = h.contiguous()
+        dev = h.device
+        rows = rows.to(device=dev, dtype=torch.int64).contiguous()
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            hd = self._plans.handle(dev)
+            sc = in_scale.data_ptr() if (in_scale is not None and h.dtype == torch.float32) else None
+            _lib.check(lib.e3_msg_refresh_rows(hd, h.data_ptr(), h.stride(0), N, rows.data_ptr(), rows.numel(), sc,
+                                               premix.data_ptr(), _lib.dtype_code(h.dtype),
+                                               torch.cuda.current_stream(dev).cuda_stream), "e3_msg_refresh_rows")
+        return self.premix_regions(dev, premix, N)[2][rows].max()
+
+    def premix_regions(self, device, premix: torch.Tensor, N: int):
+        """Views of the pre-mix buffer's regions (include/e3gnn.h): the table [N, UD], the pre-split rows [N, S] (S = 0 for
+        shapes whose edge kernel does not gather them) and the row maxima [N].  The offsets come from the library."""
+        off_s, per, off_m = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.load().e3_msg_premix_regions(self._plans.handle(device), N, ctypes.byref(off_s), ctypes.byref(per),
+                                                     ctypes.byref(off_m)), "e3_msg_premix_regions")
+        table = premix[:off_s.value].view(N, -1) if N else premix[:0]
+        split = premix[off_s.value:off_m.value].view(N, per.value) if N else premix[:0]
+        return table, split, premix[off_m.value:off_m.value + N]
 
     def executed_flops_per_edge(self) -> int:
         """Flops the edge kernel actually EXECUTES on the matrix pipe per edge and product pass: the dst half and the distance
