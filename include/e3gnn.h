@@ -714,6 +714,30 @@ int e3_nl_update_cell(const float* pos, const int32_t* perm, const float* ref_po
                       int64_t N, int64_t E, float r, const float cell[9], float* pos4_out, int32_t* rowptr_out,
                       int32_t* src_out, int32_t* dst_out, uint32_t* stats, void* workspace, void* stream);
 
+/* =================================================================================================
+ * Differentiable ghost refresh of the sharded path (sharding.Halo.refresh / reduce_ghosts): the once-per-layer refresh as
+ * an out-of-place row copy, and its backward as a row sum.  Rows are [n, D] of dtype E3_F32 or E3_F64 with a leading
+ * dimension (elements); n = the rows of the local cloud [owned | ghosts] in graph order.
+ *   slot [n] int32 : -1 for an owned row, else the row's position in the received buffer.
+ *   e3_halo_refresh : out[i] = slot[i] < 0 ? h[i] : recv[slot[i]]          (recv [n_recv, D]; h is not written and its
+ *             ghost rows are not read; a slot >= n_recv reads nothing and writes a zero row)
+ *   e3_halo_reduce  : out[i] = (slot[i] < 0 ? g[i] : 0) + sum_{q = red_ptr[i]}^{red_ptr[i+1] - 1} back[red_k[q]]
+ *             back [n_back, D]: the gradient rows that came back for the rows this rank sent, in send order; red_ptr [n + 1]
+ *             / red_k [n_back] int32: the send list grouped by its target row (CSR), k ascending inside a row.  The sum
+ *             starts from the row's own gradient and adds the list in its order, in the rows' dtype: no atomics, bit-equal
+ *             from run to run.  List bounds are clamped to [0, n_back] and a k outside [0, n_back) adds nothing.
+ * One wave per row; 16-byte accesses when every pointer is 16-byte aligned and every leading dimension is a multiple of 16
+ * bytes, the columns past the last whole 16 bytes (or all, otherwise) by 4- / 8-byte ones: same values either way.
+ * E3_ERR_INVALID_ARG before any launch for n < 0, n_recv / n_back < 0, D < 1, a leading dimension below D, a dtype other
+ * than E3_F32 / E3_F64, and, when n > 0, a NULL h / g, slot or out, or a NULL recv (back, red_ptr, red_k) with n_recv
+ * (n_back) > 0.  n = 0 returns E3_OK and launches nothing; n_recv = 0 / n_back = 0 (no ghosts / nothing sent) are valid.
+ * ================================================================================================= */
+int e3_halo_refresh(const void* h, int64_t ld_h, const void* recv, int64_t ld_recv, int64_t n_recv, const int32_t* slot,
+                    int64_t n, int D, int dtype, void* out, int64_t ld_out, void* stream);
+int e3_halo_reduce(const void* g, int64_t ld_g, const void* back, int64_t ld_back, int64_t n_back, const int32_t* slot,
+                   const int32_t* red_ptr, const int32_t* red_k, int64_t n, int D, int dtype, void* out, int64_t ld_out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

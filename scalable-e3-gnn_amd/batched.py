@@ -84,22 +84,29 @@ def _neighbors_graph(neighbors, pos, r, skin, defaults: dict):
     return neighbors.update(pos)
 
 
-def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure, cutoff_kw=None):
+def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure, cutoff_kw=None, halo=None,
+                          split=None):
     """Energy of ``net``'s scalar node readout summed per segment (``seg`` [N] graph order, ``n_seg`` segments; ``seg``
     None: the 0-d total), and from ONE backward pass through the differentiable chain dE/dpos_g [N,3] (``forces``) and
     dE/deps [n_strain,3,3] at a zero per-structure strain (``n_strain`` > 0; ``structure`` [N] graph order, None = one
-    structure).  -> (energy, dE/dpos_g | None, dE/deps | None); the energy keeps its graph in training mode."""
+    structure).  -> (energy, dE/dpos_g | None, dE/deps | None); the energy keeps its graph in training mode.
+
+    ``halo`` / ``split`` (sharded path; ``g`` = ``split.graph``): the readout is summed over THIS rank's owned rows, the
+    ghost rows are refreshed by ``halo.refresh`` in every layer, and ``halo.anchor`` is among the differentiated inputs, so
+    the backward of every refresh runs on every rank; dE/dpos_g then covers the local cloud, ghost rows included."""
     from . import ops
     with torch.enable_grad():
         p = pos_g.detach().float().requires_grad_(forces)
         eps = torch.zeros((n_strain, 3, 3), dtype=torch.float32, device=p.device, requires_grad=True) if n_strain else None
         geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p, strain=eps, structure=structure)  # differentiable Y, d, A
-        e_node = net(x_g, g, geometry=geometry, **(cutoff_kw or {}))
+        e_node = net(x_g, g, geometry=geometry, halo=halo, split=split, **(cutoff_kw or {}))
+        if halo is not None:
+            e_node = e_node[halo.owned_new]
         if seg is None:
             energy = e_node[:, 0].sum()
         else:
             energy = torch.zeros(n_seg, dtype=e_node.dtype, device=e_node.device).index_add(0, seg, e_node[:, 0])
-        leaves = ([p] if forces else []) + ([eps] if eps is not None else [])
+        leaves = ([p] if forces else []) + ([eps] if eps is not None else []) + ([] if halo is None else [halo.anchor])
         grads = list(torch.autograd.grad(energy.sum(), leaves, retain_graph=net.training))
     gpos = grads.pop(0) if forces else None
     geps = grads.pop(0) if eps is not None else None
@@ -218,4 +225,62 @@ class PeriodicEnergyModel(nn.Module):
         if stress:
             V = float(g.volume) if g.cell is not None else float(g.box[0]) * float(g.box[1]) * float(g.box[2])
             out.append((geps[0].double() / V).float())
+        return tuple(out)
+
+
+class ShardedEnergyModel(nn.Module):
+    """``PeriodicEnergyModel``'s energy, forces, virial and stress for a cloud sharded over ranks by a ``sharding.GridHalo``
+    (open or periodic) or ``MortonHalo``: every rank passes its OWNED particles and gets the total energy, the forces on
+    its owned particles and the box's virial / stress.  ``.net`` is the same ``SEGNN(..., "1x0e", ...)``: a state dict of
+    ``PeriodicEnergyModel`` loads as it is.  Gradients cross the ghost refresh of every layer by ``Halo.refresh``; an
+    owned particle's force also collects what its ghost copies on other ranks (and its own periodic images) received
+    (``Halo.reduce_ghosts``).  fp32, first order; no envelope, no neighbour list, and the exchanges of the backward are
+    not overlapped with compute."""
+
+    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2):
+        super().__init__()
+        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax)
+
+    def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, halo, forces: bool = False, virial: bool = False,
+                stress: bool = False):
+        """x [n, in_dim], pos [n,3] fp32: the particles this rank owns (``halo.owner_of``), caller order.  Every rank of
+        the halo's group calls with the same flags.  -> the 0-d TOTAL energy (all-reduced), then whichever of forces
+        [n,3] (= -dE_total/dpos of the owned particles, caller order), virial W [3,3] (= -dE_total/deps, all-reduced,
+        not symmetrised) and stress [3,3] (= -W / V, V = the volume of the halo's box) were requested, in that order.
+        ``stress=True`` needs a ``GridHalo`` periodic on all three axes (ValueError otherwise).
+
+        With nothing requested under ``torch.no_grad()`` the fused inference path runs.  In training mode the energy
+        returned is ``E_local + (E_total - E_local).detach()``: its value is the total, and ``loss.backward()`` on every
+        rank -- each exactly once, the refreshes exchange gradients -- leaves each rank's share of dE_total/dtheta in
+        ``.grad``; ``sharding.all_reduce_grads(model, halo.group)`` sums the shares."""
+        from .sharding import GridHalo, all_reduce_sum
+        if stress and not (isinstance(halo, GridHalo) and halo.periodic == 7):
+            raise ValueError("stress is defined for a GridHalo periodic on all three axes; use virial=True otherwise")
+        lpos, lx = halo.setup(pos, x, r)
+        lo, hi = halo.local_bounds(r)
+        g = radius_graph(lpos, r, lo, hi)            # open graph over [owned (wrapped) | ghosts and images]
+        halo.renumber(g.perm)
+        split = halo.split_graph(g)
+        perm = g.perm.long()
+        gpos = geps = None
+        if not (forces or virial or stress):
+            e_local = self.net(lx[perm], g, halo=halo, split=split)[halo.owned_new, 0].sum()
+        else:
+            e_local, gpos, geps = _energy_and_gradients(self.net, lx[perm], split.graph, lpos[perm], None, 1, forces,
+                                                        1 if (virial or stress) else 0, None, halo=halo, split=split)
+        parts = [e_local.detach().reshape(1)] + ([geps.reshape(9)] if geps is not None else [])
+        total = all_reduce_sum(torch.cat(parts), halo.group)
+        energy = total[0]
+        if self.training and e_local.requires_grad:
+            energy = e_local + (energy - e_local.detach())
+        if not (forces or virial or stress):
+            return energy
+        out = [energy]
+        if forces:
+            out.append(-halo.reduce_ghosts(gpos))
+        if virial:
+            out.append(-total[1:].view(3, 3))
+        if stress:
+            V = math.prod(float(halo.hi[a]) - float(halo.lo[a]) for a in range(3))
+            out.append((total[1:].view(3, 3).double() / V).float())
         return tuple(out)

@@ -86,7 +86,8 @@ class SEGNNLayer(nn.Module):
 
     def forward(self, h, g: RadiusGraph, Y, d, A, h_scale=None, halo=None, split=None, w=None):
         """-> (h_next, operand scale of h_next | None).  ``halo`` / ``split`` (sharding.Halo / SplitGraph): the layer
-        refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges.
+        refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges; a call
+        that needs a gradient refreshes out of place through ``halo.refresh`` (differentiable, blocking) instead.
 
         ``w`` [E] (``ops.cutoff_envelope``): the messages are summed with these edge weights, a_i = sum_e w_e m_e
         (``ops.segment_sum(weight=)``).  The one-launch message kernel and the scatter epilogue of message TP #2 sum with
@@ -117,7 +118,9 @@ class SEGNNLayer(nn.Module):
         r16u = self.fused and inference and (r16 or (one_launch and self.fused_update_available()))   # update product
         if h.dtype == torch.bfloat16 and not ((one_launch or r16) and r16u):
             raise RuntimeError("bf16 storage needs the fused MFMA kernels (inference; hidden 32, or 64 at l_max = 2)")
-        if halo is not None and not (one_launch and split is not None):
+        if halo is not None and not inference:
+            h = halo.refresh(h)  # differentiable refresh, out of place: ghost-row gradients return to their owners
+        elif halo is not None and not (one_launch and split is not None):
             halo.exchange(h)  # blocking refresh of the ghost rows, in place
         if one_launch and halo is not None and split is not None:
             # the refresh is posted first; interior edges (owned src) run while it is in flight, boundary edges after it

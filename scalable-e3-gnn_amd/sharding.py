@@ -15,6 +15,10 @@ box, wrapped modulo ``dims`` on periodic axes, and ``t`` (whole box lengths per 
   * ``start`` / ``finish`` — once per layer: the refreshed features of the boundary particles are posted (grouped
                      isend/irecv), the interior edges' message kernel runs meanwhile, ``finish`` waits and writes the ghost
                      rows of ``h`` IN PLACE (inference only: see ``finish``), then the boundary edges run.
+  * ``refresh``    — once per layer when a gradient is needed: the same exchange, blocking and OUT of place
+                     (``csrc/e3_halo_grad.hip``), as an autograd node whose backward sends the ghost rows' gradients back
+                     along the same entries and sums them into their owners' rows in a fixed order; ``reduce_ghosts`` does
+                     that for a per-row quantity such as dE/dpos, ``all_reduce_grads`` sums parameter gradients.
 
 The exchange above needs only the entry table and is the base class ``Halo``.  Three layouts add their geometry and selection:
 
@@ -220,6 +224,99 @@ class SplitGraph:
     dropped: int                  # edges into ghost rows that were removed
 
 
+def halo_refresh_torch(h, recv, recv_idx):
+    """Torch restatement of ``e3_halo_refresh`` (any device): the ghost rows ``recv_idx`` of a copy of ``h`` <- ``recv``."""
+    return h.clone().index_copy_(0, recv_idx, recv)
+
+
+def halo_reduce_torch(g, back, recv_idx, send_idx):
+    """Torch restatement of ``e3_halo_reduce`` (any device): ``g`` with its ghost rows zeroed, plus ``back[k]`` added to row
+    ``send_idx[k]``."""
+    return g.clone().index_fill_(0, recv_idx, 0).index_add_(0, send_idx, back)
+
+
+def _rows(t):
+    return t if t.stride(-1) == 1 or t.shape[0] == 0 else t.contiguous()
+
+
+def halo_refresh(h, recv, slot, recv_idx):
+    """``out[i] = slot[i] < 0 ? h[i] : recv[slot[i]]`` -> a new contiguous [n, D] tensor (``recv_idx``: the rows with a
+    slot, in slot order).  ROCm tensors: ``e3_halo_refresh`` (csrc/e3_halo_grad.hip; row-strided views are read in place);
+    CPU tensors: ``halo_refresh_torch``."""
+    if not h.is_cuda:
+        return halo_refresh_torch(h, recv, recv_idx)
+    from . import _lib
+    h, recv = _rows(h), _rows(recv)
+    n, D = h.shape
+    out = torch.empty((n, D), dtype=h.dtype, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.check(_lib.load().e3_halo_refresh(
+            h.data_ptr(), h.stride(0), recv.data_ptr() if recv.shape[0] else None, max(recv.stride(0), D), recv.shape[0],
+            slot.data_ptr(), n, D, _lib.dtype_code(h.dtype), out.data_ptr(), D,
+            torch.cuda.current_stream(h.device).cuda_stream), "e3_halo_refresh")
+    return out
+
+
+def halo_reduce(g, back, slot, red_ptr, red_k, recv_idx, send_idx):
+    """``out[i] = (slot[i] < 0 ? g[i] : 0) + sum of back[k] over the k of row i`` (``red_ptr`` / ``red_k``: ``send_idx``
+    grouped by row, k ascending) -> a new contiguous [n, D] tensor.  ROCm tensors: ``e3_halo_reduce``; CPU tensors:
+    ``halo_reduce_torch``."""
+    if not g.is_cuda:
+        return halo_reduce_torch(g, back, recv_idx, send_idx)
+    from . import _lib
+    g, back = _rows(g), _rows(back)
+    n, D = g.shape
+    out = torch.empty((n, D), dtype=g.dtype, device=g.device)
+    nb = back.shape[0]
+    with torch.cuda.device(g.device):
+        _lib.check(_lib.load().e3_halo_reduce(
+            g.data_ptr(), g.stride(0), back.data_ptr() if nb else None, max(back.stride(0), D), nb, slot.data_ptr(),
+            red_ptr.data_ptr(), red_k.data_ptr() if nb else None, n, D, _lib.dtype_code(g.dtype), out.data_ptr(), D,
+            torch.cuda.current_stream(g.device).cuda_stream), "e3_halo_reduce")
+    return out
+
+
+class _HaloRefreshFn(torch.autograd.Function):
+    """``Halo.refresh``: forward = exchange + ``halo_refresh``, backward = reverse exchange + ``halo_reduce``."""
+
+    @staticmethod
+    def forward(ctx, h, anchor, halo):
+        ctx.halo = halo
+        return halo._forward(h)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.halo._reverse(g), torch.zeros_like(ctx.halo.anchor), None
+
+
+def all_reduce_sum(t, group=None):
+    """Sum of ``t`` over the ranks of ``group`` -> a new tensor on ``t``'s device (host-staged under gloo, as the halo's
+    transfers are); ``t`` itself without a process group."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return t
+    buf = t.cpu() if t.is_cuda and dist.get_backend(group) == "gloo" else t.clone()
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf.to(t.device)
+
+
+def all_reduce_grads(module, group=None):
+    """Sum the parameter gradients of ``module`` over the ranks of ``group`` in place (one all-reduce of the flattened
+    gradients; a parameter without a gradient on this rank counts as zero and gets one).  After ``loss.backward()`` on
+    every rank, with the training-mode energy of ``ShardedEnergyModel`` in the loss, every rank holds dE_total/dtheta.
+    Without a process group (world 1) nothing is exchanged."""
+    params = [p for p in module.parameters() if p.requires_grad]
+    if not params:
+        return
+    for p in params:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+    flat = all_reduce_sum(torch.cat([p.grad.reshape(-1) for p in params]), group)
+    o = 0
+    for p in params:
+        p.grad.copy_(flat[o:o + p.numel()].view_as(p.grad))
+        o += p.numel()
+
+
 def _world_rank(group):
     return (dist.get_world_size(group), dist.get_rank(group)) if dist.is_initialized() else (1, 0)
 
@@ -240,6 +337,8 @@ class Halo:
         self.world, self.rank = _world_rank(group)
         self.n_owned = 0
         self.bytes_last_exchange = 0
+        self.anchor = None          # see ``refresh``: the leaf that keeps every refresh in a backward pass
+        self._grad_maps = None
         ent = self.images = entries
         self.neighbours = sorted({q for q, _, _ in ent if q != self.rank})
         at = {d: e for e, (_, d, _) in enumerate(ent)}
@@ -251,22 +350,29 @@ class Halo:
         self._recv_ops = sorted((ent[e][0], recv_tags[e], e) for e in self._remote)
 
     # -- p2p helpers ----------------------------------------------------------------------------------
-    def _post(self, sends, recvs):
+    def _post(self, sends, recvs, reverse=False):
         """Grouped send / recv of the remote entries (``sends[e]`` / ``recvs[e]`` by entry index), per peer in tag order;
-        empty messages are skipped on both ends (the sizes were agreed on in ``setup``)."""
-        ops = [dist.P2POp(dist.isend, sends[e], q, self.group, tag=tag) for q, tag, e in self._send_ops if sends[e].numel()]
-        ops += [dist.P2POp(dist.irecv, recvs[e], q, self.group, tag=tag) for q, tag, e in self._recv_ops if recvs[e].numel()]
+        empty messages are skipped on both ends (the sizes were agreed on in ``setup``).  ``reverse``: the way back
+        (``_reverse``) -- what entry ``e`` RECEIVED goes back to its peer under the entry's receive tag, and what was sent
+        for ``e`` is answered under its send tag, so the two ends pair up exactly as they do on the way out."""
+        send_ops, recv_ops = (self._recv_ops, self._send_ops) if reverse else (self._send_ops, self._recv_ops)
+        ops = [dist.P2POp(dist.isend, sends[e], q, self.group, tag=tag) for q, tag, e in send_ops if sends[e].numel()]
+        ops += [dist.P2POp(dist.irecv, recvs[e], q, self.group, tag=tag) for q, tag, e in recv_ops if recvs[e].numel()]
         return dist.batch_isend_irecv(ops) if ops else []
 
     def _gloo(self):
         return dist.get_backend(self.group) == "gloo"
 
-    def _start(self, sends, recvs):
+    def _start(self, sends, recvs, reverse=False):
         """Serve the self entries by local copies and post the remote ones -> ``(works, staged, posted)`` for ``_wait``.
         gloo has no device transport: device tensors are staged through host memory (rehearsal mode only); ``staged`` lists
-        the (device recv, host recv) pairs and ``posted`` keeps the send buffers referenced until the wait."""
+        the (device recv, host recv) pairs and ``posted`` keeps the send buffers referenced until the wait.  ``reverse``:
+        ``sends[e]`` holds what entry ``e`` received and ``recvs[e]`` takes the answer to what was sent for ``e``."""
         for e, m in self._self_pairs:
-            recvs[e].copy_(sends[m])
+            if reverse:
+                recvs[m].copy_(sends[e])
+            else:
+                recvs[e].copy_(sends[m])
         if not self._remote:
             return [], [], sends
         staged = []
@@ -275,7 +381,7 @@ class Halo:
             host = {e: torch.empty(recvs[e].shape, dtype=recvs[e].dtype) for e in self._remote}
             staged = [(recvs[e], host[e]) for e in self._remote]
             recvs = host
-        return self._post(sends, recvs), staged, sends
+        return self._post(sends, recvs, reverse), staged, sends
 
     @staticmethod
     def _wait(works, staged, posted):
@@ -313,6 +419,10 @@ class Halo:
             self._wait(*self._start(list(send.split(self.send_counts)), list(ghosts.split(self.recv_counts))))
             out.append(torch.cat([t, ghosts], 0))
         self._recv_idx = torch.arange(n, n + self.n_ghost, device=dev)
+        self.owned_new = torch.arange(n, device=dev)
+        self._grad_maps = None                  # built by ``renumber`` (or on first use in the setup numbering)
+        if self.anchor is None or self.anchor.device != dev:
+            self.anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
         return out[0], out[1]
 
     def renumber(self, perm: torch.Tensor):
@@ -325,7 +435,25 @@ class Halo:
         self.owned_new = inv[:n]                    # new ids of the owned particles, in their original order
         self.is_ghost = torch.zeros(perm.numel(), dtype=torch.bool, device=perm.device)
         self.is_ghost[self._recv_idx] = True
+        self._grad_maps = self._build_grad_maps(perm.numel())
         return self
+
+    def _build_grad_maps(self, n_local):
+        """Index maps of ``refresh`` / ``reduce_ghosts`` in the current numbering (once per graph build) -> (slot [n_local]
+        int32: -1 for an owned row, else the row's position in the received buffer; red_ptr [n_local + 1], red_k [total
+        sent] int32: the send list grouped by its target row, positions ascending inside a row)."""
+        dev = self._recv_idx.device
+        slot = torch.full((n_local,), -1, dtype=torch.int32, device=dev)
+        slot[self._recv_idx] = torch.arange(self.n_ghost, dtype=torch.int32, device=dev)
+        red_k = torch.sort(self._send_idx, stable=True).indices.to(torch.int32)
+        red_ptr = torch.zeros(n_local + 1, dtype=torch.int32, device=dev)
+        red_ptr[1:] = torch.cumsum(torch.bincount(self._send_idx, minlength=n_local), 0)
+        return slot, red_ptr, red_k
+
+    def _maps(self):
+        if self._grad_maps is None:
+            self._grad_maps = self._build_grad_maps(self.n_owned + self.n_ghost)
+        return self._grad_maps
 
     def ghost_fraction(self) -> float:
         return self.n_ghost / max(1, self.n_owned)
@@ -397,6 +525,51 @@ class Halo:
         """Local (graph-order) ids of the ghost rows."""
         return self._recv_idx
 
+    # -- once per layer, differentiable ---------------------------------------------------------------
+    def _forward(self, h: torch.Tensor) -> torch.Tensor:
+        """The blocking refresh, out of place: the owners' current rows arrive as in ``start`` and ONE pass writes
+        ``[owned rows of h | received rows]`` (``halo_refresh``); ``h`` is not written, its ghost rows are not read."""
+        recv = torch.empty((self.n_ghost, h.shape[1]), dtype=h.dtype, device=h.device)
+        send = h[self._send_idx]
+        self.bytes_last_exchange = sum(self.send_counts[e] for e in self._remote) * h.shape[1] * h.element_size()
+        self._wait(*self._start(list(send.split(self.send_counts)), list(recv.split(self.recv_counts))))
+        return halo_refresh(h, recv, self._maps()[0], self._recv_idx)
+
+    def _reverse(self, t: torch.Tensor) -> torch.Tensor:
+        """The transpose of the refresh: the ghost rows of ``t`` [n_local, C] travel back along the entries they came by
+        (every receive list is a send and vice versa, same tags, empty messages skipped on both ends, self entries by
+        local copies) and are summed into their owners' rows (``halo_reduce``) -> [n_local, C], ghost rows zero."""
+        back = torch.empty((self._send_idx.numel(), t.shape[1]), dtype=t.dtype, device=t.device)
+        ghosts = t[self._recv_idx]
+        self._wait(*self._start(list(ghosts.split(self.recv_counts)), list(back.split(self.send_counts)), reverse=True))
+        return halo_reduce(t, back, *self._maps(), self._recv_idx, self._send_idx)
+
+    def refresh(self, h: torch.Tensor) -> torch.Tensor:
+        """Differentiable ghost refresh: -> a new ``[n_local, D]`` tensor, the owned rows of ``h`` and the owners' current
+        values in the ghost rows (``exchange`` out of place).  fp32 or fp64.  Backward: the ghost rows of the incoming
+        gradient go back to their owners (``_reverse``) and are added to the owned rows' own gradient, in a fixed order.
+        First order only.
+
+        Every rank has to run the backward of every refresh exactly once per backward pass -- its peers wait for the
+        messages -- whatever the rank owns.  Autograd runs a node only if it lies between the differentiated output and
+        one of the requested ``inputs``; so every refresh also takes ``halo.anchor``, a 0-d leaf that requires grad (its
+        gradient is zero): the output always requires grad, and a caller of ``torch.autograd.grad(..., inputs=...)``
+        puts ``halo.anchor`` among the inputs (``ShardedEnergyModel`` does).  ``backward()`` without ``inputs`` needs
+        nothing.  The result must be USED by what is differentiated on every rank -- an empty sum over no owned rows
+        counts -- and the halo must not be set up again between the forward and the backward."""
+        if h.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError(f"the differentiable refresh is fp32 / fp64, got {h.dtype}")
+        return _HaloRefreshFn.apply(h, self.anchor, self)
+
+    def reduce_ghosts(self, t: torch.Tensor) -> torch.Tensor:
+        """``t`` [n_local, C] in graph order (e.g. dE/dpos of the local cloud, C = 3: an image's position is its owner's
+        plus a constant, so the Jacobian is the identity) -> [n_owned, C] in the caller's owned order: every owned row's
+        own value plus the values of all its ghost copies on all ranks.  A collective of the halo: every rank calls it,
+        in the same order relative to other exchanges (it is not an autograd node: call it after ``autograd.grad``)."""
+        if t.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError(f"reduce_ghosts is fp32 / fp64, got {t.dtype}")
+        return self._reverse(t.detach().contiguous())[self.owned_new]
+
 
 class GridHalo(Halo):
     """Ghost-cell halo of a ``dims = (px, py, pz)`` grid of equal boxes covering ``[lo, hi)``; rank = (ix py + iy) pz + iz.
@@ -462,6 +635,11 @@ class GridHalo(Halo):
 
     def _check_cutoff(self, pos, r):
         check_cutoff(self.dims, self.lo, self.hi, self._axes, r)
+
+    def local_bounds(self, r):
+        """Box for the local ``radius_graph`` call: this rank's box widened by ``2 r`` (it holds the ghosts and images)."""
+        blo, bhi = self.box(self.rank)
+        return [v - 2 * r for v in blo], [v + 2 * r for v in bhi]
 
 
 class SlabHalo(GridHalo):
@@ -641,11 +819,7 @@ class MortonPartition:
         """Choose the splitters from the particles this process holds (any subset; with a process group the histograms of
         all ranks are summed, host-staged under gloo as the halo's transfers are).  One host read.  -> self."""
         hist = torch.bincount(self.keys(pos_owned), minlength=self.n_keys)
-        if dist.is_initialized():
-            if hist.is_cuda and dist.get_backend(group) == "gloo":
-                hist = hist.cpu()
-            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=group)
-        hist = hist.cpu()
+        hist = all_reduce_sum(hist, group).cpu()
         P, N = self.world, int(hist.sum())
         below = torch.zeros(self.n_keys + 1, dtype=torch.int64)             # below[k] = number of particles with key < k
         below[1:] = torch.cumsum(hist, 0)
