@@ -714,6 +714,33 @@ int e3_nl_update_cell(const float* pos, const int32_t* perm, const float* ref_po
                       int64_t N, int64_t E, float r, const float cell[9], float* pos4_out, int32_t* rowptr_out,
                       int32_t* src_out, int32_t* dst_out, uint32_t* stats, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * e3_nl_update_split: the prune above and e3_split_edges in one pass, for the stored graph of a shard's local cloud
+ * [owned | ghosts] (sharded_list.ShardedNeighborList).  Open mode only: the local cloud of a shard is an open graph.
+ *   inputs  : as e3_nl_update, plus is_ghost [N] uint8 (non-zero = ghost row), in the stored graph's node order.
+ *   outputs : pos4_out, rowptr_out, src_out / dst_out as e3_nl_update; src_interior / dst_interior and src_boundary /
+ *             dst_boundary (room for E each);  stats [4] uint32 (device), zeroed on the stream inside the entry:
+ *             stats[0] = the bits of max_i d2_i over ALL rows, as e3_nl_update;  stats[1] = E_kept = rowptr_out[N];
+ *             stats[2] = E_interior;  stats[3] = E_boundary = E_kept - E_interior.
+ * Contract: every output is bit for bit what e3_nl_update followed by e3_split_edges (same is_ghost) on its result
+ * produces, for any input graph, also one that still has edges into ghost rows:
+ *   - a ghost row keeps nothing; an edge of an owned row is kept iff d2 <= fl(r r), the test of e3_nl_update;
+ *   - the kept edges go to src_out / dst_out (rowptr_out is their CSR); those with an owned src also to the interior
+ *     list, those with a ghost src also to the boundary list;
+ *   - every list is in row order and a row's src keep the stored order.
+ * One count and one fill pass over the stored edges (a 16-lane group per row, the two ballots "kept" and "kept with a
+ * ghost src" give the counts and the write positions) and two exclusive sums; no atomics on the lists.  The composition
+ * reads the stored edges twice and the kept edges twice more; this entry reads the stored edges twice and nothing else.
+ * E3_ERR_INVALID_ARG as e3_nl_update, and for a NULL is_ghost when N > 0 (the interior / boundary arrays are edge arrays:
+ * they may be NULL when E = 0).  N = 0 launches nothing and writes stats = {0, 0, 0, 0} and rowptr_out[0] = 0.
+ * workspace = e3_nl_update_split_workspace_bytes(N) bytes (-1 for N outside int32).
+ * ------------------------------------------------------------------------------------------------- */
+int64_t e3_nl_update_split_workspace_bytes(int64_t N);
+int e3_nl_update_split(const float* pos, const int32_t* perm, const float* ref_pos4, const int32_t* rowptr, const int32_t* src,
+                       const uint8_t* is_ghost, int64_t N, int64_t E, float r, float* pos4_out, int32_t* rowptr_out,
+                       int32_t* src_out, int32_t* dst_out, int32_t* src_interior, int32_t* dst_interior,
+                       int32_t* src_boundary, int32_t* dst_boundary, uint32_t* stats, void* workspace, void* stream);
+
 /* =================================================================================================
  * Differentiable ghost refresh of the sharded path (sharding.Halo.refresh / reduce_ghosts): the once-per-layer refresh as
  * an out-of-place row copy, and its backward as a row sum.  Rows are [n, D] of dtype E3_F32 or E3_F64 with a leading

@@ -9,11 +9,15 @@ Public surface:
   * ``Irreps`` / ``Irrep`` / ``Instruction`` — e3nn-shaped bookkeeping (e3nn itself is optional).
   * ``NeighborList`` — Verlet list: a graph built at ``r + skin``, pruned to ``r`` on the device on every step.
   * ``ShardedEnergyModel`` — energy, forces, virial and stress of a cloud sharded over ranks (``sharding`` halos).
+  * ``ShardedNeighborList`` / ``OwnershipChanged`` — the Verlet list of a sharded cloud: halo and local graph built at
+    ``r + skin``, positions sent along the stored entries and the stored edges pruned and split on the device on every step.
 Everything computes through ``lib/libe3gnn_hip.so`` (C ABI: ``include/e3gnn.h``); there is no CPU path.
 """
 from .irreps import Instruction, Irrep, Irreps, as_blocks  # noqa: F401
 from .l1_tensor_prod import L1TensorProduct  # noqa: F401
 from .neighbor_list import NeighborList  # noqa: F401
 from .batched import ShardedEnergyModel  # noqa: F401
+from .sharded_list import OwnershipChanged, ShardedNeighborList  # noqa: F401
 
-__all__ = ["L1TensorProduct", "Irreps", "Irrep", "Instruction", "as_blocks", "NeighborList", "ShardedEnergyModel"]
+__all__ = ["L1TensorProduct", "Irreps", "Irrep", "Instruction", "as_blocks", "NeighborList", "ShardedEnergyModel",
+           "ShardedNeighborList", "OwnershipChanged"]

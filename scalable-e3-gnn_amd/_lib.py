@@ -186,6 +186,11 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e3_nl_update_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_float, Float9,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ... and the same walk with the shard's edge split (is_ghost after src; seven lists, stats [4])
+    "e3_nl_update_split_workspace_bytes": (c_int64, [c_int64]),
+    "e3_nl_update_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                   ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     # differentiable ghost refresh: out-of-place row copy by slot, and its backward (row sum over a CSR of the send list)
     "e3_halo_refresh": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
                                 c_int64, c_void_p]),

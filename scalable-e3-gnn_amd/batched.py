@@ -234,15 +234,18 @@ class ShardedEnergyModel(nn.Module):
     its owned particles and the box's virial / stress.  ``.net`` is the same ``SEGNN(..., "1x0e", ...)``: a state dict of
     ``PeriodicEnergyModel`` loads as it is.  Gradients cross the ghost refresh of every layer by ``Halo.refresh``; an
     owned particle's force also collects what its ghost copies on other ranks (and its own periodic images) received
-    (``Halo.reduce_ghosts``).  fp32, first order; no envelope, no neighbour list, and the exchanges of the backward are
-    not overlapped with compute."""
+    (``Halo.reduce_ghosts``).  fp32, first order; the exchanges of the backward are not overlapped with compute.
+    ``envelope`` (the exponent p, e.g. 6): the smooth cutoff envelope of ``PeriodicEnergyModel``; an enveloped model runs
+    the per-product kernels with the blocking ghost refresh -- the overlap of the refresh with the interior edges belongs
+    to the one-launch message kernel, which has no envelope."""
 
-    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2):
+    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2,
+                 envelope: int | None = None):
         super().__init__()
-        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax)
+        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, halo, forces: bool = False, virial: bool = False,
-                stress: bool = False):
+                stress: bool = False, skin: float = 0.0, neighbors=None):
         """x [n, in_dim], pos [n,3] fp32: the particles this rank owns (``halo.owner_of``), caller order.  Every rank of
         the halo's group calls with the same flags.  -> the 0-d TOTAL energy (all-reduced), then whichever of forces
         [n,3] (= -dE_total/dpos of the owned particles, caller order), virial W [3,3] (= -dE_total/deps, all-reduced,
@@ -252,22 +255,47 @@ class ShardedEnergyModel(nn.Module):
         With nothing requested under ``torch.no_grad()`` the fused inference path runs.  In training mode the energy
         returned is ``E_local + (E_total - E_local).detach()``: its value is the total, and ``loss.backward()`` on every
         rank -- each exactly once, the refreshes exchange gradients -- leaves each rank's share of dE_total/dtheta in
-        ``.grad``; ``sharding.all_reduce_grads(model, halo.group)`` sums the shares."""
+        ``.grad``; ``sharding.all_reduce_grads(model, halo.group)`` sums the shares.
+
+        ``skin`` (enveloped models only): the halo is set up and the local graph built at ``r + skin`` -- the halo's
+        cutoff checks apply to that radius -- while the envelope's radius stays ``r``; the outputs are those of
+        ``skin = 0`` up to rounding.
+
+        ``neighbors`` (a ``ShardedNeighborList(r, skin, halo)``): the local cloud is ``neighbors.update(pos, x)`` -- halo
+        and graph built at the list's ``r + skin`` once, then positions sent along the stored entries and the stored
+        edges pruned and split on the device while no particle on any rank has moved half the skin -- for any model,
+        enveloped or not; ``r`` and ``halo`` must be the list's and ``skin`` stays 0 (ValueError otherwise).  May raise
+        ``OwnershipChanged`` (on every rank) when the list has to rebuild."""
         from .sharding import GridHalo, all_reduce_sum
         if stress and not (isinstance(halo, GridHalo) and halo.periodic == 7):
             raise ValueError("stress is defined for a GridHalo periodic on all three axes; use virial=True otherwise")
-        lpos, lx = halo.setup(pos, x, r)
-        lo, hi = halo.local_bounds(r)
-        g = radius_graph(lpos, r, lo, hi)            # open graph over [owned (wrapped) | ghosts and images]
-        halo.renumber(g.perm)
-        split = halo.split_graph(g)
-        perm = g.perm.long()
+        cut = _cutoff_kw(self.net, r)
+        if neighbors is not None:
+            if float(r) != neighbors.r:
+                raise ValueError(f"r = {r} is not the radius of neighbors= ({neighbors.r})")
+            if halo is not neighbors.halo:
+                raise ValueError("halo= is not the halo of neighbors=: the list holds the index state of the halo it was "
+                                 "made with")
+            if skin != 0.0:
+                raise ValueError("skin= must stay 0 with neighbors=: the list has a skin of its own and returns the graph "
+                                 "at r")
+            cloud = neighbors.update(pos, x)
+            split, x_g, pos_g = cloud.split, cloud.x, cloud.pos
+        else:
+            r = _skin_radius(self.net, r, skin)
+            lpos, lx = halo.setup(pos, x, r)
+            lo, hi = halo.local_bounds(r)
+            g = radius_graph(lpos, r, lo, hi)            # open graph over [owned (wrapped) | ghosts and images]
+            halo.renumber(g.perm)
+            split = halo.split_graph(g)
+            perm = g.perm.long()
+            x_g, pos_g = lx[perm], lpos[perm]
         gpos = geps = None
         if not (forces or virial or stress):
-            e_local = self.net(lx[perm], g, halo=halo, split=split)[halo.owned_new, 0].sum()
+            e_local = self.net(x_g, split.graph, halo=halo, split=split, **cut)[halo.owned_new, 0].sum()
         else:
-            e_local, gpos, geps = _energy_and_gradients(self.net, lx[perm], split.graph, lpos[perm], None, 1, forces,
-                                                        1 if (virial or stress) else 0, None, halo=halo, split=split)
+            e_local, gpos, geps = _energy_and_gradients(self.net, x_g, split.graph, pos_g, None, 1, forces,
+                                                        1 if (virial or stress) else 0, None, cut, halo=halo, split=split)
         parts = [e_local.detach().reshape(1)] + ([geps.reshape(9)] if geps is not None else [])
         total = all_reduce_sum(torch.cat(parts), halo.group)
         energy = total[0]

@@ -47,6 +47,10 @@ def _make_tp(in_irreps, out_irreps, lmax: int):
     return SHTensorProduct(in_irreps, out_irreps, lmax_sh=2)
 
 
+_ENVELOPE_NEEDS_BOTH = ("the cutoff envelope on the sharded path works on the split graph with a refresh per layer: halo= and "
+                        "split= (halo.split_graph) come together; one without the other is not implemented")
+
+
 class SEGNNLayer(nn.Module):
     _warned_unfused = False   # the fused -> unfused switch is announced once per process
 
@@ -91,10 +95,12 @@ class SEGNNLayer(nn.Module):
 
         ``w`` [E] (``ops.cutoff_envelope``): the messages are summed with these edge weights, a_i = sum_e w_e m_e
         (``ops.segment_sum(weight=)``).  The one-launch message kernel and the scatter epilogue of message TP #2 sum with
-        weight 1 and are not used; fp32 only, not sharded."""
+        weight 1 and are not used; fp32 only.  Sharded (``halo`` / ``split``): ``g`` is ``split.graph`` and the refresh is
+        the blocking one (``halo.exchange``, or ``halo.refresh`` with a gradient) -- the interior / boundary overlap is the
+        one-launch kernel's and is not available with an envelope; ``halo`` and ``split`` come together there."""
         if w is not None:
-            if halo is not None or split is not None:
-                raise NotImplementedError("the cutoff envelope is not implemented on the sharded path (halo / split)")
+            if (halo is None) != (split is None):
+                raise NotImplementedError(_ENVELOPE_NEEDS_BOTH)
             if h.dtype != torch.float32:
                 raise RuntimeError("the cutoff envelope is fp32: bf16 storage has no weighted aggregation")
         if (halo is not None or split is not None) and (g.box is not None or g.cell is not None):
@@ -264,19 +270,29 @@ class SEGNN(nn.Module):
 
     def _forward_enveloped(self, x, g, geometry, halo, split, cutoff):
         """The forward with the cutoff envelope: w = u_p(d / cutoff) once from the edge lengths, the enveloped node
-        attribute in place of the mean, and w on every layer's aggregation."""
-        if halo is not None or split is not None:
-            raise NotImplementedError("the cutoff envelope is not implemented on the sharded path (halo / split)")
+        attribute in place of the mean, and w on every layer's aggregation.  Sharded: the graph is ``split.graph`` (the
+        edges into ghost rows removed) and every layer refreshes the ghost rows before its messages, blocking: the
+        overlap of the refresh with the interior edges needs the one-launch message kernel, which has no envelope.
+        ``halo`` and ``split`` come together: the weights and the enveloped node attribute are those of ``split.graph``,
+        and without the refresh of ``halo`` its ghost rows would be stale."""
+        if (halo is None) != (split is None):
+            raise NotImplementedError(_ENVELOPE_NEEDS_BOTH)
         if x.dtype != torch.float32:
             raise RuntimeError("the cutoff envelope is fp32: bf16 storage has no weighted aggregation")
+        if split is not None:
+            g = split.graph
         if geometry is not None:
             Y, d, _ = geometry
         else:
             Y, d, _ = ops.edge_geometry(g, lmax=self.lmax, want_node_attr=False, want_edge=True)
         w = ops.cutoff_envelope(d, cutoff, self.envelope)
+        # sharded: a ghost row has no incoming edge in split.graph, so its A is that of an isolated node; it only enters
+        # the ghost row's own update, whose result the next refresh overwrites and no owned result reads
         A = ops.enveloped_node_attr(Y, w, g)
         h = self.embed(x, A)
         sc = None
         for layer in self.layers:
-            h, sc = layer(h, g, Y, d, A, sc, w=w)
+            if halo is not None:
+                sc = None  # the ghost rows are about to change: the scale of the previous layer's output is stale
+            h, sc = layer(h, g, Y, d, A, sc, halo=halo, split=split, w=w)
         return self.readout(h, A)

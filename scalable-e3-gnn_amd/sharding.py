@@ -12,6 +12,10 @@ box, wrapped modulo ``dims`` on periodic axes, and ``t`` (whole box lengths per 
   * ``split_graph``— once per graph build: edges INTO ghost rows are dropped (their sums would be thrown away), the rest is
                      split into *interior* edges (owned src: computable before the layer's exchange has landed) and
                      *boundary* edges (ghost src).  On a GPU one HIP launch pair classifies and compacts (``e3_split_edges``).
+  * ``update_positions`` — once per step between two builds (``sharded_list.ShardedNeighborList``): the current positions
+                     and features travel along the entries, send lists and counts of the last ``setup`` -- no selection, no
+                     count exchange, no host read; owned rows continue their build-time local coordinates across periodic
+                     faces, a ghost is its owner's local position plus the entry's shift.  ``generation`` counts the setups.
   * ``start`` / ``finish`` — once per layer: the refreshed features of the boundary particles are posted (grouped
                      isend/irecv), the interior edges' message kernel runs meanwhile, ``finish`` waits and writes the ghost
                      rows of ``h`` IN PLACE (inference only: see ``finish``), then the boundary edges run.
@@ -336,6 +340,7 @@ class Halo:
         self.group = group
         self.world, self.rank = _world_rank(group)
         self.n_owned = 0
+        self.generation = 0         # bumped by every ``setup``: how a ShardedNeighborList notices a foreign one
         self.bytes_last_exchange = 0
         self.anchor = None          # see ``refresh``: the leaf that keeps every refresh in a backward pass
         self._grad_maps = None
@@ -398,7 +403,11 @@ class Halo:
         self._check_cutoff(pos, r)                                        # ValueError before any transfer
         dev = pos.device
         n = pos.shape[0]
+        self.generation += 1
+        self._build_pos = pos.detach().clone()                            # the caller's coordinates (``update_positions``)
         pos, idx, cnt, gpos = self._select(pos, r)                        # host sync #1
+        self._build_local = pos                                           # ... and the owned rows of the local cloud
+        self._send_shift = None
         # the counts: on the CPU for gloo, else on the device; self entries are local copies; ONE read of [out | in]
         cdev = dev if self._remote and not self._gloo() else torch.device("cpu")
         co = torch.as_tensor(cnt, dtype=torch.int64).to(cdev)
@@ -424,6 +433,61 @@ class Halo:
         if self.anchor is None or self.anchor.device != dev:
             self.anchor = torch.zeros((), dtype=torch.float32, device=dev, requires_grad=True)
         return out[0], out[1]
+
+    # -- once per step between two builds --------------------------------------------------------------
+    def _check_like_build(self, pos):
+        if pos.shape != self._build_pos.shape or pos.device != self._build_pos.device:
+            raise ValueError(f"positions {tuple(pos.shape)} on {pos.device}: the last setup saw "
+                             f"{tuple(self._build_pos.shape)} on {self._build_pos.device}")
+
+    def displacement(self, pos: torch.Tensor) -> torch.Tensor:
+        """``pos`` [n,3] (the owned particles, the order of the last ``setup``) -> their displacement since that ``setup``
+        [n,3]: ``d = pos - pos_at_build``, and on every periodic axis of a ``GridHalo`` its minimum image in the rint form
+        of ``e3_nl_update`` (include/e3gnn.h), ``fl(d - fl(L rint(fl(d invL))))``, every fp32 operation rounded once: a
+        caller that re-wraps its coordinates has not moved."""
+        self._check_like_build(pos)
+        d = pos - self._build_pos
+        for a in range(3):
+            if (self.periodic >> a) & 1:
+                L = _f32(_f32(self.hi[a]) - _f32(self.lo[a]))
+                invL = float(np.float32(1.0) / np.float32(L))
+                d[:, a] = d[:, a] - L * torch.round(d[:, a] * invL)      # torch.round is rint (half to even)
+        return d
+
+    def update_positions(self, pos: torch.Tensor, feats: torch.Tensor | None = None, disp: torch.Tensor | None = None):
+        """The local cloud of the last ``setup`` at the current positions, along the stored entries: no selection, no count
+        exchange, no host read.  pos [n,3] (feats [n,F]) of the owned particles in the order ``setup`` saw -> (local_pos,
+        local_feats | None) = ``[owned | ghosts]`` in ``setup``'s order.
+
+        Owned rows hold the continuation of the build-time local coordinates: ``pos`` itself on an open axis, and on a
+        periodic axis ``fl(ref + displacement)`` (``displacement``) with ``ref`` the wrapped coordinate ``setup`` returned
+        -- the image of the current position nearest to where the particle was in the local cloud, so a re-wrapped
+        coordinate or a particle that crosses a periodic face moves nothing discontinuously (the local cloud is an open
+        graph: an owned row may leave ``[lo, hi)``).  Ghost rows hold ``fl(owner's local position + the entry's shift)``,
+        the shift ``setup`` used: zero for open and Morton halos, ``-t`` for periodic images.  ``feats`` travel the same
+        way, unshifted.  ``disp``: ``displacement(pos)`` when the caller has it already.  Every rank of the group calls
+        it (it is an exchange); who owns what is frozen since the ``setup``."""
+        self._check_like_build(pos)
+        local = pos
+        if self.periodic:
+            d = self.displacement(pos) if disp is None else disp
+            local = pos.clone()
+            for a in range(3):
+                if (self.periodic >> a) & 1:
+                    local[:, a] = self._build_local[:, a] + d[:, a]
+        send = local[self.sel]
+        if any(v != 0.0 for _, _, t in self.images for v in t):
+            if self._send_shift is None:
+                # per sent row the shift of its entry; sizes are host integers since ``setup``: an upload, not a read
+                esh = torch.tensor([[-v if v else 0.0 for v in t] for _, _, t in self.images], dtype=local.dtype)
+                self._send_shift = esh.repeat_interleave(torch.tensor(self.send_counts), 0).to(local.device)
+            send = send + self._send_shift
+        out = []
+        for t, snd in ((local, send),) + (() if feats is None else ((feats, feats[self.sel]),)):
+            ghosts = torch.empty((self.n_ghost, t.shape[1]), dtype=t.dtype, device=t.device)
+            self._wait(*self._start(list(snd.split(self.send_counts)), list(ghosts.split(self.recv_counts))))
+            out.append(torch.cat([t, ghosts], 0))
+        return out[0], (out[1] if feats is not None else None)
 
     def renumber(self, perm: torch.Tensor):
         """The graph builder renumbers the local cloud (``perm[new] = old``): translate the halo index lists."""
