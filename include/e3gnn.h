@@ -311,6 +311,30 @@ int e3_morton_select_fill(const float* pos, int64_t n, const float lo[3], const 
                           const int32_t* splitters, int n_ranks, int self_rank, int64_t total, int32_t* idx, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* Migration of particles between ranks (sharding.Halo.migrate): split the rows of a row table by a GIVEN owner.
+ *   table  : int32 [n, W], row-major: whatever the caller keeps per particle, viewed as 32-bit words (sharding.pack_rows).
+ *   owner  : int32 [n] (device): the rank each row belongs to now.  An input -- the ownership rule is halo.owner_of and
+ *            nothing here restates it.  A row whose owner lies outside [0, n_ranks) is INVALID: it is counted, never
+ *            copied, and nothing is indexed by its owner.
+ *   count  : counts [n_ranks + 1] (device): counts[q] = the rows with owner == q (counts[self_rank] = the stayers),
+ *            counts[n_ranks] = the invalid rows; the sum is n.
+ *   output : stay [counts[self_rank], W] = the rows with owner == self_rank in their original order; send [.., W] = the
+ *            valid rows with owner != self_rank, grouped by destination rank ascending, ascending row ids inside a group.
+ *            Plain stores in a fixed order: the same inputs give the same bytes.  Rows past the counts are not written.
+ * Call sequence: e3_migrate_workspace_bytes -> e3_migrate_count (counts) -> read counts -> e3_migrate_fill (the same
+ *   workspace, owner, n_ranks and self_rank; `counts` = the HOST copy of what was read; stay_rows / send_rows = the
+ *   capacities of stay / send in rows).
+ * E3_ERR_INVALID_ARG before any launch (and before any HIP call) for n_ranks outside [1, E3_MORTON_MAX_RANKS], self_rank
+ * outside the ranks, n < 0, n * n_ranks >= 2^31 - 1, a NULL pointer that would be used, a workspace too small; fill also
+ * for W outside [1, 4096], n * W >= 2^31 - 1, a negative count, counts that do not sum to n, and stay_rows / send_rows
+ * smaller than the counts imply.  n = 0 is legal: count zeroes the counts, fill launches nothing. */
+int64_t e3_migrate_workspace_bytes(int64_t n, int n_ranks);
+int e3_migrate_count(const int32_t* owner, int64_t n, int n_ranks, int self_rank, int32_t* counts, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int e3_migrate_fill(const int32_t* table, const int32_t* owner, int64_t n, int W, int n_ranks, int self_rank,
+                    const int32_t* counts, int64_t stay_rows, int64_t send_rows, int32_t* stay, int32_t* send, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* =================================================================================================
  * General SH tensor product, l <= 2 (builder-defined generalisation of the reference operator, which
  * hard-asserts lmax == 1, l1_tensor_prod.py:13-14).

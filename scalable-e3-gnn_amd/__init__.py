@@ -10,7 +10,11 @@ Public surface:
   * ``NeighborList`` — Verlet list: a graph built at ``r + skin``, pruned to ``r`` on the device on every step.
   * ``ShardedEnergyModel`` — energy, forces, virial and stress of a cloud sharded over ranks (``sharding`` halos).
   * ``ShardedNeighborList`` / ``OwnershipChanged`` — the Verlet list of a sharded cloud: halo and local graph built at
-    ``r + skin``, positions sent along the stored entries and the stored edges pruned and split on the device on every step.
+    ``r + skin``, positions sent along the stored entries and the stored edges pruned and split on the device on every step;
+    ``nl.redistribute(pos, x, *rows)`` before the model moves the particles that left their owner's region to their new rank
+    when a rebuild is due (``Halo.migrate``), so a trajectory rebuilds through a crossing.
+  * ``pack_rows`` / ``unpack_rows`` — the per-particle tensors of a caller as one int32 row table and back, bit for bit:
+    what a migration moves (``sharding.Halo.migrate``, ``sharding.migrate_rows``).
 Everything computes through ``lib/libe3gnn_hip.so`` (C ABI: ``include/e3gnn.h``); there is no CPU path.
 """
 from .irreps import Instruction, Irrep, Irreps, as_blocks  # noqa: F401
@@ -18,6 +22,7 @@ from .l1_tensor_prod import L1TensorProduct  # noqa: F401
 from .neighbor_list import NeighborList  # noqa: F401
 from .batched import ShardedEnergyModel  # noqa: F401
 from .sharded_list import OwnershipChanged, ShardedNeighborList  # noqa: F401
+from .sharding import pack_rows, unpack_rows  # noqa: F401
 
 __all__ = ["L1TensorProduct", "Irreps", "Irrep", "Instruction", "as_blocks", "NeighborList", "ShardedEnergyModel",
-           "ShardedNeighborList", "OwnershipChanged"]
+           "ShardedNeighborList", "OwnershipChanged", "pack_rows", "unpack_rows"]

@@ -72,6 +72,11 @@ SIGNATURES = {
                                        c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "e3_morton_select_fill": (c_int, [c_void_p, c_int64, Float3, Float3, Int3, ctypes.c_float, POINTER(c_int32), c_int,
                                       c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    # migration between ranks (owner = device int32[n]; counts of the fill = host int32[n_ranks + 1])
+    "e3_migrate_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "e3_migrate_count": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_migrate_fill": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, POINTER(c_int32), c_int64, c_int64,
+                                c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "e3_tp_plan_create": (c_int, [POINTER(c_int32), c_int, c_int, POINTER(c_int32), c_int, POINTER(c_void_p)]),
     "e3_tp_plan_destroy": (c_int, [c_void_p]),
     "e3_tp_in1_dim": (c_int, [c_void_p]),

@@ -9,7 +9,10 @@ pass on the device (``e3_nl_update_split``), with one host read of the three cou
 
 Ownership is frozen between two builds, and a halo ``r + skin`` wide is complete only for particles inside their owner's
 region: a build checks ``halo.owner_of(pos) == rank`` for every owned particle and raises ``OwnershipChanged`` on EVERY rank
-when any rank has a stray (the caller redistributes and calls again; migration itself is not the list's business).
+when any rank has a stray.  ``redistribute(pos, x, *rows)``, called before the model on every step, is the way through a
+crossing: it takes the same shared decision, and when a rebuild is due it moves the strays to their new owners first
+(``Halo.migrate``), so the build that follows finds none; while the list holds it hands its decision to the ``update`` of the
+same positions and costs nothing more.  ``update`` without it behaves as before.
 
 The rounding budget behind ``skin / 2`` and ``MAX_COORD_OVER_SKIN``: DESIGN.md §4.4b.
 """
@@ -31,7 +34,7 @@ _STALE = 0xffffffff   # the all-ones word: a NaN pattern, above every threshold
 
 class OwnershipChanged(RuntimeError):
     """An owned particle has left its owner's region (raised by every rank of the halo's group at once): redistribute the
-    particles by ``halo.owner_of`` and call again."""
+    particles by ``halo.owner_of`` and call again -- ``ShardedNeighborList.redistribute`` before every ``update`` does."""
 
 
 @dataclass
@@ -108,9 +111,11 @@ class ShardedNeighborList:
         self.graph_builder = graph_builder
         self.threshold = verlet_threshold(self.skin)
         self.builds = self.updates = 0
+        self.migrations = self.migrated = 0     # redistributions that moved something; ``halo.migrated`` of the last one
         self.rebuilt = False
         self._g = None
         self._ws = self._stats = None
+        self._held = None                       # ``redistribute``'s decision, for the ``update`` of the same positions
 
     @property
     def stored(self):
@@ -120,6 +125,7 @@ class ShardedNeighborList:
     def invalidate(self):
         """Drop the stored graph: the next update rebuilds (on every rank: the decision is shared)."""
         self._g = None
+        self._held = None
 
     # ---- the shared decision ------------------------------------------------------------------------------------------
     def _all_reduce(self, t, op):
@@ -208,6 +214,36 @@ class ShardedNeighborList:
         perm = g.perm.long()
         return ShardedCloud(SplitGraph(out, inner, outer, E - ek), lx[perm], pos4[:, :3])
 
+    # ---- redistribute -------------------------------------------------------------------------------------------------
+    def _key(self, pos):
+        """What "the same positions" means between ``redistribute`` and the ``update`` that follows: the same storage,
+        shape and version counter, and a halo nobody has set up or migrated in between."""
+        return (pos.data_ptr(), tuple(pos.shape), pos.stride(), pos._version, pos.device, self.halo.generation)
+
+    def redistribute(self, pos: torch.Tensor, x: torch.Tensor, *rows: torch.Tensor):
+        """Call before the model on every step -- a collective --: ``(pos, x, *rows)`` of the particles this rank owns,
+        before -> after.  While the list holds (the shared decision of ``update``) the inputs themselves come back and the
+        decision is kept for the ``update`` of the same ``pos`` tensor, which then skips its own: a holding step costs one
+        all-reduce, with or without this call.  When a rebuild is due, ``halo.migrate(pos, x, *rows)`` moves every particle
+        that has left its owner's region to its new rank (order of the result: ``Halo.migrate``) and the list is
+        invalidated: the ``update`` that follows builds, and its stray check passes.  ``rows``: whatever else the caller
+        keeps per particle (velocities, ids; ``sharding.pack_rows``).  ``migrations`` counts the calls that moved
+        something, ``migrated`` is ``halo.migrated`` of the last one."""
+        if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
+            raise RuntimeError(f"pos must be [n,3] float32, got {tuple(pos.shape)} {pos.dtype}")
+        if x.shape[0] != pos.shape[0]:
+            raise ValueError(f"x has {x.shape[0]} rows for {pos.shape[0]} positions")
+        self._held = None
+        holds, disp = self._decide(pos)
+        if holds:
+            self._held = (self._key(pos), disp)
+            return (pos, x, *rows)
+        out = self.halo.migrate(pos, x, *rows)
+        self.migrated = self.halo.migrated
+        self.migrations += 1 if self.migrated else 0
+        self.invalidate()
+        return out
+
     def update(self, pos: torch.Tensor, x: torch.Tensor) -> ShardedCloud:
         """pos [n,3] fp32, x [n,F]: the particles this rank owns, in the same order on every call between two builds
         (periodic coordinates may be unwrapped or re-wrapped).  Rebuilds -- on every rank -- when any rank has no stored
@@ -218,7 +254,11 @@ class ShardedNeighborList:
             raise ValueError(f"x has {x.shape[0]} rows for {pos.shape[0]} positions")
         self.updates += 1
         self.rebuilt = False
-        holds, disp = self._decide(pos)
+        held, self._held = self._held, None
+        if held is not None and held[0] == self._key(pos):
+            holds, disp = True, held[1]          # ``redistribute`` has just decided for these positions, on every rank
+        else:
+            holds, disp = self._decide(pos)
         if not holds:
             self._build(pos, x)
             self.rebuilt = True

@@ -16,6 +16,12 @@ box, wrapped modulo ``dims`` on periodic axes, and ``t`` (whole box lengths per 
                      and features travel along the entries, send lists and counts of the last ``setup`` -- no selection, no
                      count exchange, no host read; owned rows continue their build-time local coordinates across periodic
                      faces, a ghost is its owner's local position plus the entry's shift.  ``generation`` counts the setups.
+  * ``migrate``    — once per rebuild, before the ``setup``: every owned particle whose owner (``owner_of``) is another rank
+                     moves there with everything the caller keeps per particle, as rows of one int32 row table
+                     (``pack_rows``); the split by owner is one HIP launch pair with one host read (``csrc/e3_migrate.hip``,
+                     on CPU tensors ``migrate_rows_torch``), the counts are agreed on in one ``all_gather``, the rows travel
+                     in one message per ordered pair of ranks.  Bumps ``generation`` and drops the setup state when anything
+                     moved; otherwise the inputs themselves come back.
   * ``start`` / ``finish`` — once per layer: the refreshed features of the boundary particles are posted (grouped
                      isend/irecv), the interior edges' message kernel runs meanwhile, ``finish`` waits and writes the ghost
                      rows of ``h`` IN PLACE (inference only: see ``finish``), then the boundary edges run.
@@ -219,6 +225,122 @@ def select_images(pos, lo, hi, periodic, r, entries):
     return pw, idx.long(), cnt, ghost
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# migration between ranks: the row table, its split by owner (csrc/e3_migrate.hip) and the torch restatement
+# ---------------------------------------------------------------------------------------------------------------------
+_MIGRATE_TAG = len(OFFSETS)   # P2POp tag of a migration message: above every halo entry's tag
+
+
+def _row_words(tensors):
+    """Validate the per-particle tensors of a migration (positions first) -> their widths in 32-bit words."""
+    n = tensors[0].shape[0] if tensors[0].dim() else -1
+    words = []
+    for k, t in enumerate(tensors):
+        what = f"tensor {k} ({tuple(t.shape)} {t.dtype})"
+        if t.requires_grad:
+            raise ValueError(f"{what} requires grad: migration is outside the autograd graph (its outputs are new leaves); "
+                             "pass a detached tensor")
+        row_bytes = (t.shape[1] if t.dim() == 2 else 1) * t.element_size()
+        if t.dim() not in (1, 2) or not t.is_contiguous() or t.is_complex() or row_bytes == 0 or row_bytes % 4:
+            raise ValueError(f"{what}: a row table takes contiguous [n] or [n, k] tensors whose row is a multiple of 4 bytes")
+        if t.shape[0] != n or t.device != tensors[0].device:
+            raise ValueError(f"{what}: every tensor needs the {n} rows and the device of the positions")
+        words.append(row_bytes // 4)
+    return words
+
+
+def pack_rows(pos, *rows):
+    """The per-particle tensors of the caller, viewed as 32-bit words and concatenated column-wise, positions first ->
+    (table int32 [n, W], layout).  Bit-exact; ``unpack_rows`` is the inverse.  Accepted: contiguous ``[n]`` or ``[n, k]``
+    tensors whose row is a multiple of 4 bytes (fp32 / int32 of any ``k``, int64 / fp64 of any ``k``, fp16 / bf16 with even
+    ``k``), none requiring grad; anything else is a ``ValueError`` naming the tensor's position and dtype."""
+    tensors = (pos, *rows)
+    words = _row_words(tensors)
+    n = pos.shape[0]
+    cols = []
+    for t in tensors:
+        t = t.detach().reshape(n, t.shape[1] if t.dim() == 2 else 1)
+        try:
+            cols.append(t.view(torch.int32))
+        except RuntimeError:                      # a narrow dtype at an odd storage offset: the view needs 4-byte alignment
+            cols.append(t.clone().view(torch.int32))
+    layout = [(t.dtype, tuple(t.shape[1:]), w) for t, w in zip(tensors, words)]
+    return torch.cat(cols, 1), layout
+
+
+def unpack_rows(table, layout):
+    """The inverse of ``pack_rows``: -> the list of per-particle tensors (new contiguous tensors, the table's bits)."""
+    n, out, o = table.shape[0], [], 0
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != sum(w for _, _, w in layout):
+        raise ValueError(f"a row table of this layout is int32 [n, {sum(w for _, _, w in layout)}], got "
+                         f"{tuple(table.shape)} {table.dtype}")
+    for dtype, tail, w in layout:
+        # a copy at storage offset 0 (a slice of a table of one row or none is "contiguous" where it lies)
+        out.append(table[:, o:o + w].clone(memory_format=torch.contiguous_format).view(dtype).reshape(n, *tail))
+        o += w
+    return out
+
+
+def migrate_rows_torch(table, owner, rank, world):
+    """Torch restatement of ``e3_migrate_count`` / ``_fill`` (any device; the CPU twin of the kernel): the rows of ``table``
+    [n, W] split by ``owner`` [n] -> (stay [n_stay, W]: the rows with ``owner == rank`` in their original order; send
+    [n_leave, W]: the rows of the other ranks, grouped by destination ascending, ascending original index inside a group;
+    counts [world] int64, ``counts[rank] = n_stay``; n_invalid: the rows whose owner is outside ``[0, world)``, which are in
+    neither output)."""
+    owner = owner.long()
+    valid = (owner >= 0) & (owner < world)
+    stay = table[owner == rank]
+    idx = (valid & (owner != rank)).nonzero().flatten()
+    send = table[idx[torch.sort(owner[idx], stable=True).indices]]
+    counts = torch.bincount(owner[valid], minlength=world)[:world]
+    return stay, send, counts, int(owner.numel() - int(valid.sum()))
+
+
+def _migrate_count(owner, rank, world, workspace=None):
+    """``e3_migrate_count`` and the ONE host read of the pack: owner int32 [n] on a ROCm device -> (the ``world + 1``
+    counts, the last one the invalid owners; the workspace, for ``_migrate_fill``)."""
+    from . import _lib
+    lib = _lib.load()
+    dev, n = owner.device, owner.numel()
+    counts = torch.zeros(world + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        wbytes = int(lib.e3_migrate_workspace_bytes(n, world))
+        if wbytes < 0:
+            raise RuntimeError(f"e3_migrate_workspace_bytes: unsupported size (n = {n}, {world} ranks)")
+        if workspace is None or workspace.numel() < wbytes or workspace.device != dev:
+            workspace = torch.empty(max(wbytes, 16), dtype=torch.uint8, device=dev)
+        _lib.check(lib.e3_migrate_count(owner.data_ptr(), n, world, rank, counts.data_ptr(), workspace.data_ptr(),
+                                        workspace.numel(), torch.cuda.current_stream(dev).cuda_stream), "e3_migrate_count")
+        return [int(v) for v in counts.tolist()], workspace
+
+
+def _migrate_fill(table, owner, rank, world, cnt, workspace, stay):
+    """``e3_migrate_fill`` after ``_migrate_count``: the stayers into ``stay`` [>= cnt[rank], W], -> send [n_leave, W]."""
+    from . import _lib
+    dev, (n, W) = table.device, table.shape
+    n_send = sum(cnt[:world]) - cnt[rank]
+    send = torch.empty((n_send, W), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().e3_migrate_fill(
+            table.data_ptr(), owner.data_ptr(), n, W, world, rank, (ctypes.c_int32 * (world + 1))(*cnt), stay.shape[0], n_send,
+            stay.data_ptr() if stay.shape[0] else None, send.data_ptr() if n_send else None, workspace.data_ptr(),
+            workspace.numel(), torch.cuda.current_stream(dev).cuda_stream), "e3_migrate_fill")
+    return send
+
+
+def migrate_rows(table, owner, rank, world, workspace=None):
+    """``migrate_rows_torch``'s result, bit for bit.  ROCm tensors and at most ``MORTON_MAX_RANKS`` ranks: the HIP pair
+    ``e3_migrate_count`` / ``_fill`` (csrc/e3_migrate.hip; one host read of the counts); CPU tensors, or more ranks: the
+    torch restatement."""
+    if not table.is_cuda or world > MORTON_MAX_RANKS:
+        return migrate_rows_torch(table, owner, rank, world)
+    table, owner = table.contiguous(), owner.to(torch.int32).contiguous()
+    cnt, workspace = _migrate_count(owner, rank, world, workspace)
+    stay = torch.empty((cnt[rank], table.shape[1]), dtype=torch.int32, device=table.device)
+    send = _migrate_fill(table, owner, rank, world, cnt, workspace, stay)
+    return stay, send, torch.tensor(cnt[:world], dtype=torch.int64, device=table.device), cnt[world]
+
+
 @dataclass
 class SplitGraph:
     """Edge lists of a sharded graph, all sorted by dst (CSR order) in the graph's local (Morton) numbering."""
@@ -344,6 +466,10 @@ class Halo:
         self.bytes_last_exchange = 0
         self.anchor = None          # see ``refresh``: the leaf that keeps every refresh in a backward pass
         self._grad_maps = None
+        self._build_pos = None      # the stored setup state: None before the first ``setup`` and after a ``migrate`` that moved
+        # the last ``migrate``: rows sent to / received from every rank, and the particles that changed rank anywhere
+        self.migrated_out, self.migrated_in, self.migrated = [0] * self.world, [0] * self.world, 0
+        self._migrate_ws = None
         ent = self.images = entries
         self.neighbours = sorted({q for q, _, _ in ent if q != self.rank})
         at = {d: e for e, (_, d, _) in enumerate(ent)}
@@ -436,6 +562,9 @@ class Halo:
 
     # -- once per step between two builds --------------------------------------------------------------
     def _check_like_build(self, pos):
+        if self._build_pos is None:
+            raise RuntimeError("the halo holds no setup state (none yet, or a migrate has moved particles since): call "
+                               "setup first")
         if pos.shape != self._build_pos.shape or pos.device != self._build_pos.device:
             raise ValueError(f"positions {tuple(pos.shape)} on {pos.device}: the last setup saw "
                              f"{tuple(self._build_pos.shape)} on {self._build_pos.device}")
@@ -488,6 +617,82 @@ class Halo:
             self._wait(*self._start(list(snd.split(self.send_counts)), list(ghosts.split(self.recv_counts))))
             out.append(torch.cat([t, ghosts], 0))
         return out[0], (out[1] if feats is not None else None)
+
+    # -- once per rebuild, before the setup: particles that changed owner change rank -------------------
+    def migrate(self, pos: torch.Tensor, *rows: torch.Tensor):
+        """Move every owned particle whose owner (``owner_of``) is another rank to that rank, with everything the caller
+        keeps per particle: pos [n,3] and any number of ``rows`` ([n] or [n, k], ``pack_rows``) -> ``(pos, *rows)`` of the
+        particles this rank owns now.  A collective: every rank of the group calls it with the same number of ``rows`` and
+        the same row widths.
+
+        Ownership is computed on the caller's coordinates (periodic axes may be unwrapped: ``owner_of`` wraps) and the
+        positions travel as the caller's bits.  Order of the result: the stayers in their original relative order, then
+        the arrivals by source rank ascending, each in the sender's original order.  The split is one device pack
+        (``e3_migrate_count``, ONE host read of the counts, ``e3_migrate_fill``; ``migrate_rows_torch`` on CPU tensors and
+        above ``MORTON_MAX_RANKS`` ranks), the counts are agreed on in one ``all_gather`` (host-staged under gloo), the rows
+        travel in one message per ordered pair of ranks with a non-zero count, straight into the new table.
+
+        Nobody moved on any rank: the inputs themselves come back, ``generation`` and the setup state stay.  Otherwise
+        ``generation`` is bumped (a ``ShardedNeighborList`` rebuilds) and the setup state is dropped: ``displacement`` and
+        ``update_positions`` raise until the next ``setup``.  A position that is not finite has no owner: EVERY rank raises
+        ``ValueError`` before any row is sent.  ``migrated_out[q]`` / ``migrated_in[q]``: rows sent to / received from rank
+        ``q``; ``migrated``: the particles that changed rank anywhere.
+
+        Re-balancing a ``MortonHalo`` is ``halo.partition.fit(pos, halo.group)`` followed by ``halo.migrate(...)``: the
+        splitters are read when they are used.  Outside the autograd graph: the outputs are new leaves."""
+        world, rank = self.world, self.rank
+        tensors = (pos, *rows)
+        _row_words(tensors)                                               # ValueError before any collective
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError(f"positions must be [n,3], got {tuple(pos.shape)}")
+        dev = pos.device
+        owner = self.owner_of(pos)
+        owner = torch.where(torch.isfinite(pos).all(1), owner, torch.full_like(owner, -1)).to(torch.int32)
+        on_device = pos.is_cuda and world <= MORTON_MAX_RANKS
+        if on_device:
+            cnt, self._migrate_ws = _migrate_count(owner, rank, world, self._migrate_ws)   # the one host read of the pack
+        else:
+            valid = (owner >= 0) & (owner < world)
+            cnt = torch.bincount(owner[valid].long(), minlength=world)[:world].tolist()
+            cnt.append(pos.shape[0] - sum(cnt))
+        # every rank's count row: who sends how many to whom, and whether anybody had a row without an owner
+        matrix = [cnt]
+        if world > 1:
+            cdev = torch.device("cpu") if self._gloo() else dev
+            gathered = [torch.empty(world + 1, dtype=torch.int64, device=cdev) for _ in range(world)]
+            dist.all_gather(gathered, torch.tensor(cnt, dtype=torch.int64, device=cdev), group=self.group)
+            matrix = torch.stack(gathered).tolist()
+        n_bad = sum(row[world] for row in matrix)
+        if n_bad:
+            raise ValueError(f"Halo.migrate: {n_bad} particle(s) have no owner among the {world} rank(s) (a position is not "
+                             "finite?): nothing was moved")
+        others = [q for q in range(world) if q != rank]
+        self.migrated_out = [0 if q == rank else cnt[q] for q in range(world)]
+        self.migrated_in = [0 if q == rank else matrix[q][rank] for q in range(world)]
+        self.migrated = sum(matrix[p][q] for p in range(world) for q in range(world) if p != q)
+        if not self.migrated:
+            return tensors
+        table, layout = pack_rows(*tensors)
+        n_stay, n_in = cnt[rank], sum(self.migrated_in)
+        new = torch.empty((n_stay + n_in, table.shape[1]), dtype=torch.int32, device=dev)
+        if on_device:
+            send = _migrate_fill(table, owner, rank, world, cnt, self._migrate_ws, new[:n_stay])
+        else:
+            stay, send, _, _ = migrate_rows_torch(table, owner, rank, world)
+            new[:n_stay] = stay
+        sends = list(send.split([cnt[q] for q in others]))
+        recvs = list(new[n_stay:].split([matrix[q][rank] for q in others]))
+        staged = []
+        if pos.is_cuda and self._gloo():                                  # gloo has no device transport (``_start``)
+            sends = [t.cpu() for t in sends]
+            host = [torch.empty(t.shape, dtype=t.dtype) for t in recvs]
+            staged, recvs = list(zip(recvs, host)), host
+        ops = [dist.P2POp(dist.isend, t, q, self.group, tag=_MIGRATE_TAG) for q, t in zip(others, sends) if t.numel()]
+        ops += [dist.P2POp(dist.irecv, t, q, self.group, tag=_MIGRATE_TAG) for q, t in zip(others, recvs) if t.numel()]
+        self._wait(dist.batch_isend_irecv(ops) if ops else [], staged, sends)
+        self.generation += 1
+        self._build_pos = self._build_local = None
+        return tuple(unpack_rows(new, layout))
 
     def renumber(self, perm: torch.Tensor):
         """The graph builder renumbers the local cloud (``perm[new] = old``): translate the halo index lists."""
@@ -723,6 +928,10 @@ class SlabHalo(GridHalo):
         by = {d: c for (_, d, _), c in zip(self.images, self.recv_counts)}
         self.n_ghost_left, self.n_ghost_right = by.get((-1, 0, 0), 0), by.get((1, 0, 0), 0)
         return out
+
+    def migrate(self, pos, *rows):
+        raise NotImplementedError("SlabHalo has no bounds until setup, so it has no owner to migrate to: use a GridHalo "
+                                  "(world, 1, 1) over the whole domain")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
