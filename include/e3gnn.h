@@ -559,6 +559,36 @@ int e3_msg_forward_cell(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t 
                         const float* premix, float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block,
                         const float cell[9], void* stream);
 /*
+ * Owned sums: e3_msg_forward for a launch that does not accumulate, with every row of `out` written exactly once -- no
+ * zero-fill, no atomics -- and the operand scale of `out` from the same launches.  The edges are dst-sorted and a chunk of
+ * the weights-stationary kernel is a contiguous edge range, so a node whose run lies strictly inside a chunk is complete when
+ * the kernel flushes it: the kernel stores such rows itself.  The first and the last node of every chunk go through a
+ * boundary buffer in `workspace` and are summed in edge order by a small kernel; a second one zeroes the rows of nodes
+ * without an incoming edge (one pass over dst).  Sums are reproducible from run to run, and bit-identical to
+ * e3_msg_forward's for every node with at most two partial sums.
+ *   workspace : e3_msg_owned_workspace_bytes(plan, E, dtype, tiles_per_block) bytes, 16-byte aligned, scratch of the call
+ *               (-1: the shape / tiles_per_block < 0 does not run the weights-stationary kernel; the forward entries then
+ *               return E3_ERR_UNSUPPORTED with nothing launched: use e3_msg_forward + e3_pow2_scale)
+ *   out_scale4: receives what e3_pow2_scale(out [N, D], target_log2) would (the contract above e3_pow2_scale):
+ *               {s, 1/s, bits of max |out| over the finite elements, -}
+ * Everything else as e3_msg_forward / _pbc / _cell with accumulate = 0.
+ */
+int64_t e3_msg_owned_workspace_bytes(const e3_msg_plan* plan, int64_t E, int dtype, int tiles_per_block);
+int e3_msg_forward_owned(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const float* pos4,
+                         const int32_t* src, const int32_t* dst, int64_t E, const void* packed, const float* in_scale,
+                         const float* premix, float* out, int64_t ld_out, int dtype, int tiles_per_block,
+                         void* workspace, int64_t workspace_bytes, float* out_scale4, int target_log2, void* stream);
+int e3_msg_forward_owned_pbc(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const float* pos4,
+                             const int32_t* src, const int32_t* dst, int64_t E, const void* packed,
+                             const float* in_scale, const float* premix, float* out, int64_t ld_out, int dtype,
+                             int tiles_per_block, void* workspace, int64_t workspace_bytes, float* out_scale4,
+                             int target_log2, const float box[3], void* stream);
+int e3_msg_forward_owned_cell(e3_msg_plan* plan, const void* h, int64_t ld_h, int64_t N, const float* pos4,
+                              const int32_t* src, const int32_t* dst, int64_t E, const void* packed,
+                              const float* in_scale, const float* premix, float* out, int64_t ld_out, int dtype,
+                              int tiles_per_block, void* workspace, int64_t workspace_bytes, float* out_scale4,
+                              int target_log2, const float cell[9], void* stream);
+/*
  * bf16 storage (dtype E3_BF16, BASELINE config 3): segments / in1 / out / weights / norms are bf16, in2 (the
  * spherical harmonics) stays fp32, products run once on v_mfma_f32_16x16x32_bf16 with fp32 accumulation and one
  * rounding of the result.  Only the MFMA path exists for bf16 (E3_ERR_UNSUPPORTED otherwise).

@@ -104,6 +104,17 @@ SIGNATURES = {
                                     c_void_p]),
     "e3_msg_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    # owned sums: (..., dtype, tiles_per_block, workspace, workspace_bytes, out_scale4, target_log2[, box | cell], stream)
+    "e3_msg_owned_workspace_bytes": (c_int64, [c_void_p, c_int64, c_int, c_int]),
+    "e3_msg_forward_owned": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p,
+                                     c_int, c_void_p]),
+    "e3_msg_forward_owned_pbc": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
+                                         c_void_p, c_int, Float3, c_void_p]),
+    "e3_msg_forward_owned_cell": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
+                                          c_void_p, c_int, Float9, c_void_p]),
     "e3_edge_geometry_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
     # periodic boxes (box = float[3] of L per axis, 0 = open; periodic = axis bit mask)

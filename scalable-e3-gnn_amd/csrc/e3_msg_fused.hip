@@ -1336,17 +1336,44 @@ int e3_msg_refresh_rows(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, 
 
 }  // extern "C"
 
+// Owned sums (e3_msg_forward_owned*): the weights-stationary launch + the boundary merge and the isolated-rows kernel behind
+// it (e3_msg_owned.hip) write every row of `out` exactly once (the ownership rule stands above `flush` in e3_msg_ws.hip).
+// [part_node: 2 ints per chunk, padded to 256 bytes][part: 2 x D floats per chunk]
+static int64_t owned_node_bytes(int64_t nchunks) { return (nchunks * 8 + 255) / 256 * 256; }
+static int64_t owned_workspace_bytes(const e3_msg_plan* P, int64_t E, int dtype, int tiles_per_block) {
+  if (!P || E < 0 || E > 0x7fffffffLL - 65536 || tiles_per_block < 0 || !msg_ws_supported(P->lmax, P->H, dtype)) return -1;
+  if (E == 0) return 0;
+  const int64_t nch = msg_ws_owned_chunks(E, tiles_per_block > (1 << 20) ? (1 << 24) : tiles_per_block * 16);
+  return owned_node_bytes(nch) + nch * 2 * (int64_t)P->k->D * 4;
+}
+
 // box: NULL = the open kernels; else L per axis (0 = open axis), already validated.  cell (excludes box): NULL, or what
-// make_cell derived = the cell kernels
+// make_cell derived = the cell kernels.  out_scale4 != NULL: the owned-sums form (e3_msg_forward_owned*): no zero-fill, no
+// atomics, and the operand scale of `out` from the same launches; `accumulate` is 0 then.
 static int msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
                        const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
                        float* out, int64_t ld_out, int dtype, int accumulate, int tiles_per_block, void* stream,
-                       const float* box, const PbcCell* cell = nullptr) {
+                       const float* box, const PbcCell* cell = nullptr, void* workspace = nullptr,
+                       int64_t workspace_bytes = 0, float* out_scale4 = nullptr, int target_log2 = 0) {
   if (!P || N < 0 || E < 0 || E > 0x7fffffffLL - 16) return E3_ERR_INVALID_ARG;  // edge ids are int32
   if (!e3_msg_supports(P, dtype)) return E3_ERR_UNSUPPORTED;
+  const bool owned = out_scale4 != nullptr;
+  int64_t need = 0;
+  if (owned) {
+    if (accumulate || target_log2 < -20 || target_log2 > 14) return E3_ERR_INVALID_ARG;
+    need = owned_workspace_bytes(P, E, dtype, tiles_per_block);
+    if (need < 0) return E3_ERR_UNSUPPORTED;  // shapes of the one-wave-per-tile kernel: e3_msg_forward + e3_pow2_scale
+    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return E3_ERR_INVALID_ARG;
+  }
   const MsgKernels& k = *P->k;
   const int io = dtype == E3_BF16 ? 1 : 0, es = io ? 2 : 4;
-  if (N == 0) return E3_OK;
+  if (N == 0) {
+    if (owned) {
+      E3_HIP_CHECK(hipMemsetAsync(out_scale4, 0, 16, (hipStream_t)stream));
+      return scale_finalize(out_scale4, target_log2, (hipStream_t)stream);
+    }
+    return E3_OK;
+  }
   if (!h || !pos4 || !packed || !premix || !out || ld_h < k.D || ld_out < k.D || (E > 0 && (!src || !dst)))
     return E3_ERR_INVALID_ARG;
   if ((ld_h * es & 15) || ((uintptr_t)h & 15) || ((uintptr_t)premix & 15)) return E3_ERR_INVALID_ARG;  // 16-byte row gathers
@@ -1354,7 +1381,25 @@ static int msg_forward(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, c
   if (st != E3_OK) return st;
   hipStream_t s = (hipStream_t)stream;
   // out is an accumulation target of atomics: the rows start from zero unless this launch continues an earlier one
-  if (!accumulate) E3_HIP_CHECK(hipMemset2DAsync(out, (size_t)ld_out * 4, 0, (size_t)k.D * 4, (size_t)N, s));
+  // (owned sums with E > 0: every row is stored once by one of the three writers -- no fill)
+  if (!accumulate && !(owned && E > 0)) E3_HIP_CHECK(hipMemset2DAsync(out, (size_t)ld_out * 4, 0, (size_t)k.D * 4, (size_t)N, s));
+  if (owned) {
+    E3_HIP_CHECK(hipMemsetAsync(out_scale4, 0, 16, s));
+    if (E > 0) {
+      const int chunk_edges = tiles_per_block > (1 << 20) ? (1 << 24) : tiles_per_block * 16;
+      const int64_t nch = msg_ws_owned_chunks(E, chunk_edges);
+      int* part_node = static_cast<int*>(workspace);
+      float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + owned_node_bytes(nch));
+      uint32_t* amax = reinterpret_cast<uint32_t*>(out_scale4) + 2;
+      E3_HIP_CHECK(hipMemsetAsync(part_node, 0xFF, (size_t)nch * 8, s));  // -1: slots that no chunk fills
+      st = msg_ws_launch(P->lmax, P->H, dtype, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out,
+                         chunk_edges, s, box, cell, part, part_node, amax);
+      if (st != E3_OK) return st;
+      st = msg_owned_finish(part, part_node, 2 * nch, dst, E, N, k.D, out, ld_out, amax, s);
+      if (st != E3_OK) return st;
+    }
+    return scale_finalize(out_scale4, target_log2, s);
+  }
   if (E == 0) return E3_OK;
   // H = 32, fp32: the weights-stationary kernel (e3_msg_ws.hip); tiles_per_block > 0 = its chunk size in 16-edge units.
   // tiles_per_block < 0 asks for this file's one-wave-per-tile kernel with |tiles_per_block| tiles per wave block.
@@ -1408,6 +1453,39 @@ int e3_msg_forward_cell(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, 
   if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
   return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, accumulate,
                      tiles_per_block, stream, nullptr, &c);
+}
+
+int64_t e3_msg_owned_workspace_bytes(const e3_msg_plan* P, int64_t E, int dtype, int tiles_per_block) {
+  return owned_workspace_bytes(P, E, dtype, tiles_per_block);
+}
+
+int e3_msg_forward_owned(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
+                         const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
+                         float* out, int64_t ld_out, int dtype, int tiles_per_block, void* workspace,
+                         int64_t workspace_bytes, float* out_scale4, int target_log2, void* stream) {
+  if (!out_scale4) return E3_ERR_INVALID_ARG;
+  return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, 0, tiles_per_block,
+                     stream, nullptr, nullptr, workspace, workspace_bytes, out_scale4, target_log2);
+}
+
+int e3_msg_forward_owned_pbc(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
+                             const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
+                             float* out, int64_t ld_out, int dtype, int tiles_per_block, void* workspace,
+                             int64_t workspace_bytes, float* out_scale4, int target_log2, const float box[3], void* stream) {
+  if (!out_scale4 || !box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
+  return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, 0, tiles_per_block,
+                     stream, box, nullptr, workspace, workspace_bytes, out_scale4, target_log2);
+}
+
+int e3_msg_forward_owned_cell(e3_msg_plan* P, const void* h, int64_t ld_h, int64_t N, const float* pos4, const int32_t* src,
+                              const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix,
+                              float* out, int64_t ld_out, int dtype, int tiles_per_block, void* workspace,
+                              int64_t workspace_bytes, float* out_scale4, int target_log2, const float cell[9],
+                              void* stream) {
+  PbcCell c;
+  if (!out_scale4 || !make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return msg_forward(P, h, ld_h, N, pos4, src, dst, E, packed, in_scale, premix, out, ld_out, dtype, 0, tiles_per_block,
+                     stream, nullptr, &c, workspace, workspace_bytes, out_scale4, target_log2);
 }
 
 #if E3_MSG_STAMP

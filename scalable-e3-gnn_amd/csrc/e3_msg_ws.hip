@@ -615,6 +615,10 @@ struct WsArgsT {
   const float4* pos4; const int32_t* src; const int32_t* dst; int64_t E;
   const float* packed; const float* U; const void* split; const float* hmax; const float* in_scale; float* out; int64_t ldo;
   int chunk;  // edges per chunk (multiple of 16)
+  // owned sums (part != nullptr: a launch that does not accumulate; `flush` below): boundary rows of the chunks
+  // part[chunk][head | tail][D], their node ids part_node[chunk][head | tail], chunks per XCD eighth, and the max-bits word
+  // that receives max |row| over the finite values of the rows this kernel stores itself
+  float* part; int* part_node; uint32_t* amax; int chunks_per_xcd;
   BOX box;  // periodic instantiations only (the open kernel never reads it); PbcCell for the cell instantiations
 };
 using WsArgs = WsArgsT<PbcBox>;
@@ -839,12 +843,43 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
   float carry[NQW];
 #pragma unroll
   for (int q = 0; q < NQW; ++q) carry[q] = 0.f;
-  auto flush = [&]() {
+  // Owned sums (launches that do not accumulate): the edges are dst-sorted and a chunk is a contiguous edge range, so a node
+  // whose run lies strictly inside a chunk is COMPLETE when it is flushed; only the first and the last flushed node of a chunk
+  // can continue in a neighbouring chunk.  State (wave-uniform): the workgroup's next chunk starts at edge onext and has the
+  // global index ochunk (XCD eighth x chunks per eighth + index inside the eighth); ocur = the chunk of the running sum,
+  // onfl = nodes flushed in it so far; rmax = running max |row| over the finite values of the rows stored here.
+  const bool owned = A.part != nullptr;
+  int onext = xlo + wg_idx * A.chunk, ochunk = (int)(blockIdx.x & 7) * A.chunks_per_xcd + wg_idx, ocur = 0, onfl = 0;
+  float rmax = 0.f;
+  // OWNERSHIP: every row of `out` is written exactly once by exactly one of three writers.  (1) this kernel: a flushed node
+  // that is neither the first nor the last flushed node of its chunk -- plain stores of the final row; (2) the boundary
+  // merge (msg_boundary_merge_kernel): the first and the last flushed node of every chunk, whose partial sums go to `part`
+  // here (a chunk with a single node fills its head slot only; its tail id stays -1); (3) the isolated-rows kernel: nodes
+  // without an incoming edge.  `last`: the flush ends the chunk (chunk switch, or the end of the tile stream).
+  auto flush = [&](const bool last) {
     if (cur >= 0) {
-      float* o = A.out + (int64_t)cur * A.ldo;
+      if (!owned) {  // accumulating launches: one fp32 atomic per node, column and chunk
+        float* o = A.out + (int64_t)cur * A.ldo;
 #pragma unroll
-      for (int q = 0; q < Q1 - Q0; ++q)
-        if (64 * (Q0 + q) + lane < D) __builtin_amdgcn_global_atomic_fadd_f32(o + 64 * (Q0 + q) + lane, carry[q]);
+        for (int q = 0; q < Q1 - Q0; ++q)
+          if (64 * (Q0 + q) + lane < D) __builtin_amdgcn_global_atomic_fadd_f32(o + 64 * (Q0 + q) + lane, carry[q]);
+      } else if (onfl == 0 || last) {
+        const int64_t slot = 2 * (int64_t)ocur + (onfl == 0 ? 0 : 1);
+        float* o = A.part + slot * D;
+#pragma unroll
+        for (int q = 0; q < Q1 - Q0; ++q)
+          if (64 * (Q0 + q) + lane < D) o[64 * (Q0 + q) + lane] = carry[q];
+        if (SY == 0 && lane == 0) A.part_node[slot] = cur;
+      } else {
+        float* o = A.out + (int64_t)cur * A.ldo;
+#pragma unroll
+        for (int q = 0; q < Q1 - Q0; ++q)
+          if (64 * (Q0 + q) + lane < D) {
+            o[64 * (Q0 + q) + lane] = carry[q];
+            rmax = fmax_finite(rmax, carry[q]);
+          }
+      }
+      ++onfl;
     }
 #pragma unroll
     for (int q = 0; q < NQW; ++q) carry[q] = 0.f;
@@ -1216,11 +1251,18 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
             }
           }
         }
-        if (t1.node0 != cur) { flush(); cur = t1.node0; }
+        // a tile that starts a chunk ((e0 - xlo) % chunk == 0: the workgroup's chunks are visited in order) ends the sum of
+        // the previous chunk even when the node id continues (one workgroup taking adjacent chunks)
+        const bool cstart = owned && t1.e0 == onext;
+        if (cstart || t1.node0 != cur) {
+          flush(cstart);
+          if (cstart) { ocur = ochunk; onfl = 0; ochunk += per_xcd; onext += per_xcd * A.chunk; }
+          cur = t1.node0;
+        }
 #pragma unroll
         for (int q = 0; q < NQW; ++q) carry[q] += s0[q];
         if (t1.node1 >= 0) {
-          flush();
+          flush(false);
           cur = t1.node1;
 #pragma unroll
           for (int q = 0; q < NQW; ++q) carry[q] = s1[q];
@@ -1239,7 +1281,14 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
     ws_barrier();
     t1 = t0; t0 = tn;
   }
-  if constexpr (RSW) flush();
+  if constexpr (RSW) {
+    flush(true);
+    if (owned) {  // one wave reduction and one atomicMax per run-sum wave
+      float m = rmax;
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      if (lane == 0 && m > 0.f) atomicMax(A.amax, __builtin_bit_cast(uint32_t, m));
+    }
+  }
 #if E3_WS_STAMP
   if (lane == 0) {
     for (int i = 0; i < 4; ++i) atomicAdd(&g_ws_stamps[W][i], (unsigned long long)st_acc[i]);
@@ -1294,10 +1343,21 @@ int msg_ws_split_floats(int lmax, int hidden) {
 }
 static_assert(MsgSplit<2>::FLOATS == 9 * 32 && MsgSplit<1>::FLOATS == 4 * 32, "msg_ws_split_floats");
 
+int msg_ws_chunk_edges(int chunk_edges) { return chunk_edges > 0 ? (chunk_edges + 15) / 16 * 16 : 256; }
+
+// the kernel's split of the edges: eight contiguous eighths of e_per_xcd edges (a multiple of 16), each cut into chunks
+int64_t msg_ws_owned_chunks(int64_t E, int chunk_edges) {
+  const int64_t chunk = msg_ws_chunk_edges(chunk_edges);
+  const int64_t e_per_xcd = ((E + 7) / 8 + 15) / 16 * 16;
+  return 8 * ((e_per_xcd + chunk - 1) / chunk);
+}
+
 int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, int64_t N, const float* pos4, const int32_t* src,
                   const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix, float* out,
-                  int64_t ldo, int chunk_edges, hipStream_t stream, const float* box, const PbcCell* cell) {
+                  int64_t ldo, int chunk_edges, hipStream_t stream, const float* box, const PbcCell* cell, float* part,
+                  int* part_node, uint32_t* amax) {
   if (!msg_ws_supported(lmax, hidden, dtype)) return E3_ERR_UNSUPPORTED;
+  if (part && (!part_node || !amax)) return E3_ERR_INVALID_ARG;
   const int pb = cell ? kCell : (box ? kBox : kOpen);
   if (E > 0x7fffffffLL - 65536) return E3_ERR_UNSUPPORTED;  // 32-bit edge arithmetic with chunk head room
   const int io = dtype == E3_BF16 ? 1 : 0;
@@ -1337,7 +1397,7 @@ int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, i
     }
     cus = cus_of[dev][io][li][pb];
   }
-  int chunk = chunk_edges > 0 ? (chunk_edges + 15) / 16 * 16 : 256;
+  const int chunk = msg_ws_chunk_edges(chunk_edges);
   const int64_t nchunks = (E + chunk - 1) / chunk;
   int nwg = (int)std::min<int64_t>(cus, nchunks);  // one workgroup of 8 waves per CU
   nwg = std::max(8, (nwg + 7) / 8 * 8);
@@ -1348,7 +1408,8 @@ int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, i
   // the argument block of the mode: the box / cell sits behind the common fields (kernel-argument segment: SGPRs)
   auto launch = [&](const auto& pbc) {
     WsArgsT<std::decay_t<decltype(pbc)>> a = {h, ldh, reinterpret_cast<const float4*>(pos4), src, dst, E,
-                                              static_cast<const float*>(packed), premix, split, hmax, in_scale, out, ldo, chunk, pbc};
+                                              static_cast<const float*>(packed), premix, split, hmax, in_scale, out, ldo, chunk,
+                                              part, part_node, amax, (int)(msg_ws_owned_chunks(E, chunk_edges) / 8), pbc};
     void* args[] = {&a};
     return hipLaunchKernel(kern, dim3(nwg), dim3(512), args, lds, stream) == hipSuccess ? E3_OK : E3_ERR_HIP;
   };

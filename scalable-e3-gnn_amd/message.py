@@ -26,6 +26,10 @@ class FusedMessage:
         self._plans = _lib.DevicePlans("e3_msg_plan_create", "e3_msg_plan_destroy", self.lmax, self.hidden)
         self._packed = {}
         self.tiles_per_block = 0  # 0 = library default
+        # non-accumulating launches of the weights-stationary kernel write every row of the sums exactly once (plain stores
+        # + a merge of the chunk-boundary rows: no zero-fill, no atomics, reproducible) and return the operand scale of the
+        # sums from the same launches (e3_msg_forward_owned); False = the zero-fill + atomics path (e3_msg_forward)
+        self.owned_sums = True
 
     def __deepcopy__(self, memo):
         return FusedMessage(self.lmax, self.hidden)
@@ -153,7 +157,7 @@ class FusedMessage:
         return fl
 
     def forward(self, h: torch.Tensor, g: RadiusGraph, msg1, msg2, in_scale: torch.Tensor | None = None, edges=None,
-                cont=None, return_state: bool = False):
+                cont=None, return_state: bool = False, return_scale: bool = False, out: torch.Tensor | None = None):
         """h [N, width] fp32 | bf16 (Morton order of ``g``) -> aggregated messages [N, width] in h's dtype (the sums are
         fp32 in both cases; bf16 storage rounds them once).
 
@@ -161,7 +165,12 @@ class FusedMessage:
         ``return_state``: return ``(out, state)`` with ``state = (out, premix)`` -- the pre-mix table (6.8 GB at 1 M
         particles) stays referenced only as long as the caller keeps it.
         ``cont``: such a state -- the call then ADDS its edges' messages to ``out`` (same ``h`` rows for every dst node
-        required) and returns ``out``."""
+        required) and returns ``out``.
+        ``out``: a contiguous fp32 [N, width] tensor that receives the sums instead of a fresh one (its contents are
+        ignored; not with ``cont``).
+        ``return_scale``: the result is followed by the operand scale of ``out`` -- what ``ops.pow2_scale([out])`` returns
+        ({s, 1/s, bits of max |out|, -}, device) -- or by None where the launch does not produce it (``owned_sums`` off, a
+        ``cont`` call, a shape without the weights-stationary kernel): the caller scans ``out`` then."""
         if not h.is_cuda or not self.supports(h.dtype):
             raise RuntimeError(f"fused message: ROCm tensor in float32 (or bfloat16 for hidden >= 32) required, got "
                                f"{h.dtype} on {h.device} (no CPU path)")
@@ -177,11 +186,20 @@ class FusedMessage:
         E = int(src.numel())
         assert src.dtype == torch.int32 and dst.dtype == torch.int32 and dst.numel() == E
         if cont is None:
-            out = torch.empty((N, W), dtype=torch.float32, device=dev)
+            if out is None:
+                out = torch.empty((N, W), dtype=torch.float32, device=dev)
+            elif out.shape != (N, W) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+                raise RuntimeError(f"fused message: out must be a contiguous float32 [{N}, {W}] tensor on {dev}")
         else:
             out = cont[0]
+        def result(o, state, scale):
+            r = (o, state) if return_state else (o,)
+            r = r + (scale,) if return_scale else r
+            return r if len(r) > 1 else r[0]
+
         if N == 0:
-            return (out.to(io), None) if return_state else out.to(io)
+            return result(out.to(io), None, None)
+        out_scale = None
         with torch.cuda.device(dev):
             packed = self.packed(msg1, msg2, dev, io)
             if in_scale is None and io == torch.float32:
@@ -207,7 +225,19 @@ class FusedMessage:
             args = (hd, h.data_ptr(), h.stride(0), N, g.pos4.data_ptr(), src.data_ptr(), dst.data_ptr(), E,
                     packed.data_ptr(), sc, premix.data_ptr(), out.data_ptr(), out.stride(0), code,
                     0 if cont is None else 1, int(self.tiles_per_block))
-            if g.cell is not None:  # general cell: harmonics of the minimum image by lattice vectors
+            wsb = int(lib.e3_msg_owned_workspace_bytes(hd, E, code, int(self.tiles_per_block))) \
+                if (self.owned_sums and cont is None) else -1
+            if wsb >= 0:
+                work = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+                out_scale = torch.empty(4, dtype=torch.float32, device=dev)
+                args = args[:14] + (int(self.tiles_per_block), work.data_ptr(), wsb, out_scale.data_ptr(), 10)
+                if g.cell is not None:
+                    _lib.check(lib.e3_msg_forward_owned_cell(*args, g.cell_arg, stream), "e3_msg_forward_owned_cell")
+                elif g.box is not None:
+                    _lib.check(lib.e3_msg_forward_owned_pbc(*args, g.box_arg, stream), "e3_msg_forward_owned_pbc")
+                else:
+                    _lib.check(lib.e3_msg_forward_owned(*args, stream), "e3_msg_forward_owned")
+            elif g.cell is not None:  # general cell: harmonics of the minimum image by lattice vectors
                 _lib.check(lib.e3_msg_forward_cell(*args, g.cell_arg, stream), "e3_msg_forward_cell")
             elif g.box is not None:  # periodic box: harmonics of the minimum-image edge vectors
                 _lib.check(lib.e3_msg_forward_pbc(*args, g.box_arg, stream), "e3_msg_forward_pbc")
@@ -222,4 +252,4 @@ class FusedMessage:
                               kernel=("e3::msg_ws_kernel" if ws else "e3::msg_fused_kernel") + mode,
                               executed_flops=self.executed_flops_per_edge() * E)
         # fp32 sums; callers in bf16 storage round once (SEGNNLayer)
-        return (out, (out, premix)) if return_state else out
+        return result(out, (out, premix), out_scale)

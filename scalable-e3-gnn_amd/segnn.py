@@ -59,8 +59,11 @@ class SEGNNLayer(nn.Module):
         hid, gated = _hidden_irreps(H, lmax)
         self.H, self.lmax = H, lmax
         self.fused = True           # fused gather + TP + gate (+ segment-sum) kernels when the shapes allow it
-        self.fuse_scatter = True    # segment-sum by fp32 atomics in the message kernel (sums agree to fp32 rounding, not
-        #                             bit for bit); False = separate, bitwise reproducible e3_segment_sum
+        self.fuse_scatter = True    # segment-sum inside the message kernel.  The one-launch message kernel for hidden 32,
+        #                             l_max = 2 writes every row once (FusedMessage.owned_sums): reproducible from run to
+        #                             run.  The other fused kernels (and sharded / accumulating launches) sum by fp32
+        #                             atomics: sums agree to fp32 rounding, not bit for bit.
+        #                             False = separate, bitwise reproducible e3_segment_sum
         self.fuse_message = True    # fp32: the whole message function in one launch (message.FusedMessage)
         self._msg = FusedMessage(lmax, H) if FusedMessage.supported(lmax, H) else None
         self.msg1 = _make_tp(hid + hid + Irreps("1x0e"), gated, lmax)
@@ -121,6 +124,7 @@ class SEGNNLayer(nn.Module):
         # ---- message function -> aggregated messages a [N, width] ----
         one_launch = (self.fused and inference and self.fuse_message and self.fuse_scatter and self._msg is not None and
                       self._msg.supports(h.dtype) and w is None)
+        a_scale = None  # operand scale of the aggregated messages where the message launch returns it
         r16u = self.fused and inference and (r16 or (one_launch and self.fused_update_available()))   # update product
         if h.dtype == torch.bfloat16 and not ((one_launch or r16) and r16u):
             raise RuntimeError("bf16 storage needs the fused MFMA kernels (inference; hidden 32, or 64 at l_max = 2)")
@@ -153,7 +157,8 @@ class SEGNNLayer(nn.Module):
             # one launch: SH + TP #1 + gate + TP #2 + gate + segment-sum (message.FusedMessage)
             if h_scale is None and f32:
                 h_scale = ops.pow2_scale([h])
-            a = self._msg.forward(h, g, self.msg1, self.msg2, h_scale).to(h.dtype)
+            a, a_scale = self._msg.forward(h, g, self.msg1, self.msg2, h_scale, return_scale=True)
+            a = a.to(h.dtype)
         elif r16:
             # gather + concat + TP + gate in one kernel each: no [E, 2D+1] / raw-TP tensors in HBM
             if d.dtype != h.dtype:
@@ -176,7 +181,8 @@ class SEGNNLayer(nn.Module):
             # operand scale of [h | a]: h's is known (the previous layer returned it), so only `a` is scanned
             sc = None
             if f32 and h_scale is not None and halo is None:
-                sc = ops.join_pow2_scales(h_scale, ops.pow2_scale([a]))
+                # (the one-launch message kernel returns the scale of its sums: no scan)
+                sc = ops.join_pow2_scales(h_scale, a_scale if a_scale is not None else ops.pow2_scale([a]))
             if self.upd2.fused_supported(False) and h.stride(-1) == 1:
                 if isinstance(self.upd1, SHTensorProduct) and a.stride(-1) == 1:
                     # both products in one launch: u stays on chip with a power-of-two scale per row
@@ -253,8 +259,15 @@ class SEGNN(nn.Module):
             Y, d, A = ops.edge_geometry(g, lmax=self.lmax, want_edge=not one_launch)
         if x.dtype == torch.bfloat16 and self.lmax != 2:
             raise RuntimeError("bf16 storage is implemented for l_max = 2 (BASELINE config 3)")
-        h = self.embed(x, A)
         sc = None
+        if (x.dtype == torch.float32 and not (torch.is_grad_enabled() and _needs_grad(self, x)) and x.is_cuda and
+                getattr(self.embed, "exact", None) is False and A.shape[0] == x.shape[0] and x.shape[0] > 0 and
+                self.embed.fused_supported(False)):
+            # inference, fp32, a shape of the fused kernel: the embedding's epilogue emits the operand scale of h, so that
+            # layer 0 runs no scan over h
+            h, sc = self.embed.forward_fused([(x, None)], A, gate=False, out_scale=10)
+        else:
+            h = self.embed(x, A)
         if halo is not None:
             halo.overflow = None
         for layer in self.layers:
