@@ -65,6 +65,37 @@ def gate_blocks(x, ns, blocks):
     return np.concatenate(out, 1)
 
 
+def hidden_irreps(H, lmax):
+    """(hidden, gated) irreps strings of a layer: Hx0e+Hx1o(+Hx2e) and Hx0e + lmax*H x0e + Hx1o (+Hx2e)."""
+    tail = f"+{H}x1o" + (f"+{H}x2e" if lmax == 2 else "")
+    return f"{H}x0e" + tail, f"{H}x0e+{lmax * H}x0e" + tail
+
+
+def message_sums(lmax, H, wn1, wn2, h, rel, src, dst, n_nodes, return_messages=False):
+    """The message function of one layer (include/e3gnn.h, "Fused message function"):
+
+        a_i = sum_{e: dst[e] = i} gate(TP2(gate(TP1([h[dst[e]] | h[src[e]] | |rel_e|]; Y(rel_e))); Y(rel_e)))
+
+    ``wn1`` / ``wn2``: the ``(W, norms)`` pairs of the two products as ``tp_oracle.forward`` takes them.  ``h`` [N, (lmax+1)^2 H],
+    ``rel`` [E, 3] the edge vectors (periodicity is the caller's business: the raw difference pos[src] - pos[dst] or its minimum
+    image), ``src`` / ``dst`` [E] in any order.  Y = ``cg.sh_component``: 0 for a zero vector at l > 0, the kernels' convention.
+    -> a [n_nodes, width] (and the per-edge messages [E, width] with ``return_messages``)."""
+    from . import cg, tp_oracle as T
+    hid, gated = hidden_irreps(H, lmax)
+    blocks = [(l, H) for l in range(1, lmax + 1)]
+    h = np.asarray(h, np.float64)
+    rel = np.asarray(rel, np.float64).reshape(-1, 3)
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    Y = cg.sh_component(lmax, rel)
+    d = np.sqrt((rel * rel).sum(1))
+    m = np.concatenate([h[dst], h[src], d[:, None]], 1)
+    m = gate_blocks(T.forward(f"{hid}+{hid}+1x0e", gated, lmax, m, Y, *wn1), H, blocks)
+    m = gate_blocks(T.forward(hid, gated, lmax, m, Y, *wn2), H, blocks)
+    a = np.zeros((n_nodes, h.shape[1]))
+    np.add.at(a, dst, m)
+    return (a, m) if return_messages else a
+
+
 def forward_l2(params, H, num_layers, in_irreps, out_irreps, x, pos, rowptr, src):
     """l_max = 2 model (hidden Hx0e+Hx1o+Hx2e), every TP through tp_oracle."""
     from . import tp_oracle as T

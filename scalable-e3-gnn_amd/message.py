@@ -56,6 +56,11 @@ class FusedMessage:
         return dtype == torch.bfloat16 and bool(_lib.load().e3_msg_supports(self._plans.handle(None), _lib.E3_BF16))
 
     def packed(self, msg1, msg2, device, dtype=torch.float32) -> torch.Tensor:
+        """The packed image of the two products' weights and norms, built once and kept per (device, dtype).  The image is
+        rebuilt when the ``(data_ptr, _version)`` of one of the twelve tensors changes: in-place operations (``mul_``,
+        ``copy_``, an optimizer step, ``load_state_dict``) and a replaced tensor are seen.  Writes through ``.data`` (or any
+        other alias with a version counter of its own) do NOT advance ``_version`` and are not picked up: the stale image
+        is used until another change is seen."""
         lib = _lib.load()
         w1, n1 = self._tensors(msg1)
         w2, n2 = self._tensors(msg2)
