@@ -31,6 +31,10 @@ def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True,
     Y = torch.empty((E, ny), dtype=torch.float32, device=dev) if want_edge else None
     d = torch.empty(E, dtype=torch.float32, device=dev) if (want_dist and want_edge) else None
     A = torch.empty((N, ny), dtype=torch.float32, device=dev) if want_node_attr else None
+    if E == 0:  # nothing to launch on (an empty src has no address to hand to the library): every row is empty, A = [1, 0, ...]
+        if A is not None:
+            A.zero_()[:, 0] = 1.0
+        return Y, d, A
     fn = {1: "e3_edge_geometry", 2: "e3_edge_geometry_l2"}[lmax]
     outs = (Y.data_ptr() if Y is not None else None, d.data_ptr() if d is not None else None,
             A.data_ptr() if A is not None else None, _stream(pos4))
@@ -102,6 +106,8 @@ class _EdgeGeometryFn(torch.autograd.Function):
         gY, gd, gA = c(gY), c(gd), c(gA)
         p = lambda t: t.data_ptr() if t is not None else None
         gstrain = None
+        if g.num_edges == 0:  # no edge: the outputs do not depend on pos or strain
+            return gpos.zero_(), (torch.zeros_like(strain) if strain is not None else None), None, None, None
         with torch.cuda.device(pos4.device):
             lib = _lib.load()
             if strain is not None:
@@ -172,7 +178,7 @@ class _GatherConcatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, extra, g):
         ctx.g, ctx.has_extra = g, extra is not None
-        ctx.D, ctx.nx = h.shape[1], (extra.reshape(g.num_edges, -1).shape[1] if extra is not None else 0)
+        ctx.D, ctx.nx = h.shape[1], (extra.shape[1] if extra is not None else 0)  # extra: [E, n_extra] (gather_concat)
         return _gather_concat_raw(h, g, extra)
 
     @staticmethod
@@ -182,6 +188,8 @@ class _GatherConcatFn(torch.autograd.Function):
         N = g.rowptr.numel() - 1
         gh = torch.empty((N, D), dtype=torch.float32, device=gm.device)
         gx = torch.empty((g.num_edges, nx), dtype=torch.float32, device=gm.device) if nx else None
+        if g.num_edges == 0:  # no edge: nothing reaches h (an empty tensor has no address to hand to the library)
+            return gh.zero_(), gx, None
         with torch.cuda.device(gm.device):
             _lib.check(_lib.load().e3_gather_concat_backward(gm.data_ptr(), gm.stride(0), D, g.rowptr.data_ptr(),
                                                              g.src.data_ptr(), N, nx, gh.data_ptr(), gh.stride(0),
@@ -192,6 +200,16 @@ class _GatherConcatFn(torch.autograd.Function):
         return gh, gx, None
 
 
+def _extra_columns(extra, E):
+    """extra [E] or [E, ...] -> [E, n_extra]; E = 0 has no -1 to infer: the width is that of the trailing dimensions"""
+    if E == 0:
+        nx = 1
+        for s in extra.shape[1:]:
+            nx *= s
+        return extra.reshape(0, nx)
+    return extra.reshape(E, -1)
+
+
 def _gather_concat_raw(h, g, extra):
     if h.stride(-1) != 1:
         h = h.contiguous()
@@ -199,9 +217,11 @@ def _gather_concat_raw(h, g, extra):
     E = g.num_edges
     nx = 0
     if extra is not None:
-        extra = extra.reshape(E, -1).contiguous()
+        extra = _extra_columns(extra, E).contiguous()
         nx = extra.shape[1]
     out = torch.empty((E, 2 * D + nx), dtype=torch.float32, device=h.device)
+    if E == 0:  # nothing to launch on: the empty result has no address to hand to the library
+        return out
     with torch.cuda.device(h.device):
         _lib.check(_lib.load().e3_gather_concat(h.data_ptr(), h.stride(0), D, g.rowptr.data_ptr(), g.src.data_ptr(), N,
                                                 extra.data_ptr() if nx else None, nx, out.data_ptr(), out.stride(0),
@@ -215,7 +235,7 @@ def gather_concat(h: torch.Tensor, g: RadiusGraph, extra: torch.Tensor | None = 
     if extra is not None:
         _check(extra, "extra")
     if _wants_grad(h, extra):
-        ex2 = extra.reshape(g.num_edges, -1) if extra is not None else None
+        ex2 = _extra_columns(extra, g.num_edges) if extra is not None else None
         return _GatherConcatFn.apply(h, ex2, g)
     return _gather_concat_raw(h, g, extra)
 
@@ -271,6 +291,8 @@ class _SegmentSumFn(torch.autograd.Function):
         ga = ga.contiguous()
         N, D = ga.shape
         gm = torch.empty((g.num_edges, D), dtype=torch.float32, device=ga.device)
+        if g.num_edges == 0:
+            return gm, None
         with torch.cuda.device(ga.device):
             _lib.check(_lib.load().e3_segment_sum_backward(ga.data_ptr(), ga.stride(0), g.rowptr.data_ptr(), N, D,
                                                            gm.data_ptr(), max(gm.stride(0), D), _stream(ga)),
@@ -283,6 +305,8 @@ def _segment_sum_raw(msg, g):
         msg = msg.contiguous()
     N = g.rowptr.numel() - 1
     D = msg.shape[1]
+    if g.num_edges == 0:  # nothing to launch on: every row is empty
+        return torch.zeros((N, D), dtype=msg.dtype, device=msg.device)
     agg = torch.empty((N, D), dtype=msg.dtype, device=msg.device)
     fn = "e3_segment_sum" if msg.dtype == torch.float32 else "e3_segment_sum_bf16"
     with torch.cuda.device(msg.device):
