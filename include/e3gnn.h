@@ -520,7 +520,7 @@ int e3_tp_forward_fused_scatter(const e3_tp_plan* plan, const e3_tp_segment* seg
  *   tiles_per_block: work granularity (0 = default).  hidden = 32, l_max = 2, fp32: the weights-stationary kernel
  *            (e3_msg_ws.hip: one workgroup of 8 waves per CU walks chunks of 16 * tiles_per_block edges, default 256 edges,
  *            dealt round-robin to the workgroups of an XCD; tiles inside a chunk are cut at dst-run boundaries: <= 16 edges,
- *            <= 2 runs).  Other shapes, or tiles_per_block < 0: the one-wave-per-tile kernel (e3_msg_fused.hip), where
+ *            <= 2 runs).  Other shapes, or tiles_per_block < 0: the one-wave-per-tile kernel (e3_msg_fused_kernel.h), where
  *            |tiles_per_block| = consecutive 16-edge tiles a wave processes before it jumps to its workgroup's next chunk (0 = 4)
  *   E      : edges of this call, dst-sorted (src / dst int32); E <= 2^31 - 17 (E3_ERR_INVALID_ARG beyond: the edge ids are
  *            int32 and the kernel's tile arithmetic is 32-bit)

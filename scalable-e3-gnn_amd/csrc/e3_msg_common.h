@@ -1,6 +1,7 @@
-// Shared pieces of the fused message kernels (e3_msg_fused.hip: one wave per 16-edge tile; e3_msg_ws.hip: weights
-// stationary in registers, one workgroup per tile stream).  Internal header, included inside namespace e3 after
-// e3_tp_mfma_core.h and cg_tables.h.
+// Shared device pieces of the message kernels (e3_msg_fused_kernel.h: one wave per 16-edge tile; e3_msg_ws.hip: weights
+// stationary in registers, one workgroup per tile stream; e3_msg_premix.hip, e3_msg_pack.hip: the per-node and per-weight
+// launches).  Internal header, included inside namespace e3 after e3_tp_mfma_core.h and cg_tables.h; what the host files
+// share is in e3_msg_plan.h.
 #pragma once
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -133,6 +134,30 @@ __device__ __forceinline__ void split8(const float (&f)[8], uint4& bh, uint4& bl
   }
   bh = uint4{ph[0], ph[1], ph[2], ph[3]};
   bl = uint4{pl[0], pl[1], pl[2], pl[3]};
+}
+
+// Everything one tensor product of the one-wave-per-tile kernel (and of the pre-mix launch) needs besides its inputs.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+struct TpCtx {
+  __amdgpu_buffer_rsrc_t w;  // buffer descriptor over ALL weight blocks (wave-uniform, 4 SGPRs)
+  uint32_t wrole;       // byte offset of this role's first block; block b at wrole + b * 2048 (1 KiB hi then 1 KiB lo)
+  uint32_t woff;        // this lane's byte offset inside a block half: lane * 16
+  const float* ud;      // FIRST: this lane's row of the dst pre-mix table (+ 4 g), else nullptr
+  const float* wd;      // FIRST: d-term weights in LDS (+ 4 g)
+  float dsc;            // FIRST: distance * xs
+};
+
+// A operand of one weight block: buffer load = descriptor (SGPRs) + scalar block offset + this lane's 32-bit offset, so
+// the ~70 block addresses of a product cost no vector registers and no 64-bit address arithmetic
+template <bool IO16>
+__device__ __forceinline__ void load_w(const TpCtx& cx, const int blk, uint4& hi, uint4& lo) {
+  const uint32_t so = cx.wrole + (uint32_t)blk * 2048u;
+  const u32x4 h = __builtin_amdgcn_raw_buffer_load_b128(cx.w, cx.woff, so, 0);
+  hi = uint4{h[0], h[1], h[2], h[3]};
+  if constexpr (!IO16) {
+    const u32x4 l = __builtin_amdgcn_raw_buffer_load_b128(cx.w, cx.woff + 1024u, so, 0);
+    lo = uint4{l[0], l[1], l[2], l[3]};
+  }
 }
 
 // real "component" spherical harmonics of the edge vector (same expressions as edge_geometry_l2_kernel, e3_edge_ops.hip)

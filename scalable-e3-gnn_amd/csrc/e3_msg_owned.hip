@@ -2,8 +2,7 @@
 // they write every row of `out` exactly once (the ownership rule stands above `flush` in e3_msg_ws.hip):
 //   msg_boundary_merge_kernel   the first and the last flushed node of every chunk, from their partial sums
 //   msg_isolated_rows_kernel    nodes without an incoming edge
-#include "e3_common.h"
-#include "e3_msg_ws.h"
+#include "e3_msg_plan.h"
 
 #include <algorithm>
 

@@ -1,9 +1,10 @@
 // The SEGNN message function with the weights STATIONARY in registers (same operator, C ABI and packed-weight format as
-// e3_msg_fused.hip; this file is the kernel e3_msg_forward launches for H = 32).
+// the one-wave-per-tile kernel, e3_msg_fused_kernel.h; this file is the kernel e3_msg_forward* launch for H = 32, l_max = 2,
+// and its launch function, msg_ws_launch, called from e3_msg_forward.hip).
 //
 //     a_i = sum_{e: dst(e) = i}  gate( TP2( gate( TP1( [h_dst | h_src | d_e] ; Y_e ) ) ; Y_e ) )
 //
-// Why a second structure: in e3_msg_fused.hip every wave owns a 16-edge tile from gather to scatter and therefore streams
+// Why a second structure: in the one-wave-per-tile kernel every wave owns a 16-edge tile from gather to scatter and therefore streams
 // ALL weight blocks of both products (140 KB) plus 106 pre-mix loads per tile through the CU's vector-memory path -- 283
 // KB per 16 edges, and that path (one 1-KiB instruction per ~28 cycles per CU) is what the kernel ran at.  Here ONE
 // workgroup of 8 waves per CU walks a stream of tiles and the waves split the OUTPUT tiles of the two products:
@@ -26,7 +27,10 @@
 //                           maxima and pre-mix rows (a row already staged for the previous tile is not copied again), ids of s + 2
 //                team 1   : product #2 + gate of tile s - 1 -> out tile
 //   phase Y(s)   team 0   : product #1 + gate of tile s -> B fragments of product #2, written directly (below)
-//                waves 4-5: run sums of tile s - 1 (fp32 atomics, one per node, column and chunk)
+//                waves 4-5: run sums of tile s - 1.  Owned sums (e3_msg_forward_owned*): a node's row is stored once, by
+//                           plain stores (the ownership rule stands above `flush`); the accumulating launches that remain
+//                           (sharded and continued sums into a zeroed or continued `out`): fp32 atomics, one per node,
+//                           column and chunk
 //                waves 6-7: copies of the (pre-split) h[src] rows of tile s + 1 (9 x 1 KiB each; fp32: into the image of the
 //                           tile's parity -- product #1 is reading the other one)
 //
@@ -41,9 +45,8 @@
 //
 // Tiles are cut adaptively: a tile never spans more than two dst runs (so the pre-mix rows of a tile fit two of the four
 // staged row slots and the segment sum has at most two runs); with dst-sorted edges and ~24 edges per node most tiles are full.
-#include "e3_common.h"
+#include "e3_msg_plan.h"
 #include "cg_tables.h"
-#include "e3_msg_ws.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -224,19 +227,11 @@ __device__ __forceinline__ void dma16(const void* gsrc, uint32_t lds_dst) {
 }
 // the same copy marked non-temporal: rows that are read once (the pre-mix table) should not displace the gathered h rows,
 // which every neighbouring tile of the XCD reads again, from the L2.  Measured (FETCH_SIZE, 1 M particles): 2 x 4.84 -> 2 x 4.62
-// GB per launch, time unchanged.  (Plain stores instead of atomics for rows whose run lies inside one chunk were tried too:
-// FETCH_SIZE and the time did not move -- the zero-filled rows are still on chip when the atomics arrive.)
-#ifndef WS_UNT
-#define WS_UNT 1
-#endif
+// GB per launch, time unchanged.
 __device__ __forceinline__ void dma16_stream(const void* gsrc, uint32_t lds_dst) {
-#if WS_UNT
   uint32_t keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#else
-  dma16(gsrc, lds_dst);
-#endif
 }
 __device__ __forceinline__ void dma4(const void* gsrc, uint32_t lds_dst) {
   uint32_t keep;
@@ -351,48 +346,28 @@ __device__ __forceinline__ void ws_load_w(const float* packed, const int prod /*
 // tile), accS (scalar tile) -- raw contractions, norms applied by the gates.
 //
 // The B fragments are consumed as a flat list of items -- (degree 0), (degree 1: 3 components, feature-first operand),
-// (degree 2: 5 components, feature-first operand) -- and item i + WS_PF is REQUESTED (its two 16-byte LDS reads, and the pre-mix
+// (degree 2: 5 components, feature-first operand) -- and item i + kWsPF is REQUESTED (its two 16-byte LDS reads, and the pre-mix
 // values that initialise its accumulators) before item i computes.  hipcc's scheduler left to itself issues every LDS read
 // right in front of its use (it minimises registers): ~25 exposed LDS round trips per product; the requests are therefore
 // pinned with sched_barrier.  All indices are compile-time constants (operand ring = registers).
 // ------------------------------------------------------------------------------------------------------------------
-#ifndef WS_XROT
-#define WS_XROT 2   // measured 19.43 -> 19.00 ms per launch pair (1: 19.24, 3: 19.38)
-#endif
-#ifndef WS_NREG
-#define WS_NREG 1
-#endif
-#ifndef WS_PRIO1
-#define WS_PRIO1 WS_PRIO   // product #1 (phase Y: its partners have slack)
-#endif
-#ifndef WS_LMAX1
-#define WS_LMAX1 0   // 1: also instantiate the kernel for l_max = 1 (correct, but 10.0 vs 6.4 ms per launch pair against the one-wave-per-tile kernel: the phase structure does not pay for so little work per edge)
-#endif
-#ifndef WS_INITMAP
-#define WS_INITMAP 0
-#endif
-#ifndef WS_YROT
-#define WS_YROT 0
-#endif
-#ifndef WS_PF
-#define WS_PF 2
-#endif
+constexpr int kWsPF = 2;    // prefetch distance of the B fragments, in items
+constexpr int kWsXrot = 2;  // rotation of the phase-X service jobs against the product roles (ws_run): measured 19.43 -> 19.00
+                            // ms per launch pair (1: 19.24, 3: 19.38)
 // Whole-vector forms (f32x4 fma / products -> v_pk_fma_f32 / v_pk_mul_f32 with the per-edge factor broadcast through op_sel) of
 // the folds and the gate epilogues, fp32 storage only (bf16 storage measured 4 % slower with them).  bit 0: folds with table
 // couplings, 1: folds with one-harmonic couplings, 2: epilogue of product #2, 3: epilogue of product #1.  Measured 19.76 ->
 // 19.50 ms per launch pair: the product waves are bound by LDS reads and dependent-MFMA latency more than by vector issue.
-#ifndef WS_PKT
-#define WS_PKT 15
-#endif
+constexpr int kWsPKT = 15;
 // per table coupling: bit 0 (1,1,2), 1 (1,2,1), 2 (2,1,1), 3 (2,2,2).  Path (2, 1, 1) stays in scalar form: its vector form gives
 // wrong sums with this compiler (hipcc 7.2; the other three and every other use check out against the oracle) --
 // tools/build_variant.sh x "-DWS_PKZ=15" e3_msg_ws + tools/exp_check.py x tests/test_msg_fused_gpu.py reproduces it.
 #ifndef WS_PKZ
 #define WS_PKZ 11
 #endif
-#ifndef WS_PRIO
-#define WS_PRIO 0   // s_setprio of a product wave while it multiplies (0: none; 2 measured 20.4 vs 19.6 ms: the partner waves are near-critical too)
-#endif
+// s_setprio of a product wave while it multiplies (0: none; 2 measured 20.4 vs 19.6 ms: the partner waves are near-critical
+// too).  The instruction is issued all the same, for both products.
+constexpr int kWsPrio = 0;
 template <int LMAX>
 struct TpItems {  // degrees in DESCENDING order: the largest fold (degree l_max) overlaps the products of the degrees after it
   static constexpr int N = (LMAX + 1) * (LMAX + 1) + LMAX;
@@ -427,7 +402,7 @@ struct TpRun {
   f32x4& accS;
   float dsc;
   // operand ring and per-degree state (everything indexed at compile time)
-  uint4 bh[WS_PF + 1], bl[WS_PF + 1];
+  uint4 bh[kWsPF + 1], bl[kWsPF + 1];
   f32x4 uV[3][3][5];       // [l1][l2][a]: mix-first accumulators of the paths into the vector tile
   f32x4 wdV;               // FIRST: d-term weights of the vector tile
   f32x4 yv[3];             // harmonics of this lane's edge (y[0..8], d xs)
@@ -445,7 +420,7 @@ struct TpRun {
   template <int I>
   __device__ __forceinline__ void request() {
     if constexpr (I < IT::N) {
-      constexpr int L1 = IT::l1(I), a = IT::a(I), slot = I % (WS_PF + 1);
+      constexpr int L1 = IT::l1(I), a = IT::a(I), slot = I % (kWsPF + 1);
       constexpr int fr = a >= 0 ? L::frag(L1, a) : L::frag_ff(L1);
       if constexpr (a >= 0 || SC) {
         if constexpr (PIMG) {
@@ -485,7 +460,7 @@ struct TpRun {
 
   template <int I>
   __device__ __forceinline__ void compute() {
-    constexpr int L1 = IT::l1(I), a = IT::a(I), slot = I % (WS_PF + 1);
+    constexpr int L1 = IT::l1(I), a = IT::a(I), slot = I % (kWsPF + 1);
     const uint4 xh = bh[slot], xl = bl[slot];
     if constexpr (a >= 0) {
       if constexpr (L1 == 0 && FIRST && LV > 0) {  // distance channel of product #1: couples through (0, l, l)
@@ -524,7 +499,7 @@ struct TpRun {
                 // whole-vector form: two v_pk_fma_f32 with the coupling broadcast through op_sel instead of four v_fmac
                 const float z = zq[L1][L2][(aa * D3 + c) >> 2][(aa * D3 + c) & 3];
                 constexpr int zi = (L1 == 1 && L2 == 1) ? 0 : (L1 == 1 && L2 == 2) ? 1 : (L1 == 2 && L2 == 1) ? 2 : 3;
-                if constexpr (!IO16 && (WS_PKT & 1) && ((WS_PKZ >> zi) & 1)) {
+                if constexpr (!IO16 && (kWsPKT & 1) && ((WS_PKZ >> zi) & 1)) {
                   accV[c] = __builtin_elementwise_fma(uV[L1][L2][aa], f32x4{z, z, z, z}, accV[c]);
                 } else {
 #pragma unroll
@@ -542,7 +517,7 @@ struct TpRun {
 #pragma unroll
             for (int aa = 0; aa < D1; ++aa)
               if (z_nonzero<L1, L2, LV>(aa, c)) {
-                if constexpr (!IO16 && (WS_PKT & 2)) {
+                if constexpr (!IO16 && (kWsPKT & 2)) {
                   accV[c] = __builtin_elementwise_fma(uV[L1][L2][aa], f32x4{zz[aa][c], zz[aa][c], zz[aa][c], zz[aa][c]}, accV[c]);
                 } else {
 #pragma unroll
@@ -554,12 +529,12 @@ struct TpRun {
     });
   }
 
-  // One scheduling region per item: the requests of item I + WS_PF, the products of item I and -- at the first item of a
+  // One scheduling region per item: the requests of item I + kWsPF, the products of item I and -- at the first item of a
   // degree -- the fold of the PREVIOUS degree (vector work that depends only on finished products: it fills the issue slots
   // between this degree's MFMAs).
   template <int I>
   __device__ __forceinline__ void step() {
-    request<I + WS_PF>();
+    request<I + kWsPF>();
     __builtin_amdgcn_sched_barrier(0);
     compute<I>();
     if constexpr (IT::first(I) && IT::l1(I) < LMAX) fold<IT::l1(I) + 1>();
@@ -581,9 +556,9 @@ struct TpRun {
       if constexpr (tS >= 0) accS = init[64 * tS];
     }
     request<0>();
-    if constexpr (WS_PF >= 2) request<1>();
-    if constexpr (WS_PF >= 3) request<2>();
-    static_assert(WS_PF >= 1 && WS_PF <= 3, "prefetch distance");
+    if constexpr (kWsPF >= 2) request<1>();
+    if constexpr (kWsPF >= 3) request<2>();
+    static_assert(kWsPF >= 1 && kWsPF <= 3, "prefetch distance");
     __builtin_amdgcn_sched_barrier(0);
     dsc = yv[2][1];
     WS_TPMARK(0)
@@ -631,18 +606,17 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
   constexpr bool TEAM1 = W >= 4;
   constexpr int ROLE = W & 3;
   // service job of a team-0 wave in phase X: 0 / 1 conversion of rows 0-7 / 8-15 (+ initial values; fp32 storage: 0 the
-  // feature-first operands, 1 initial values), 2 initial values + edge table, 3 the tile cutter.  Rotated against the product roles (WS_XROT) so that the two conversion waves -- the longest,
-  // vector-heavy jobs -- share their SIMDs with the lighter roles of product #2 (l3 = 1 tiles: waves 6, 7), not with the
+  // feature-first operands, 1 initial values), 2 initial values + edge table, 3 the tile cutter.  Rotated against the product
+  // roles (kWsXrot) so that the two conversion waves -- the longest, vector-heavy jobs -- share their SIMDs with the lighter roles of product #2 (l3 = 1 tiles: waves 6, 7), not with the
   // l3 = 2 roles (waves 4, 5), which are the longest of phase X
-  constexpr int SX = TEAM1 ? -1 : ((W + WS_XROT) & 3);
-  // scalar-type tiles whose initial values this wave computes (two at a time): WS_INITMAP 0: two tiles on each of the jobs
-  // 0-2; 1: four on the cutter's wave (the shortest job), two on the table's wave, none on the conversion waves (the longest)
-  // fp32 storage (pre-split rows: job 0 = the feature-first operands, no conversion): four tiles on job 1, two on the table's wave
-  constexpr int ITB = SX < 0 ? 0 : L::PRE ? (SX == 2 ? 4 : 0) : (WS_INITMAP ? (SX == 3 ? 0 : 4) : 2 * SX);
-  constexpr int ITE0 = SX < 0 ? 0 : L::PRE ? (SX == 1 ? 4 : (SX == 2 ? 6 : 0))
-                                           : (WS_INITMAP ? (SX == 3 ? 4 : (SX == 2 ? 6 : 4)) : (SX <= 2 ? 2 * SX + 2 : 2 * SX));
+  constexpr int SX = TEAM1 ? -1 : ((W + kWsXrot) & 3);
+  // scalar-type tiles [ITB, ITE) whose initial values this wave computes (two at a time).  bf16 storage: two tiles on each of
+  // the jobs 0-2; fp32 storage (pre-split rows: job 0 = the feature-first operands, no conversion): four tiles on job 1, two
+  // on the table's wave
+  constexpr int ITB = SX < 0 ? 0 : L::PRE ? (SX == 2 ? 4 : 0) : 2 * SX;
+  constexpr int ITE0 = SX < 0 ? 0 : L::PRE ? (SX == 1 ? 4 : (SX == 2 ? 6 : 0)) : (SX <= 2 ? 2 * SX + 2 : 2 * SX);
   constexpr int ITE = ITE0 < G::T(0) ? ITE0 : G::T(0);
-  constexpr int SY = TEAM1 ? ((W + WS_YROT) & 3) : -1;  // phase Y jobs of team 1: 0 / 1 run sums, 2 / 3 row copies
+  constexpr int SY = TEAM1 ? (W & 3) : -1;  // phase Y jobs of team 1: 0 / 1 run sums, 2 / 3 row copies
   using O = Own<LMAX, TT, ROLE>;
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
@@ -672,7 +646,8 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
   // otherwise hipcc places counted vmcnt waits for them at their first uses INSIDE the loop, where the counter also holds
   // this wave's copies / atomics
   wait_vm0();
-  // per-column norms of this wave's output tiles: they do not change from tile to tile, so they live in registers (WS_NREG;
+  // per-column norms of this wave's output tiles: they do not change from tile to tile, so they live in registers (norm slot s of
+  // a table is the f32x4 at [4 s] + g;
   // read from the LDS table in the epilogue, each read sat with its latency exposed right in front of its use: ~6 round trips
   // per product)
   f32x4 nrS = {0.f, 0.f, 0.f, 0.f}, nrG = {0.f, 0.f, 0.f, 0.f}, nrV[5];
@@ -1100,14 +1075,17 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         const float isrow = IO16 ? 1.0f : __builtin_bit_cast(float, 0x7F000000u - sb);
         f32x4 accV[5], accG, accS;
         // (the product wave is the longest of its SIMD pair in either phase: it gets the vector issue slots first)
-        __builtin_amdgcn_s_setprio(WS_PRIO);
+        __builtin_amdgcn_s_setprio(kWsPrio);
         WS_PM(5)
         ws_tp<LMAX, TT, ROLE, false, IO16>(w, smem + L::o_b2 + lane * 16, nullptr, lane, ztr, nullptr, nullptr, nullptr, accV, accG, accS, y, tpmk);
         WS_PM0
-        const f32x4* nt = reinterpret_cast<const f32x4*>(n2tab) + g;
+        // (`nt`, here and in phase Y: the LDS norm table the epilogues read before the norms moved to registers.  Nothing reads
+        // it, but hipcc's register assignment in the bf16 instantiations follows the declaration: without it their code moves
+        // (profiles/msg_split_isa.txt).  It goes with the next change that measures those kernels again.)
+        [[maybe_unused]] const f32x4* nt = reinterpret_cast<const f32x4*>(n2tab) + g;
         float* orow = reinterpret_cast<float*>(smem + L::o_o) + j * L::RS;
         if constexpr (O::tS >= 0) {
-          const f32x4 nv = WS_NREG ? nrS : nt[4 * O::tS];
+          const f32x4 nv = nrS;
           f32x4 o;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -1118,16 +1096,16 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         }
         if constexpr (O::LV > 0) {  // a lane's 4 channels x (2l+1) components are contiguous in the output row
           constexpr int Dc = 2 * O::LV + 1;
-          const f32x4 gn = WS_NREG ? nrG : nt[4 * O::tG];
+          const f32x4 gn = nrG;
           f32x4 gt;
 #pragma unroll
           for (int r = 0; r < 4; ++r) gt[r] = sigmoid_(accG[r] * gn[r] * isrow) * isrow;
           float o[4 * Dc];
 #pragma unroll
           for (int c = 0; c < Dc; ++c) {
-            const f32x4 nv = WS_NREG ? nrV[c] : nt[4 * (G::slot0(O::LV) + Dc * O::t + c)];
+            const f32x4 nv = nrV[c];
             f32x4 oc;
-            if constexpr (!IO16 && (WS_PKT & 4)) {
+            if constexpr (!IO16 && (kWsPKT & 4)) {
               oc = accV[c] * nv * gt;  // whole-vector products: v_pk_mul_f32
             } else {
 #pragma unroll
@@ -1159,7 +1137,7 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         const int slot = (j >= t0.n0 && j < t0.n) ? t0.sl1 : t0.sl0;
         const float* urow = reinterpret_cast<const float*>(smem + L::o_u + slot * L::U_ROW) + 4 * g;
         f32x4 accV[5], accG, accS;
-        __builtin_amdgcn_s_setprio(WS_PRIO1);
+        __builtin_amdgcn_s_setprio(kWsPrio);
         WS_PM(5)
         const unsigned char* img = smem + L::o_g + (L::PRE ? (s & 1) * L::P_IMG : 0);
         ws_tp<LMAX, TT, ROLE, true, IO16>(w, L::PRE ? img + L::p_abase(lane) : smem + L::o_b1 + lane * 16,
@@ -1171,12 +1149,12 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         // on the row's inputs only)
         float srow = 1.0f;
         if constexpr (!IO16) srow = pow2_scale_from_bits(__builtin_bit_cast(uint32_t, bwx * fmaxf(fmaxf(hs, hd), dsc)), 12);
-        const f32x4* nt = reinterpret_cast<const f32x4*>(n1tab) + g;  // norm slot s at nt[4 s]; carries 1 / (sw1 xs)
+        [[maybe_unused]] const f32x4* nt = reinterpret_cast<const f32x4*>(n1tab) + g;  // (see phase X; the norms carry 1 / (sw1 xs))
         // this wave's half (tile t: k slots 4 t .. 4 t + 3) of every fragment lane: 8 bytes hi, 8 bytes lo
         unsigned char* b2 = smem + L::o_b2 + lane * 16 + 8 * O::t;
         auto put4 = [&](const int fr, const float (&f)[4]) { ws_put4<IO16>(b2 + fr * L::FRB, f, srow); };
         if constexpr (O::tS >= 0) {
-          const f32x4 nv = WS_NREG ? nrS : nt[4 * O::tS];
+          const f32x4 nv = nrS;
           float f[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -1187,7 +1165,7 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         }
         if constexpr (O::LV > 0) {
           constexpr int Dc = 2 * O::LV + 1;
-          const f32x4 gn = WS_NREG ? nrG : nt[4 * O::tG];
+          const f32x4 gn = nrG;
           f32x4 gt;
 #pragma unroll
           for (int r = 0; r < 4; ++r) gt[r] = sigmoid_(accG[r] * gn[r]);
@@ -1199,9 +1177,9 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
           f32x4 fsv = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int c = 0; c < Dc; ++c) {
-            const f32x4 nv = WS_NREG ? nrV[c] : nt[4 * (G::slot0(O::LV) + Dc * O::t + c)];
+            const f32x4 nv = nrV[c];
             f32x4 fv;
-            if constexpr (!IO16 && (WS_PKT & 8)) {
+            if constexpr (!IO16 && (kWsPKT & 8)) {
               fv = accV[c] * nv * gt;  // whole-vector products / fma: v_pk_mul_f32, v_pk_fma_f32
               const f32x4 zc = {zz[c][0], zz[c][0], zz[c][0], zz[c][0]};
               fsv = c == 0 ? zc * fv : __builtin_elementwise_fma(zc, fv, fsv);
@@ -1334,8 +1312,10 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // ------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------
+// l_max = 1 (the templates are generic in it) does not take this kernel: correct, but 10.0 vs 6.4 ms per launch pair against
+// the one-wave-per-tile kernel -- the phase structure does not pay for so little work per edge
 bool msg_ws_supported(int lmax, int hidden, int dtype) {
-  return (lmax == 2 || (lmax == 1 && WS_LMAX1)) && hidden == 32 && (dtype == E3_F32 || dtype == E3_BF16);
+  return lmax == 2 && hidden == 32 && (dtype == E3_F32 || dtype == E3_BF16);
 }
 
 int msg_ws_split_floats(int lmax, int hidden) {
@@ -1343,77 +1323,63 @@ int msg_ws_split_floats(int lmax, int hidden) {
 }
 static_assert(MsgSplit<2>::FLOATS == 9 * 32 && MsgSplit<1>::FLOATS == 4 * 32, "msg_ws_split_floats");
 
-int msg_ws_chunk_edges(int chunk_edges) { return chunk_edges > 0 ? (chunk_edges + 15) / 16 * 16 : 256; }
+int msg_ws_chunk_edges(int tiles_per_block) {
+  return tiles_per_block > (1 << 20) ? (1 << 24) : tiles_per_block > 0 ? tiles_per_block * 16 : 256;
+}
 
 // the kernel's split of the edges: eight contiguous eighths of e_per_xcd edges (a multiple of 16), each cut into chunks
-int64_t msg_ws_owned_chunks(int64_t E, int chunk_edges) {
-  const int64_t chunk = msg_ws_chunk_edges(chunk_edges);
+int64_t msg_ws_owned_chunks(int64_t E, int tiles_per_block) {
+  const int64_t chunk = msg_ws_chunk_edges(tiles_per_block);
   const int64_t e_per_xcd = ((E + 7) / 8 + 15) / 16 * 16;
   return 8 * ((e_per_xcd + chunk - 1) / chunk);
 }
 
-int msg_ws_launch(int lmax, int hidden, int dtype, const void* h, int64_t ldh, int64_t N, const float* pos4, const int32_t* src,
-                  const int32_t* dst, int64_t E, const void* packed, const float* in_scale, const float* premix, float* out,
-                  int64_t ldo, int chunk_edges, hipStream_t stream, const float* box, const PbcCell* cell, float* part,
-                  int* part_node, uint32_t* amax) {
-  if (!msg_ws_supported(lmax, hidden, dtype)) return E3_ERR_UNSUPPORTED;
-  if (part && (!part_node || !amax)) return E3_ERR_INVALID_ARG;
-  const int pb = cell ? kCell : (box ? kBox : kOpen);
-  if (E > 0x7fffffffLL - 65536) return E3_ERR_UNSUPPORTED;  // 32-bit edge arithmetic with chunk head room
-  const int io = dtype == E3_BF16 ? 1 : 0;
-  const int li = lmax == 2 ? 1 : 0;
-#if WS_LMAX1
-  const void* kern =
-      pb == kCell
-          ? (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, kCell> : (const void*)msg_ws_kernel<2, 2, false, kCell>)
-                : (io ? (const void*)msg_ws_kernel<1, 2, true, kCell> : (const void*)msg_ws_kernel<1, 2, false, kCell>))
-      : pb ? (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, kBox> : (const void*)msg_ws_kernel<2, 2, false, kBox>)
-                 : (io ? (const void*)msg_ws_kernel<1, 2, true, kBox> : (const void*)msg_ws_kernel<1, 2, false, kBox>))
-           : (li ? (io ? (const void*)msg_ws_kernel<2, 2, true, kOpen> : (const void*)msg_ws_kernel<2, 2, false, kOpen>)
-                 : (io ? (const void*)msg_ws_kernel<1, 2, true, kOpen> : (const void*)msg_ws_kernel<1, 2, false, kOpen>));
-  const int lds = li ? (io ? Ws<2, 2, true>::total : Ws<2, 2, false>::total) : (io ? Ws<1, 2, true>::total : Ws<1, 2, false>::total);
-  const int ud = li ? MsgGeom<2, 2>::UD : MsgGeom<1, 2>::UD;
-#else
-  const void* kern =
-      pb == kCell ? (io ? (const void*)msg_ws_kernel<2, 2, true, kCell> : (const void*)msg_ws_kernel<2, 2, false, kCell>)
-      : pb        ? (io ? (const void*)msg_ws_kernel<2, 2, true, kBox> : (const void*)msg_ws_kernel<2, 2, false, kBox>)
-                  : (io ? (const void*)msg_ws_kernel<2, 2, true, kOpen> : (const void*)msg_ws_kernel<2, 2, false, kOpen>);
+int msg_ws_launch(const e3_msg_plan& P, const MsgOperands& a, const MsgPbc& pbc, const MsgWsOwned* owned) {
+  if (!msg_ws_supported(P.lmax, P.H, a.dtype)) return E3_ERR_UNSUPPORTED;
+  if (owned && owned->part && (!owned->part_node || !owned->amax)) return E3_ERR_INVALID_ARG;
+  if (a.E > 0x7fffffffLL - 65536) return E3_ERR_UNSUPPORTED;  // 32-bit edge arithmetic with chunk head room
+  const int io = a.dtype == E3_BF16 ? 1 : 0;
+  static const void* const kernels[3][2] = {  // [PbcMode][0 fp32 / 1 bf16 storage]
+      {(const void*)msg_ws_kernel<2, 2, false, kOpen>, (const void*)msg_ws_kernel<2, 2, true, kOpen>},
+      {(const void*)msg_ws_kernel<2, 2, false, kBox>, (const void*)msg_ws_kernel<2, 2, true, kBox>},
+      {(const void*)msg_ws_kernel<2, 2, false, kCell>, (const void*)msg_ws_kernel<2, 2, true, kCell>}};
+  const void* kern = kernels[pbc.mode][io];
   const int lds = io ? Ws<2, 2, true>::total : Ws<2, 2, false>::total;
-  const int ud = MsgGeom<2, 2>::UD;
-#endif
   int dev = 0;
   E3_HIP_CHECK(hipGetDevice(&dev));
   static std::mutex mu;
-  static int cus_of[64][2][2][3];
+  static int cus_of[64][2][3];
   int cus = 0;
   {
     std::lock_guard<std::mutex> lock(mu);
     if (dev < 0 || dev >= 64) return E3_ERR_INVALID_ARG;
-    if (cus_of[dev][io][li][pb] == 0) {  // once per device, storage type and box kind: the kernel needs its LDS image admitted
+    if (cus_of[dev][io][pbc.mode] == 0) {  // once per device, storage type and box kind: the kernel needs its LDS image admitted
       E3_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       int n = 0;
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      cus_of[dev][io][li][pb] = n;
+      cus_of[dev][io][pbc.mode] = n;
     }
-    cus = cus_of[dev][io][li][pb];
+    cus = cus_of[dev][io][pbc.mode];
   }
-  const int chunk = msg_ws_chunk_edges(chunk_edges);
-  const int64_t nchunks = (E + chunk - 1) / chunk;
+  const int chunk = msg_ws_chunk_edges(a.tiles_per_block);
+  const int64_t nchunks = (a.E + chunk - 1) / chunk;
   int nwg = (int)std::min<int64_t>(cus, nchunks);  // one workgroup of 8 waves per CU
   nwg = std::max(8, (nwg + 7) / 8 * 8);
   // behind the table: the pre-split rows (gathered by the fp32 kernel) and the per-node row maxima (e3_msg_premix)
-  const MsgPremixLayout lay = msg_premix_layout(ud, msg_ws_split_floats(lmax, hidden), N);
-  const float* split = premix + lay.split;
-  const float* hmax = premix + lay.hmax;
+  const MsgPremixLayout lay = msg_premix_layout(MsgGeom<2, 2>::UD, msg_ws_split_floats(P.lmax, P.H), a.N);
+  const float* split = a.premix + lay.split;
+  const float* hmax = a.premix + lay.hmax;
+  const MsgWsOwned own = owned ? *owned : MsgWsOwned{nullptr, nullptr, nullptr};
   // the argument block of the mode: the box / cell sits behind the common fields (kernel-argument segment: SGPRs)
-  auto launch = [&](const auto& pbc) {
-    WsArgsT<std::decay_t<decltype(pbc)>> a = {h, ldh, reinterpret_cast<const float4*>(pos4), src, dst, E,
-                                              static_cast<const float*>(packed), premix, split, hmax, in_scale, out, ldo, chunk,
-                                              part, part_node, amax, (int)(msg_ws_owned_chunks(E, chunk_edges) / 8), pbc};
-    void* args[] = {&a};
-    return hipLaunchKernel(kern, dim3(nwg), dim3(512), args, lds, stream) == hipSuccess ? E3_OK : E3_ERR_HIP;
+  auto launch = [&](const auto& box) {
+    WsArgsT<std::decay_t<decltype(box)>> args = {
+        a.h, a.ld_h, reinterpret_cast<const float4*>(a.pos4), a.src, a.dst, a.E, static_cast<const float*>(a.packed), a.premix,
+        split, hmax, a.in_scale, a.out, a.ld_out, chunk, own.part, own.part_node, own.amax,
+        (int)(msg_ws_owned_chunks(a.E, a.tiles_per_block) / 8), box};
+    void* argv[] = {&args};
+    return hipLaunchKernel(kern, dim3(nwg), dim3(512), argv, lds, a.stream) == hipSuccess ? E3_OK : E3_ERR_HIP;
   };
-  return cell ? launch(*cell) : launch(make_box(box));
+  return pbc.mode == kCell ? launch(pbc.cell) : launch(pbc.box);
 }
 
 }  // namespace e3

@@ -1,5 +1,5 @@
 // Device-side building blocks shared by the MFMA tensor-product kernels (e3_tp_mfma_r16.hip: one TP per launch;
-// e3_msg_fused.hip: the whole message function per launch).  Internal header, included inside namespace e3.
+// e3_msg_ws.hip, e3_msg_fused_kernel.h: the whole message function per launch).  Internal header, included inside namespace e3.
 #pragma once
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void glb_void_t;

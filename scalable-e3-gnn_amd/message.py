@@ -1,4 +1,5 @@
-"""Host side of the fused SEGNN message function (``e3_msg_*`` in include/e3gnn.h; kernel: csrc/e3_msg_fused.hip).
+"""Host side of the fused SEGNN message function (``e3_msg_*`` in include/e3gnn.h; kernels: csrc/e3_msg_ws.hip and
+csrc/e3_msg_fused_kernel.h, entries: csrc/e3_msg_forward.hip, e3_msg_pack.hip, e3_msg_premix.hip).
 
     a_i = sum_{e -> i} gate(TP_m2(gate(TP_m1([h_dst | h_src | d_e]; Y_e)); Y_e))
 
