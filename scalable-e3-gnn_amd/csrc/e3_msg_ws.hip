@@ -36,7 +36,8 @@
 //
 // Product #1 -> product #2 without a message buffer: the gated output of product #1 sits in accumulator layout, which IS the
 // B-operand layout of product #2 (k order permuted at pack time), so each wave stores its own 8-byte half of every fragment
-// lane.  The fp16 (hi, lo) split needs one power-of-two scale per edge row that ALL four waves agree on without talking:
+// lane.  The fp16 (hi, lo) split needs one power-of-two scale per edge row that ALL four waves agree on without talking (the
+// table's wave forms it in phase X and the four read it):
 // it is derived from a rigorous bound, |message| <= Bw * max(|h[src]|, |h[dst]|, d) with Bw from the weights (pack time,
 // header[6]) and the per-node row maxima the pre-mix launch leaves behind its table.  The pair (hi, lo) keeps an absolute
 // error of 2^-25 of the scaled range, so a bound that is loose by many binades costs nothing (e3_tp_mfma_core.h: split2_f16).
@@ -63,8 +64,12 @@ namespace e3 {
 __device__ unsigned long long g_ws_stamps[8][4];
 __device__ unsigned long long g_ws_tp[8][8];   // per wave: cycles to the marks inside the tensor product
 #define WS_TPMARK(i) { if (tpm) { const uint32_t t_ = (uint32_t)__builtin_readcyclecounter(); tpm[i] += t_ - tpm0; tpm0 = t_; } }
+// The cycle counter does not hold pure arithmetic in place: hipcc moves MFMAs and folds across a mark.  An empty asm on the
+// accumulators a mark is meant to close keeps them on its near side (stamped builds only).
+#define WS_TPPIN(v) asm volatile("" : "+v"(v));
 #else
 #define WS_TPMARK(i)
+#define WS_TPPIN(v)
 #endif
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -530,8 +535,13 @@ struct TpRun {
   }
 
   // One scheduling region per item: the requests of item I + kWsPF, the products of item I and -- at the first item of a
-  // degree -- the fold of the PREVIOUS degree (vector work that depends only on finished products: it fills the issue slots
-  // between this degree's MFMAs).
+  // degree -- the fold of the PREVIOUS degree (vector work that depends only on finished products).  hipcc emits most of a fold
+  // between the MFMAs of the items that follow (tools/mfma_overlap.py, profiles/foldoverlap_isa.txt: 70 - 80 of a role's 86 -
+  // 106 fold fma inside its MFMA run) -- PROVIDED no branch stands between the product and the first use of accV: with the row
+  // scale's branch (pow2_scale_from_bits) in the epilogue of product #1 every fold sank behind it (2 inside the run); the row
+  // scale is formed in phase X for that reason.  Folds between the MFMAs are not free: a product wave is bound by its own
+  // in-order issue (~ 235 instructions at 8 - 9 cycles beside its partner wave; the MFMAs need <= 864 pipe cycles), so the run
+  // grows by what the folds took behind it (profiles/foldoverlap_phase_cycles.txt).
   template <int I>
   __device__ __forceinline__ void step() {
     request<I + kWsPF>();
@@ -540,7 +550,17 @@ struct TpRun {
     if constexpr (IT::first(I) && IT::l1(I) < LMAX) fold<IT::l1(I) + 1>();
     if constexpr (I + 1 < IT::N && IT::first(I + 1)) { WS_TPMARK(1 + LMAX - IT::l1(I)) }
     if constexpr (I + 1 < IT::N) step<I + 1>();
-    else { WS_TPMARK(1 + LMAX) fold<0>(); WS_TPMARK(2 + LMAX) }
+    else { pin_products(); WS_TPMARK(1 + LMAX) fold<0>(); pin_folds(); WS_TPMARK(2 + LMAX) }
+  }
+  // stamped builds: the mark behind the last item closes the MFMA run (the products of degree 0 and the scalar-type tiles have
+  // been issued, the folds are free), the last mark closes every fold: [.. | last degree | folds behind the MFMA run]
+  __device__ __forceinline__ void pin_products() {
+    if constexpr (LV > 0) { WS_TPPIN(uV[0][LV][0]) }
+    WS_TPPIN(accG) WS_TPPIN(accS)
+  }
+  __device__ __forceinline__ void pin_folds() {
+#pragma unroll
+    for (int c = 0; c < 2 * LV + 1; ++c) { WS_TPPIN(accV[c]) }
   }
 
   __device__ __forceinline__ void run() {
@@ -606,7 +626,8 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
   constexpr bool TEAM1 = W >= 4;
   constexpr int ROLE = W & 3;
   // service job of a team-0 wave in phase X: 0 / 1 conversion of rows 0-7 / 8-15 (+ initial values; fp32 storage: 0 the
-  // feature-first operands, 1 initial values), 2 initial values + edge table, 3 the tile cutter.  Rotated against the product
+  // feature-first operands, 1 initial values), 2 initial values + edge table (fp32 storage: + the row scales of product #1's
+  // messages), 3 the tile cutter.  Rotated against the product
   // roles (kWsXrot) so that the two conversion waves -- the longest, vector-heavy jobs -- share their SIMDs with the lighter roles of product #2 (l3 = 1 tiles: waves 6, 7), not with the
   // l3 = 2 roles (waves 4, 5), which are the longest of phase X
   constexpr int SX = TEAM1 ? -1 : ((W + kWsXrot) & 3);
@@ -994,6 +1015,14 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
         float y[9], dist;
         if constexpr (LMAX == 2) edge_sh<PBC>(ps, pd, y, dist, A.box); else edge_sh1<PBC>(ps, pd, y, dist, A.box);
         const float dsc = dist * xs;
+        // (wave 2) row scale of the fp16 split of product #1's messages: bound of the row's messages -> [2^12, 2^13).  It depends on
+        // the row's inputs only, all of them present here, so it is formed once per tile and not by each of the four product waves
+        // in phase Y (their longest phase); team 1 reads the same ring entry in phase X of the next step
+        if constexpr (SX == 2 && !IO16) {
+          const float* hm = reinterpret_cast<const float*>(smem + L::o_hmx + (s & 1) * 128);
+          const float srow = pow2_scale_from_bits(__builtin_bit_cast(uint32_t, bwx * fmaxf(fmaxf(hm[j], hm[16 + j]), dsc)), 12);
+          if (lane < 16) reinterpret_cast<float*>(smem + L::o_srow)[(s & 1) * 16 + lane] = srow;
+        }
         float z110[3][1], z220[5][1];
         make_z<1, 1, 0>(y, z110);
         if constexpr (LMAX == 2) make_z<2, 2, 0>(y, z220);
@@ -1132,8 +1161,9 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
       if (t0.n > 0) {
         float y[10];
         const float* ztr = reinterpret_cast<const float*>(smem + L::o_zt + (s & 1) * 16 * L::ZT * 4) + j * L::ZT;
-        const float* hm = reinterpret_cast<const float*>(smem + L::o_hmx + (s & 1) * 128);
-        const float hs = hm[j], hd = hm[16 + j];
+        // row scale of the fp16 split (phase X, the table's wave): one read, requested with the first operands
+        float srow = 1.0f;
+        if constexpr (!IO16) srow = reinterpret_cast<const float*>(smem + L::o_srow)[(s & 1) * 16 + j];
         const int slot = (j >= t0.n0 && j < t0.n) ? t0.sl1 : t0.sl0;
         const float* urow = reinterpret_cast<const float*>(smem + L::o_u + slot * L::U_ROW) + 4 * g;
         f32x4 accV[5], accG, accS;
@@ -1144,11 +1174,6 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
                                           L::PRE ? img : nullptr, lane, ztr, urow, wdtab + 4 * g,
                                           reinterpret_cast<const f32x4*>(smem + L::o_init) + lane, accV, accG, accS, y, tpmk);
         WS_PM0
-        const float dsc = y[9];
-        // row scale of the fp16 split: bound of the row's messages -> [2^12, 2^13)  (identical in the four waves: it depends
-        // on the row's inputs only)
-        float srow = 1.0f;
-        if constexpr (!IO16) srow = pow2_scale_from_bits(__builtin_bit_cast(uint32_t, bwx * fmaxf(fmaxf(hs, hd), dsc)), 12);
         [[maybe_unused]] const f32x4* nt = reinterpret_cast<const f32x4*>(n1tab) + g;  // (see phase X; the norms carry 1 / (sw1 xs))
         // this wave's half (tile t: k slots 4 t .. 4 t + 3) of every fragment lane: 8 bytes hi, 8 bytes lo
         unsigned char* b2 = smem + L::o_b2 + lane * 16 + 8 * O::t;
@@ -1195,9 +1220,6 @@ __device__ __forceinline__ void ws_run(const WsArgsT<typename PbcArg<PBC>::type>
           }
           const float fs[4] = {fsv[0], fsv[1], fsv[2], fsv[3]};
           put4(L::frag_ff(O::LV), fs);  // feature-first operand of product #2: f[k] = sum_c z[c] m[k][c]
-        }
-        if constexpr (ROLE == 3 && !IO16) {
-          if (lane < 16) reinterpret_cast<float*>(smem + L::o_srow)[(s & 1) * 16 + lane] = srow;
         }
       }
       if constexpr (SX == 3) ws_wait_vm0();  // the cutter's copies of phase X have landed before the barrier that publishes them

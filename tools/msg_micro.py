@@ -67,7 +67,7 @@ for tpb in [int(v) for v in os.environ.get("TPB", "0").split(",")]:
         for w in range(8):
             v = [buf[4 * w + i] / nwg / steps for i in range(4)]
             print(f"   wave {w}: {v[0]:8.0f} {v[1]:8.0f} {v[2]:8.0f} {v[3]:8.0f}   sum {sum(v):8.0f}")
-        print("   tensor product marks, cycles per tile: [first requests | degree 2 | degree 1 (+fold 2) | degree 0 (+fold 1) | fold 0]  (rest of the phase = gate + stores)")
+        print("   tensor product marks, cycles per tile: [first requests | degree 2 | degree 1 | degree 0: end of the MFMA run | folds behind the MFMA run]  (folds emitted between the MFMAs count with their degree; rest of the phase = gate + stores)")
         for w in range(8):
             v = [buf[32 + 8 * w + i] / nwg / steps for i in range(8)]
             print(f"   wave {w}: " + " ".join(f"{x:7.0f}" for x in v[:5]) + f"   sum {sum(v[:5]):7.0f}   | before product {v[5]:6.0f}"
