@@ -247,6 +247,11 @@ def check(status: int, what: str = ""):
         raise RuntimeError(f"libe3gnn_hip: {what}: {msg} (status {status})")
 
 
+def call(name: str, *args):
+    """Call the entry ``name`` and check its status: a failure names the entry that was called."""
+    check(getattr(load(), name)(*args), name)
+
+
 def blocks_array(blocks):
     flat = [int(v) for b in blocks for v in b]
     return (c_int32 * len(flat))(*flat), len(blocks)
@@ -317,3 +322,40 @@ class DevicePlans:
             self._handles = {}
         except Exception:
             pass
+
+
+class PackedCache:
+    """Packed weight images of one operator, one slot per ``(dtype, device)``.  A slot is rebuilt when the
+    ``(data_ptr, _version)`` of one of the tensors it was packed from changes: a replaced tensor and in-place operations
+    (``mul_``, ``copy_``, an optimizer step, ``load_state_dict``) are seen; writes through ``.data`` do not advance
+    ``_version`` and need ``invalidate()``.  A stream other than the one that packed waits for the pack's event.
+    Copies and pickles as an empty cache (an event cannot be copied, and two owners never share a buffer)."""
+
+    def __init__(self):
+        self._slots = {}
+
+    def get(self, tensors, dtype, device, pack):
+        """``pack(stream)`` checks the tensors, launches the pack on ``stream`` (the raw handle of the current stream of
+        ``device``) and returns the buffer; it runs only when the slot is missing or stale."""
+        import torch
+        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors)
+        stream = torch.cuda.current_stream(device)
+        hit = self._slots.get((dtype, device))
+        if hit is not None and hit[0] == key:
+            if hit[2] != stream.cuda_stream:
+                stream.wait_event(hit[3])  # packed on another stream: order this stream behind the pack kernels
+            return hit[1]
+        packed = pack(stream.cuda_stream)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._slots[(dtype, device)] = (key, packed, stream.cuda_stream, ev)
+        return packed
+
+    def invalidate(self):
+        self._slots = {}
+
+    def __deepcopy__(self, memo):
+        return PackedCache()
+
+    def __reduce__(self):
+        return (PackedCache, ())

@@ -152,8 +152,7 @@ class L1TensorProduct(Module):
 
         self._plan = None
         self._tpplan = None
-        self._packed = None
-        self._packed_key = None
+        self._packed = _lib.PackedCache()
         self.kernel = 0  # 0 auto, 1 generic, 2 MFMA (see e3_l1tp_forward)
 
         self.is_norm = irrep_normalization in ("component", "norm") or path_normalization in ("element", "path")
@@ -226,31 +225,23 @@ class L1TensorProduct(Module):
     def _packed_weights(self, dtype, device) -> Tensor:
         """Packed weight buffer for the kernels; rebuilt when any parameter/buffer changed."""
         ws, ns = self._weights(), self._norms()
-        key = (dtype, device) + tuple((t.data_ptr(), t._version) if t is not None else None for t in ws + ns)
-        stream = torch.cuda.current_stream(device)
-        if self._packed is not None and self._packed_key == key:
-            # packed on another stream: this stream waits for that pack launch (same rule as message.py / tensor_product.py)
-            if self._packed_stream != stream.cuda_stream:
-                stream.wait_event(self._packed_event)
-            return self._packed
-        lib = _lib.load()
-        code = _lib.dtype_code(dtype)
-        for t in ws + ns:
-            if t is not None and t.numel() > 0 and (t.dtype != dtype or t.device != device):
-                raise RuntimeError(
-                    f"L1TensorProduct: parameter/buffer dtype/device {t.dtype}/{t.device} does not match "
-                    f"input {dtype}/{device} (cast the module, autocast is not supported — as in the reference)")
-        plan = self._get_plan()
-        nbytes = lib.e3_l1tp_packed_bytes(plan.handle(device), code)
-        packed = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-        wsc = [w.detach().contiguous() if w is not None else None for w in ws]
-        nsc = [n.detach().contiguous() if n is not None else None for n in ns]
-        _lib.check(lib.e3_l1tp_pack_weights(plan.handle(device), _lib.ptr4(wsc), _lib.ptr4(nsc), code,
-                                            packed.data_ptr(), stream.cuda_stream), "e3_l1tp_pack_weights")
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        self._packed, self._packed_key, self._packed_stream, self._packed_event = packed, key, stream.cuda_stream, ev
-        return packed
+
+        def pack(stream):
+            lib = _lib.load()
+            code = _lib.dtype_code(dtype)
+            for t in ws + ns:
+                if t is not None and t.numel() > 0 and (t.dtype != dtype or t.device != device):
+                    raise RuntimeError(
+                        f"L1TensorProduct: parameter/buffer dtype/device {t.dtype}/{t.device} does not match "
+                        f"input {dtype}/{device} (cast the module, autocast is not supported — as in the reference)")
+            h = self._get_plan().handle(device)
+            packed = torch.empty(max(int(lib.e3_l1tp_packed_bytes(h, code)), 16), dtype=torch.uint8, device=device)
+            wsc = [w.detach().contiguous() if w is not None else None for w in ws]
+            nsc = [n.detach().contiguous() if n is not None else None for n in ns]
+            _lib.call("e3_l1tp_pack_weights", h, _lib.ptr4(wsc), _lib.ptr4(nsc), code, packed.data_ptr(), stream)
+            return packed
+
+        return self._packed.get(ws + ns, dtype, device, pack)
 
     def _hip_forward(self, in1: Tensor, in2: Tensor) -> Tensor:
         lib = _lib.load()
@@ -307,26 +298,12 @@ class L1TensorProduct(Module):
             # transposed (and the cross-product block negated) -- one launch of the MFMA forward kernel, nothing of size
             # [B, D3, K] in HBM.  grad_W still comes from the operand pass + one batched GEMM per class.
             g1 = self._dual_forward(ws, ns, in1, in2, grad_out)
-            gws = [None] * 6
             if need_w:
-                tpp = self._fused_plan()
-                ws6, ns6 = list(ws) + [None, None], list(ns) + [None, None]
-                with torch.cuda.device(device):
-                    packed = tpp.packed(ws6, ns6, dtype, device)
-                _, _, gws = _tp.tp_backward(tpp, packed, in1, in2, grad_out, ws6, False, False,
-                                            [w is not None for w in ws6])
-            return (g1, None, {c: (gws[i].to(ws[i].dtype) if gws[i] is not None else None) for i, c in enumerate(_CLS)})
+                g_w = self._general_backward(ws, ns, in1, in2, grad_out, False, False, True)[2]
+            return g1, None, g_w
         if B >= _tp._BWD_GEMM_MIN_ROWS and dtype in (torch.float32, torch.float64):
-            # large B: operands -> library GEMMs -> contract on the general plan (this operator is its lmax_sh = 1 case:
-            # same class order, weight-row order and norms, see forward_fused)
-            tpp = self._fused_plan()
-            ws6, ns6 = list(ws) + [None, None], list(ns) + [None, None]
-            with torch.cuda.device(device):
-                packed = tpp.packed(ws6, ns6, dtype, device)
-            g1, g2, gws = _tp.tp_backward(tpp, packed, in1, in2, grad_out, ws6, need_in1, need_in2,
-                                          [need_w and w is not None for w in ws6])
-            return (g1, g2.to(in2.dtype) if g2 is not None else None,
-                    {c: (gws[i].to(ws[i].dtype) if gws[i] is not None else None) for i, c in enumerate(_CLS)})
+            # large B: operands -> library GEMMs -> contract
+            return self._general_backward(ws, ns, in1, in2, grad_out, need_in1, need_in2, need_w)
         with torch.cuda.device(device):
             plan = self._get_plan()
             wbytes = lib.e3_l1tp_backward_workspace_bytes(plan.handle(device), B, code)
@@ -341,6 +318,19 @@ class L1TensorProduct(Module):
                 g_in2.data_ptr() if g_in2 is not None else None,
                 _lib.ptr4([g_w[c] for c in _CLS]), work.data_ptr(), B, code, stream), "e3_l1tp_backward")
         return g_in1, g_in2, g_w
+
+    def _general_backward(self, ws, ns, in1, in2, grad_out, need_in1, need_in2, need_w):
+        """``tp_backward`` on the general plan (this operator is its lmax_sh = 1 case: same class order, weight-row order
+        and norms, see forward_fused) -> (grad_in1 | None, grad_in2 | None, {class: grad_W | None})."""
+        from . import tensor_product as _tp
+        tpp = self._fused_plan()
+        ws6, ns6 = list(ws) + [None, None], list(ns) + [None, None]
+        with torch.cuda.device(in1.device):
+            packed = tpp.packed(ws6, ns6, in1.dtype, in1.device)
+        g1, g2, gws = _tp.tp_backward(tpp, packed, in1, in2, grad_out, ws6, need_in1, need_in2,
+                                      [need_w and w is not None for w in ws6])
+        return (g1, g2.to(in2.dtype) if g2 is not None else None,
+                {c: (gws[i].to(ws[i].dtype) if gws[i] is not None else None) for i, c in enumerate(_CLS)})
 
     def _dual_forward(self, ws, ns, in1, in2, grad_out):
         """grad_in1 of the forward as a forward of the dual operator (irreps swapped, lmax 1).  Weight rows of the forward

@@ -25,7 +25,7 @@ class FusedMessage:
     def __init__(self, lmax: int, hidden: int):
         self.lmax, self.hidden = int(lmax), int(hidden)
         self._plans = _lib.DevicePlans("e3_msg_plan_create", "e3_msg_plan_destroy", self.lmax, self.hidden)
-        self._packed = {}
+        self._packed = _lib.PackedCache()
         self.tiles_per_block = 0  # 0 = library default
         # non-accumulating launches of the weights-stationary kernel write every row of the sums exactly once (plain stores
         # + a merge of the chunk-boundary rows: no zero-fill, no atomics, reproducible) and return the operand scale of the
@@ -62,42 +62,35 @@ class FusedMessage:
         ``copy_``, an optimizer step, ``load_state_dict``) and a replaced tensor are seen.  Writes through ``.data`` (or any
         other alias with a version counter of its own) do NOT advance ``_version`` and are not picked up: the stale image
         is used until another change is seen."""
-        lib = _lib.load()
         w1, n1 = self._tensors(msg1)
         w2, n2 = self._tensors(msg2)
         ts = w1 + n1 + w2 + n2
-        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in ts)
-        hit = self._packed.get((device, dtype))
-        stream = torch.cuda.current_stream(device)
-        if hit is not None and hit[0] == key:
-            if hit[2] != stream.cuda_stream:
-                stream.wait_event(hit[3])
-            return hit[1]
-        h = self._plans.handle(device)
-        for tpi, ws in ((1, w1), (2, w2)):
-            for l in range(self.lmax + 1):
-                rows, cols = ctypes.c_int(), ctypes.c_int()
-                lib.e3_msg_weight_shape(h, tpi, l, ctypes.byref(rows), ctypes.byref(cols))
-                w = ws[l]
-                if w is None or tuple(w.shape) != (rows.value, cols.value) or w.dtype != dtype or w.device != device:
-                    raise RuntimeError(f"fused message: TP #{tpi} weights of degree {l} must be {dtype} "
-                                       f"[{rows.value}, {cols.value}] on {device}, got "
-                                       f"{None if w is None else (tuple(w.shape), w.dtype, w.device)}")
-        P3 = ctypes.c_void_p * 3
-        keep = [t.detach().contiguous() if t is not None else None for t in ts]
-        ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None
-        packed = torch.empty(int(lib.e3_msg_packed_bytes(h)), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            for t in keep[3:6] + keep[9:12]:
-                if t is not None and t.numel() and t.dtype != dtype:
-                    raise RuntimeError(f"fused message: norm buffers must be {dtype} (cast the module), got {t.dtype}")
-            _lib.check(lib.e3_msg_pack_weights(h, P3(*map(ptr, keep[0:3])), P3(*map(ptr, keep[3:6])),
-                                               P3(*map(ptr, keep[6:9])), P3(*map(ptr, keep[9:12])), _lib.dtype_code(dtype),
-                                               packed.data_ptr(), stream.cuda_stream), "e3_msg_pack_weights")
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        self._packed[(device, dtype)] = (key, packed, stream.cuda_stream, ev)
-        return packed
+
+        def pack(stream):
+            lib = _lib.load()
+            h = self._plans.handle(device)
+            for tpi, ws in ((1, w1), (2, w2)):
+                for l in range(self.lmax + 1):
+                    rows, cols = ctypes.c_int(), ctypes.c_int()
+                    lib.e3_msg_weight_shape(h, tpi, l, ctypes.byref(rows), ctypes.byref(cols))
+                    w = ws[l]
+                    if w is None or tuple(w.shape) != (rows.value, cols.value) or w.dtype != dtype or w.device != device:
+                        raise RuntimeError(f"fused message: TP #{tpi} weights of degree {l} must be {dtype} "
+                                           f"[{rows.value}, {cols.value}] on {device}, got "
+                                           f"{None if w is None else (tuple(w.shape), w.dtype, w.device)}")
+            P3 = ctypes.c_void_p * 3
+            keep = [t.detach().contiguous() if t is not None else None for t in ts]
+            ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None
+            packed = torch.empty(int(lib.e3_msg_packed_bytes(h)), dtype=torch.uint8, device=device)
+            with torch.cuda.device(device):
+                for t in keep[3:6] + keep[9:12]:
+                    if t is not None and t.numel() and t.dtype != dtype:
+                        raise RuntimeError(f"fused message: norm buffers must be {dtype} (cast the module), got {t.dtype}")
+                _lib.call("e3_msg_pack_weights", h, P3(*map(ptr, keep[0:3])), P3(*map(ptr, keep[3:6])),
+                          P3(*map(ptr, keep[6:9])), P3(*map(ptr, keep[9:12])), _lib.dtype_code(dtype), packed.data_ptr(), stream)
+            return packed
+
+        return self._packed.get(ts, dtype, device, pack)
 
     def flops_per_edge(self) -> int:
         """Algorithmic flops of the two message products per edge: sum over paths of 2 K M min(2 l1+1, 2 l3+1)."""
@@ -237,18 +230,10 @@ class FusedMessage:
                 work = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
                 out_scale = torch.empty(4, dtype=torch.float32, device=dev)
                 args = args[:14] + (int(self.tiles_per_block), work.data_ptr(), wsb, out_scale.data_ptr(), 10)
-                if g.cell is not None:
-                    _lib.check(lib.e3_msg_forward_owned_cell(*args, g.cell_arg, stream), "e3_msg_forward_owned_cell")
-                elif g.box is not None:
-                    _lib.check(lib.e3_msg_forward_owned_pbc(*args, g.box_arg, stream), "e3_msg_forward_owned_pbc")
-                else:
-                    _lib.check(lib.e3_msg_forward_owned(*args, stream), "e3_msg_forward_owned")
-            elif g.cell is not None:  # general cell: harmonics of the minimum image by lattice vectors
-                _lib.check(lib.e3_msg_forward_cell(*args, g.cell_arg, stream), "e3_msg_forward_cell")
-            elif g.box is not None:  # periodic box: harmonics of the minimum-image edge vectors
-                _lib.check(lib.e3_msg_forward_pbc(*args, g.box_arg, stream), "e3_msg_forward_pbc")
+                name, pbc = g.entry("e3_msg_forward_owned")
             else:
-                _lib.check(lib.e3_msg_forward(*args, stream), "e3_msg_forward")
+                name, pbc = g.entry("e3_msg_forward")
+            _lib.call(name, *args, *pbc, stream)  # periodic box / general cell: harmonics of the minimum-image edge vectors
             if t0 is not None:
                 # algorithmic bytes: h read once, positions, the two index columns, aggregated rows written once
                 nb = esz * N * W + 16 * N + 8 * E + 4 * N * W

@@ -155,7 +155,6 @@ class NeighborList:
         """The stored graph cut down to r at ``pos`` -> (RadiusGraph, max_i d2_i as a float; nan for a non-finite one)."""
         g = self._g
         N, E, dev = pos.shape[0], g.num_edges, pos.device
-        lib = _lib.load()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             pos4 = torch.empty((N, 4), dtype=torch.float32, device=dev)
@@ -165,12 +164,8 @@ class NeighborList:
             head = (pos.data_ptr(), g.perm.data_ptr(), g.pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, E, self.r)
             tail = (pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(), dst.data_ptr(), self._stats.data_ptr(),
                     self._ws.data_ptr(), stream)
-            if g.cell is not None:
-                _lib.check(lib.e3_nl_update_cell(*head, g.cell_arg, *tail), "e3_nl_update_cell")
-            elif g.box is not None:
-                _lib.check(lib.e3_nl_update_pbc(*head, g.box_arg, *tail), "e3_nl_update_pbc")
-            else:
-                _lib.check(lib.e3_nl_update(*head, *tail), "e3_nl_update")
+            name, pbc = g.entry("e3_nl_update")
+            _lib.call(name, *head, *pbc, *tail)
             bits, kept = self._stats.tolist()  # the one host read of an update
         maxd2 = struct.unpack("<f", struct.pack("<I", bits & 0xffffffff))[0]
         out = RadiusGraph(g.perm, pos4, rowptr, src[:kept], kept, g.grid, g.box, g.cell, g.origin, g.volume)

@@ -35,29 +35,18 @@ def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True,
         if A is not None:
             A.zero_()[:, 0] = 1.0
         return Y, d, A
-    fn = {1: "e3_edge_geometry", 2: "e3_edge_geometry_l2"}[lmax]
+    head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N)
     outs = (Y.data_ptr() if Y is not None else None, d.data_ptr() if d is not None else None,
             A.data_ptr() if A is not None else None, _stream(pos4))
     with torch.cuda.device(dev):
-        if strain is not None and g.cell is not None:  # general cell: the cell's minimum image, then the strain
-            _lib.check(_lib.load().e3_edge_geometry_strained_cell(
-                pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, g.cell_arg, strain.data_ptr(),
-                structure.data_ptr() if structure is not None else None, strain.shape[0], *outs),
-                "e3_edge_geometry_strained_cell")
-        elif strain is not None:  # [S,3,3] contiguous fp32, structure [N] int32 | None (checked by _strain_args)
-            _lib.check(_lib.load().e3_edge_geometry_strained(
-                pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, g.box_arg, strain.data_ptr(),
-                structure.data_ptr() if structure is not None else None, strain.shape[0], *outs),
-                "e3_edge_geometry_strained")
-        elif g.cell is not None:  # general cell: minimum-image edge vectors by lattice vectors
-            _lib.check(getattr(_lib.load(), fn + "_cell")(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
-                                                          g.cell_arg, *outs), fn + "_cell")
-        elif g.box is not None:  # periodic box: minimum-image edge vectors
-            _lib.check(getattr(_lib.load(), fn + "_pbc")(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N,
-                                                         g.box_arg, *outs), fn + "_pbc")
-        else:
-            _lib.check(getattr(_lib.load(), fn)(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, *outs),
-                       "e3_edge_geometry")
+        if strain is not None:  # [S,3,3] contiguous fp32, structure [N] int32 | None (checked by _strain_args): the
+            # minimum image of the box or cell first, then the strain
+            name, pbc = g.entry("e3_edge_geometry_strained", strained=True)
+            _lib.call(name, *head, lmax, *pbc, strain.data_ptr(), structure.data_ptr() if structure is not None else None,
+                      strain.shape[0], *outs)
+        else:  # periodic box / general cell: minimum-image edge vectors
+            name, pbc = g.entry({1: "e3_edge_geometry", 2: "e3_edge_geometry_l2"}[lmax])
+            _lib.call(name, *head, *pbc, *outs)
     return Y, d, A
 
 
@@ -109,29 +98,17 @@ class _EdgeGeometryFn(torch.autograd.Function):
         if g.num_edges == 0:  # no edge: the outputs do not depend on pos or strain
             return gpos.zero_(), (torch.zeros_like(strain) if strain is not None else None), None, None, None
         with torch.cuda.device(pos4.device):
-            lib = _lib.load()
+            head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax)
             if strain is not None:
                 gstrain = torch.empty_like(strain)
-                ws = torch.empty(max(1, lib.e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
+                ws = torch.empty(max(1, _lib.load().e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
                                  device=pos4.device)
-                name = "e3_edge_geometry_backward_strained" + ("_cell" if g.cell is not None else "")
-                _lib.check(getattr(lib, name)(
-                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax,
-                    g.cell_arg if g.cell is not None else g.box_arg, strain.data_ptr(),
-                    p(ctx.structure), strain.shape[0], p(gY), p(gd), p(gA), gpos.data_ptr(), gstrain.data_ptr(),
-                    ws.data_ptr(), ws.numel(), _stream(pos4)), name)
-            elif g.cell is not None:
-                _lib.check(lib.e3_edge_geometry_backward_cell(
-                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.cell_arg, p(gY), p(gd), p(gA),
-                    gpos.data_ptr(), _stream(pos4)), "e3_edge_geometry_backward_cell")
-            elif g.box is not None:
-                _lib.check(lib.e3_edge_geometry_backward_pbc(
-                    pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax, g.box_arg, p(gY), p(gd), p(gA),
-                    gpos.data_ptr(), _stream(pos4)), "e3_edge_geometry_backward_pbc")
+                name, pbc = g.entry("e3_edge_geometry_backward_strained", strained=True)
+                _lib.call(name, *head, *pbc, strain.data_ptr(), p(ctx.structure), strain.shape[0], p(gY), p(gd), p(gA),
+                          gpos.data_ptr(), gstrain.data_ptr(), ws.data_ptr(), ws.numel(), _stream(pos4))
             else:
-                _lib.check(lib.e3_edge_geometry_backward(pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(),
-                                                         N, ctx.lmax, p(gY), p(gd), p(gA), gpos.data_ptr(),
-                                                         _stream(pos4)), "e3_edge_geometry_backward")
+                name, pbc = g.entry("e3_edge_geometry_backward")
+                _lib.call(name, *head, *pbc, p(gY), p(gd), p(gA), gpos.data_ptr(), _stream(pos4))
         return gpos, gstrain, None, None, None
 
 

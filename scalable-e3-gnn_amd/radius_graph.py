@@ -51,6 +51,23 @@ class RadiusGraph:
         return None if self.box is None else _lib.Float3(*self.box)
 
     @property
+    def periodic(self) -> bool:
+        """Whether edge vectors are minimum images (a box with a periodic axis, or a cell)."""
+        return self.cell is not None or self.box is not None
+
+    def entry(self, name: str, strained: bool = False):
+        """The edge-stage entry of this graph's periodicity -> (``name`` + ``""`` | ``"_pbc"`` | ``"_cell"``, the host
+        arguments that entry takes for it: none, the box, or the cell).  The strained entries come in two forms only:
+        the un-suffixed one takes the box or NULL, ``_cell`` the cell."""
+        if self.cell is not None:
+            return name + "_cell", (self.cell_arg,)
+        if strained:
+            return name, (self.box_arg,)
+        if self.box is not None:
+            return name + "_pbc", (self.box_arg,)
+        return name, ()
+
+    @property
     def dst(self) -> torch.Tensor:
         """[E] int32 destination of every edge (expanded from rowptr once, then cached)."""
         d = getattr(self, "_dst", None)
@@ -174,32 +191,6 @@ def _edge_count(rowptr, N) -> int:
     return int(E)
 
 
-def _radius_graph_cell(pos, r, cell, origin) -> RadiusGraph:
-    c9, o3, hgt, vol = cell_params(cell, origin)
-    cell_check_cutoff(hgt, r)
-    pos = _check_pos(pos)
-    N, dev = pos.shape[0], pos.device
-    lib = _lib.load()
-    p = grid_params([0.0, 0.0, 0.0], hgt, r)  # the open grid of q = s * heights in [0, h)
-    ca, oa = _lib.Float9(*c9), _lib.Float3(*o3)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        wbytes = lib.e3_rg_workspace_bytes(N, ctypes.byref(p))
-        if wbytes < 0:
-            raise RuntimeError("e3_rg_workspace_bytes: invalid arguments")
-        ws = torch.empty(max(int(wbytes), 16), dtype=torch.uint8, device=dev)
-        perm = torch.empty(N, dtype=torch.int32, device=dev)
-        pos4 = torch.empty((N, 4), dtype=torch.float32, device=dev)
-        rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        _lib.check(lib.e3_rg_sort_count_cell(pos.data_ptr(), N, ctypes.byref(p), ca, oa, perm.data_ptr(), pos4.data_ptr(),
-                                             rowptr.data_ptr(), ws.data_ptr(), wbytes, stream), "e3_rg_sort_count_cell")
-        E = _edge_count(rowptr, N)
-        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.e3_rg_fill_cell(N, ctypes.byref(p), ca, oa, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
-                                       ws.data_ptr(), wbytes, stream), "e3_rg_fill_cell")
-    return RadiusGraph(perm, pos4, rowptr, src[:E], E, (tuple(p.n), p.bits), None, c9, o3, vol)
-
-
 def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, cell=None, origin=None) -> RadiusGraph:
     """pos [N,3] fp32 on a ROCm device.  ``lo``/``hi``: bounding box (computed from pos when omitted).
 
@@ -213,20 +204,28 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, 
     if cell is not None:
         if lo is not None or hi is not None or not (periodic is False or periodic is None):
             raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
-        return _radius_graph_cell(pos, r, cell, origin)
-    if origin is not None:
-        raise ValueError("origin= is the corner of a cell=; it needs cell=")
-    mask = periodic_mask(periodic, r, lo, hi)
-    pos = _check_pos(pos)
-    N = pos.shape[0]
-    if lo is None or hi is None:
-        lo = pos.min(0).values.tolist() if N else [0.0, 0.0, 0.0]
-        hi = pos.max(0).values.tolist() if N else [1.0, 1.0, 1.0]
-        hi = [h if h > l else l + 1.0 for l, h in zip(lo, hi)]
+        c9, o3, hgt, vol = cell_params(cell, origin)
+        cell_check_cutoff(hgt, r)
+        pos = _check_pos(pos)
+        p = grid_params([0.0, 0.0, 0.0], hgt, r)  # the open grid of q = s * heights in [0, h)
+        suffix, extra = "_cell", (_lib.Float9(*c9), _lib.Float3(*o3))
+        fields = dict(cell=c9, origin=o3, volume=vol)
+    else:
+        if origin is not None:
+            raise ValueError("origin= is the corner of a cell=; it needs cell=")
+        mask = periodic_mask(periodic, r, lo, hi)
+        pos = _check_pos(pos)
+        if lo is None or hi is None:
+            lo = pos.min(0).values.tolist() if pos.shape[0] else [0.0, 0.0, 0.0]
+            hi = pos.max(0).values.tolist() if pos.shape[0] else [1.0, 1.0, 1.0]
+            hi = [h if h > l else l + 1.0 for l, h in zip(lo, hi)]
+        p = grid_params(lo, hi, r)
+        suffix, extra, fields = "", (), {}
+        if mask:
+            suffix, extra = "_pbc", (mask,)
+            fields = dict(box=tuple(ctypes.c_float(p.hi[a] - p.lo[a]).value if (mask >> a) & 1 else 0.0 for a in range(3)))
+    N, dev = pos.shape[0], pos.device
     lib = _lib.load()
-    p = grid_params(lo, hi, r)
-    box = tuple(ctypes.c_float(p.hi[a] - p.lo[a]).value if (mask >> a) & 1 else 0.0 for a in range(3)) if mask else None
-    dev = pos.device
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         wbytes = lib.e3_rg_workspace_bytes(N, ctypes.byref(p))
@@ -236,19 +235,10 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, 
         perm = torch.empty(N, dtype=torch.int32, device=dev)
         pos4 = torch.empty((N, 4), dtype=torch.float32, device=dev)
         rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        if mask:
-            _lib.check(lib.e3_rg_sort_count_pbc(pos.data_ptr(), N, ctypes.byref(p), mask, perm.data_ptr(),
-                                                pos4.data_ptr(), rowptr.data_ptr(), ws.data_ptr(), wbytes, stream),
-                       "e3_rg_sort_count_pbc")
-        else:
-            _lib.check(lib.e3_rg_sort_count(pos.data_ptr(), N, ctypes.byref(p), perm.data_ptr(), pos4.data_ptr(),
-                                            rowptr.data_ptr(), ws.data_ptr(), wbytes, stream), "e3_rg_sort_count")
+        _lib.call("e3_rg_sort_count" + suffix, pos.data_ptr(), N, ctypes.byref(p), *extra, perm.data_ptr(), pos4.data_ptr(),
+                  rowptr.data_ptr(), ws.data_ptr(), wbytes, stream)
         E = _edge_count(rowptr, N)
         src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        if mask:
-            _lib.check(lib.e3_rg_fill_pbc(N, ctypes.byref(p), mask, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
-                                          ws.data_ptr(), wbytes, stream), "e3_rg_fill_pbc")
-        else:
-            _lib.check(lib.e3_rg_fill(N, ctypes.byref(p), pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
-                                      ws.data_ptr(), wbytes, stream), "e3_rg_fill")
-    return RadiusGraph(perm, pos4, rowptr, src[:E], E, (tuple(p.n), p.bits), box)
+        _lib.call("e3_rg_fill" + suffix, N, ctypes.byref(p), *extra, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
+                  ws.data_ptr(), wbytes, stream)
+    return RadiusGraph(perm, pos4, rowptr, src[:E], E, (tuple(p.n), p.bits), **fields)

@@ -47,6 +47,8 @@ def _make_tp(in_irreps, out_irreps, lmax: int):
     return SHTensorProduct(in_irreps, out_irreps, lmax_sh=2)
 
 
+_PERIODIC_NOT_SHARDED = ("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the ghost images "
+                         "of GridHalo(..., periodic=...)")
 _ENVELOPE_NEEDS_BOTH = ("the cutoff envelope on the sharded path works on the split graph with a refresh per layer: halo= and "
                         "split= (halo.split_graph) come together; one without the other is not implemented")
 
@@ -91,6 +93,24 @@ class SEGNNLayer(nn.Module):
             f = self._fused_upd_ok = bool(self.upd1.fused_supported(True))
         return f
 
+    def paths(self, dtype, needs_grad: bool, weighted: bool = False):
+        """The kernels a call runs -> (message path, update path), from what ``forward`` can observe: the storage dtype,
+        whether a gradient is needed, whether edge weights ``w`` are given, and the three flags.
+
+        message: "one_launch" (``FusedMessage``: both products, both gates and the sums in one launch; it sums with weight
+        1, so not with ``w``), "per_product" (gather + TP + gate per product, needs an MFMA instantiation of both message
+        products and update #1) or "chain" (the differentiable chain on the generic kernels).
+        update: "fused" or "chain".  bf16 storage has the fused kernels only: a RuntimeError otherwise."""
+        fast = self.fused and not needs_grad
+        per_product = fast and self.fused_available()
+        one_launch = (fast and self.fuse_message and self.fuse_scatter and self._msg is not None and
+                      self._msg.supports(dtype) and not weighted)
+        fused_update = per_product or (one_launch and self.fused_update_available())
+        if dtype == torch.bfloat16 and not ((one_launch or per_product) and fused_update):
+            raise RuntimeError("bf16 storage needs the fused MFMA kernels (inference; hidden 32, or 64 at l_max = 2)")
+        return ("one_launch" if one_launch else "per_product" if per_product else "chain",
+                "fused" if fused_update else "chain")
+
     def forward(self, h, g: RadiusGraph, Y, d, A, h_scale=None, halo=None, split=None, w=None):
         """-> (h_next, operand scale of h_next | None).  ``halo`` / ``split`` (sharding.Halo / SplitGraph): the layer
         refreshes the ghost rows of ``h`` itself -- in place -- and overlaps the transfer with the interior edges; a call
@@ -106,11 +126,10 @@ class SEGNNLayer(nn.Module):
                 raise NotImplementedError(_ENVELOPE_NEEDS_BOTH)
             if h.dtype != torch.float32:
                 raise RuntimeError("the cutoff envelope is fp32: bf16 storage has no weighted aggregation")
-        if (halo is not None or split is not None) and (g.box is not None or g.cell is not None):
-            raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
-                                      "ghost images of GridHalo(..., periodic=...)")
-        inference = not (torch.is_grad_enabled() and _needs_grad(self, h))
-        if not inference and self.fused and not SEGNNLayer._warned_unfused:
+        if (halo is not None or split is not None) and g.periodic:
+            raise NotImplementedError(_PERIODIC_NOT_SHARDED)
+        needs_grad = torch.is_grad_enabled() and _needs_grad(self, h)
+        if needs_grad and self.fused and not SEGNNLayer._warned_unfused:
             # the switch is visible: the fused MFMA kernels are inference kernels (no backward); a call that needs a gradient
             # runs the differentiable chain (gather -> TP -> gate -> TP -> gate -> segment-sum on the generic FMA kernels,
             # [E, width] tensors in HBM), which is several times slower -- tools/train_step_bench.py measures both
@@ -119,92 +138,106 @@ class SEGNNLayer(nn.Module):
             warnings.warn("SEGNNLayer: a gradient is required (grad mode on and an input or parameter requires grad) -> the "
                           "unfused differentiable chain runs instead of the fused MFMA inference kernels; wrap inference in "
                           "torch.no_grad() to get the fast path", RuntimeWarning, stacklevel=2)
-        f32 = h.dtype == torch.float32
-        r16 = self.fused and inference and self.fused_available()   # per-TP fused kernels (gather + TP + gate)
-        # ---- message function -> aggregated messages a [N, width] ----
-        one_launch = (self.fused and inference and self.fuse_message and self.fuse_scatter and self._msg is not None and
-                      self._msg.supports(h.dtype) and w is None)
-        a_scale = None  # operand scale of the aggregated messages where the message launch returns it
-        r16u = self.fused and inference and (r16 or (one_launch and self.fused_update_available()))   # update product
-        if h.dtype == torch.bfloat16 and not ((one_launch or r16) and r16u):
-            raise RuntimeError("bf16 storage needs the fused MFMA kernels (inference; hidden 32, or 64 at l_max = 2)")
-        if halo is not None and not inference:
+        message, update = self.paths(h.dtype, needs_grad, w is not None)
+        overlap = message == "one_launch" and halo is not None and split is not None
+        if halo is not None and needs_grad:
             h = halo.refresh(h)  # differentiable refresh, out of place: ghost-row gradients return to their owners
-        elif halo is not None and not (one_launch and split is not None):
+        elif halo is not None and not overlap:
             halo.exchange(h)  # blocking refresh of the ghost rows, in place
-        if one_launch and halo is not None and split is not None:
-            # the refresh is posted first; interior edges (owned src) run while it is in flight, boundary edges after it
-            # landed.  The operand scale has to be fixed BEFORE the refreshed ghost rows are known (the pre-mix table and
-            # the interior launch use it): it is taken from the owned + stale ghost rows with NINE binades of head room
-            # (joint maximum at 2^6 instead of 2^10) -- the fp16 (hi, lo) pair keeps an absolute error of 2^-25 of the scaled
-            # range, so the lower target costs no accuracy, and refreshed rows up to 512 x larger than anything this rank
-            # held stay inside the fp16 range.  Beyond that the overflow flag of the halo is raised (checked once per forward).
-            tok = halo.start(h)
-            if h_scale is None and f32:
-                h_scale = ops.pow2_scale([h], target_log2=6)
-            a, state = self._msg.forward(h, split.graph, self.msg1, self.msg2, h_scale, edges=split.interior,
-                                         return_state=True)
-            halo.finish(h, tok)
-            if state is not None:
-                # the pre-mix launch saw the STALE ghost rows: their row maxima (bound of a row's messages) are recomputed
-                top = self._msg.refresh_row_max(state, h, halo.ghost_rows(), h_scale if f32 else None)
-                if f32:
-                    flag = top >= 2.0 ** 15
-                    halo.overflow = flag if getattr(halo, "overflow", None) is None else (halo.overflow | flag)
-            a = self._msg.forward(h, split.graph, self.msg1, self.msg2, h_scale, edges=split.boundary, cont=state).to(h.dtype)
-            del state
-        elif one_launch:
-            # one launch: SH + TP #1 + gate + TP #2 + gate + segment-sum (message.FusedMessage)
-            if h_scale is None and f32:
-                h_scale = ops.pow2_scale([h])
-            a, a_scale = self._msg.forward(h, g, self.msg1, self.msg2, h_scale, return_scale=True)
-            a = a.to(h.dtype)
-        elif r16:
-            # gather + concat + TP + gate in one kernel each: no [E, 2D+1] / raw-TP tensors in HBM
-            if d.dtype != h.dtype:
-                d = d.to(h.dtype)
-            m = self.msg1.forward_fused([(h, g.dst), (h, g.src), (d, None)], Y, gate=True,
-                                        in_scale=ops.pow2_scale([h, d]) if f32 else None)
-            a = None
-            if self.fuse_scatter and w is None:  # segment-sum in the epilogue of message TP #2 where the library has that kernel
-                a = self.msg2.forward_fused([(m, None)], Y, gate=True, scatter=(g.dst, g.rowptr.numel() - 1))
-            if a is None:
-                m = self.msg2.forward_fused([(m, None)], Y, gate=True)
-                a = ops.segment_sum(m, g, weight=w)
+        # ---- message function -> aggregated messages a [N, width] ----
+        a_scale = None  # operand scale of the aggregated messages where the message launch returns it
+        if overlap:
+            a = self._messages_overlapped(h, h_scale, halo, split)
+        elif message == "one_launch":
+            a, a_scale, h_scale = self._messages_one_launch(h, g, h_scale)
+        elif message == "per_product":
+            a = self._messages_per_product(h, g, Y, d, w)
         else:
-            m = ops.gather_concat(h, g, d)
-            m = self._gate(self.msg1(m, Y))
-            m = self._gate(self.msg2(m, Y))
-            a = ops.segment_sum(m, g, weight=w)
+            a = self._messages_chain(h, g, Y, d, w)
         # ---- node update ----
-        if r16u:
+        if update == "fused":
             # operand scale of [h | a]: h's is known (the previous layer returned it), so only `a` is scanned
+            # (the one-launch message kernel returns the scale of its sums: no scan)
             sc = None
-            if f32 and h_scale is not None and halo is None:
-                # (the one-launch message kernel returns the scale of its sums: no scan)
+            if h.dtype == torch.float32 and h_scale is not None and halo is None:
                 sc = ops.join_pow2_scales(h_scale, a_scale if a_scale is not None else ops.pow2_scale([a]))
-            if self.upd2.fused_supported(False) and h.stride(-1) == 1:
-                if isinstance(self.upd1, SHTensorProduct) and a.stride(-1) == 1:
-                    # both products in one launch: u stays on chip with a power-of-two scale per row
-                    r = self.upd1.forward_update_pair(self.upd2, [(h, None), (a, None)], A, in_scale=sc, residual=h,
-                                                      out_scale=10 if f32 else None)
-                    if r is not None:
-                        return r if f32 else (r, None)
-                # the scale of u comes out of update #1's epilogue; update #2 adds the residual and emits the scale of the
-                # new h in its own: no pass over [N, width] outside the two products
-                u, u_scale = self.upd1.forward_fused([(h, None), (a, None)], A, gate=True, in_scale=sc,
-                                                     out_scale=10 if f32 else None) if f32 else \
-                    (self.upd1.forward_fused([(h, None), (a, None)], A, gate=True), None)
-                if f32:
-                    return self.upd2.forward_fused([(u, None)], A, gate=False, in_scale=u_scale, residual=h, out_scale=10)
-                return self.upd2.forward_fused([(u, None)], A, gate=False, residual=h), None
-            u = self.upd1.forward_fused([(h, None), (a, None)], A, gate=True, in_scale=sc)
-        else:
-            u = self._gate(self.upd1(torch.cat([h, a], 1), A))
-        u = self.upd2(u, A)
-        if f32 and inference:
+            return self._update_fused(h, a, A, sc)
+        u = self.upd2(self._gate(self.upd1(torch.cat([h, a], 1), A)), A)
+        if h.dtype == torch.float32 and not needs_grad:
             return ops.add_pow2_scale(h, u)
         return h + u, None
+
+    def _messages_one_launch(self, h, g, h_scale):
+        """SH + TP #1 + gate + TP #2 + gate + segment-sum in one launch (message.FusedMessage) -> (a, operand scale of a
+        | None, operand scale of h)."""
+        if h_scale is None and h.dtype == torch.float32:
+            h_scale = ops.pow2_scale([h])
+        a, a_scale = self._msg.forward(h, g, self.msg1, self.msg2, h_scale, return_scale=True)
+        return a.to(h.dtype), a_scale, h_scale
+
+    def _messages_overlapped(self, h, h_scale, halo, split):
+        """The one-launch kernel around the halo refresh (``halo.start`` / ``halo.finish``), in place."""
+        # the refresh is posted first; interior edges (owned src) run while it is in flight, boundary edges after it
+        # landed.  The operand scale has to be fixed BEFORE the refreshed ghost rows are known (the pre-mix table and
+        # the interior launch use it): it is taken from the owned + stale ghost rows with NINE binades of head room
+        # (joint maximum at 2^6 instead of 2^10) -- the fp16 (hi, lo) pair keeps an absolute error of 2^-25 of the scaled
+        # range, so the lower target costs no accuracy, and refreshed rows up to 512 x larger than anything this rank
+        # held stay inside the fp16 range.  Beyond that the overflow flag of the halo is raised (checked once per forward).
+        f32 = h.dtype == torch.float32
+        tok = halo.start(h)
+        if h_scale is None and f32:
+            h_scale = ops.pow2_scale([h], target_log2=6)
+        a, state = self._msg.forward(h, split.graph, self.msg1, self.msg2, h_scale, edges=split.interior,
+                                     return_state=True)
+        halo.finish(h, tok)
+        if state is not None:
+            # the pre-mix launch saw the STALE ghost rows: their row maxima (bound of a row's messages) are recomputed
+            top = self._msg.refresh_row_max(state, h, halo.ghost_rows(), h_scale if f32 else None)
+            if f32:
+                flag = top >= 2.0 ** 15
+                halo.overflow = flag if getattr(halo, "overflow", None) is None else (halo.overflow | flag)
+        return self._msg.forward(h, split.graph, self.msg1, self.msg2, h_scale, edges=split.boundary, cont=state).to(h.dtype)
+
+    def _messages_per_product(self, h, g, Y, d, w):
+        # gather + concat + TP + gate in one kernel each: no [E, 2D+1] / raw-TP tensors in HBM
+        if d.dtype != h.dtype:
+            d = d.to(h.dtype)
+        m = self.msg1.forward_fused([(h, g.dst), (h, g.src), (d, None)], Y, gate=True,
+                                    in_scale=ops.pow2_scale([h, d]) if h.dtype == torch.float32 else None)
+        a = None
+        if self.fuse_scatter and w is None:  # segment-sum in the epilogue of message TP #2 where the library has that kernel
+            a = self.msg2.forward_fused([(m, None)], Y, gate=True, scatter=(g.dst, g.rowptr.numel() - 1))
+        if a is None:
+            m = self.msg2.forward_fused([(m, None)], Y, gate=True)
+            a = ops.segment_sum(m, g, weight=w)
+        return a
+
+    def _messages_chain(self, h, g, Y, d, w):
+        m = ops.gather_concat(h, g, d)
+        m = self._gate(self.msg1(m, Y))
+        m = self._gate(self.msg2(m, Y))
+        return ops.segment_sum(m, g, weight=w)
+
+    def _update_fused(self, h, a, A, sc):
+        """h + TP_u2(gate(TP_u1([h | a]))) on the fused kernels, with what the library has for the shape: both products
+        in one launch, else two fused launches, else fused #1 + the module's #2.  ``sc``: operand scale of [h | a]."""
+        f32 = h.dtype == torch.float32
+        if self.upd2.fused_supported(False) and h.stride(-1) == 1:
+            if isinstance(self.upd1, SHTensorProduct) and a.stride(-1) == 1:
+                # both products in one launch: u stays on chip with a power-of-two scale per row
+                r = self.upd1.forward_update_pair(self.upd2, [(h, None), (a, None)], A, in_scale=sc, residual=h,
+                                                  out_scale=10 if f32 else None)
+                if r is not None:
+                    return r if f32 else (r, None)
+            # the scale of u comes out of update #1's epilogue; update #2 adds the residual and emits the scale of the
+            # new h in its own: no pass over [N, width] outside the two products
+            if f32:
+                u, u_scale = self.upd1.forward_fused([(h, None), (a, None)], A, gate=True, in_scale=sc, out_scale=10)
+                return self.upd2.forward_fused([(u, None)], A, gate=False, in_scale=u_scale, residual=h, out_scale=10)
+            u = self.upd1.forward_fused([(h, None), (a, None)], A, gate=True)
+            return self.upd2.forward_fused([(u, None)], A, gate=False, residual=h), None
+        u = self.upd2(self.upd1.forward_fused([(h, None), (a, None)], A, gate=True, in_scale=sc), A)
+        return ops.add_pow2_scale(h, u) if f32 else (h + u, None)
 
 
 def _needs_grad(mod: nn.Module, *tensors) -> bool:
@@ -239,28 +272,24 @@ class SEGNN(nn.Module):
         refreshed from their owners before every message-passing layer; only owned rows of the result
         are meaningful.  ``split`` (``halo.split_graph(g)``): edges into ghost rows dropped and the rest split into
         interior / boundary lists so that the refresh overlaps the interior edges."""
-        if (halo is not None or split is not None) and (g.box is not None or g.cell is not None):
-            raise NotImplementedError("a periodic graph cannot be sharded (halo / split): build the local graph OPEN over the "
-                                      "ghost images of GridHalo(..., periodic=...)")
+        if (halo is not None or split is not None) and g.periodic:
+            raise NotImplementedError(_PERIODIC_NOT_SHARDED)
         if (cutoff is None) != (self.envelope is None):
             raise ValueError("cutoff= is the radius of the envelope: a model built with envelope= needs it, and a model "
                              "without an envelope takes none")
         if self.envelope is not None:
             return self._forward_enveloped(x, g, geometry, halo, split, cutoff)
+        if x.dtype == torch.bfloat16 and self.lmax != 2:
+            raise RuntimeError("bf16 storage is implemented for l_max = 2 (BASELINE config 3)")
+        needs_grad = torch.is_grad_enabled() and _needs_grad(self, x)
         if split is not None:
             g = split.graph
         if geometry is not None:
             Y, d, A = geometry
         else:
-            # per-edge Y [E, (l_max+1)^2] and d [E] are only needed off the one-launch message path
-            one_launch = (not (torch.is_grad_enabled() and _needs_grad(self, x)) and
-                          all(l.fused and l.fuse_message and l.fuse_scatter and l._msg is not None and
-                              l._msg.supports(x.dtype) for l in self.layers))
-            Y, d, A = ops.edge_geometry(g, lmax=self.lmax, want_edge=not one_launch)
-        if x.dtype == torch.bfloat16 and self.lmax != 2:
-            raise RuntimeError("bf16 storage is implemented for l_max = 2 (BASELINE config 3)")
+            Y, d, A = ops.edge_geometry(g, lmax=self.lmax, want_edge=self.wants_edge_geometry(x.dtype, needs_grad))
         sc = None
-        if (x.dtype == torch.float32 and not (torch.is_grad_enabled() and _needs_grad(self, x)) and x.is_cuda and
+        if (x.dtype == torch.float32 and not needs_grad and x.is_cuda and
                 getattr(self.embed, "exact", None) is False and A.shape[0] == x.shape[0] and x.shape[0] > 0 and
                 self.embed.fused_supported(False)):
             # inference, fp32, a shape of the fused kernel: the embedding's epilogue emits the operand scale of h, so that
@@ -280,6 +309,10 @@ class SEGNN(nn.Module):
                                "when the layer's operand scale was fixed (fp16-split operands would overflow); run the layer "
                                "without `split` (blocking exchange) for such inputs")
         return out
+
+    def wants_edge_geometry(self, dtype, needs_grad: bool) -> bool:
+        """Per-edge Y [E, (l_max+1)^2] and d [E] are only needed off the one-launch message path (no envelope)."""
+        return any(l.paths(dtype, needs_grad)[0] != "one_launch" for l in self.layers)
 
     def _forward_enveloped(self, x, g, geometry, halo, split, cutoff):
         """The forward with the cutoff envelope: w = u_p(d / cutoff) once from the edge lengths, the enveloped node

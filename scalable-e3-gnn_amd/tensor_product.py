@@ -38,7 +38,7 @@ class TPPlan:
         self.in1_dim = lib.e3_tp_in1_dim(h)
         self.in2_dim = lib.e3_tp_in2_dim(h)
         self.out_dim = lib.e3_tp_out_dim(h)
-        self._packed = {}
+        self._packed = _lib.PackedCache()
         # algorithmic flops per row: sum over paths of 2 K M min(2 l1+1, 2 l3+1) (the contraction with W; the
         # per-row CG/feature algebra is excluded)
         n, M = {}, {}
@@ -92,36 +92,67 @@ class TPPlan:
         """ws / ns: 6-entry lists (per class) of optional tensors.  The packed buffer is rebuilt when a parameter or
         buffer was replaced or modified through autograd-visible ops (``_version``); in-place edits through ``.data``
         do not bump the version counter -- call ``invalidate_packed()`` after those."""
-        key = (dtype, device) + tuple((t.data_ptr(), t._version) if t is not None else None for t in ws + ns)
-        hit = self._packed.get((dtype, device))
-        stream = torch.cuda.current_stream(device)
-        if hit is not None and hit[0] == key:
-            if hit[2] != stream.cuda_stream:
-                stream.wait_event(hit[3])  # packed on another stream: order this stream behind the pack kernels
-            return hit[1]
-        lib = _lib.load()
-        code = _lib.dtype_code(dtype)
-        for t in ws + ns:
-            if t is not None and t.numel() and (t.dtype != dtype or t.device != device):
-                raise RuntimeError(f"tensor product: parameter {t.dtype}/{t.device} vs input {dtype}/{device}")
-        h = self.handle(device)
-        nbytes = lib.e3_tp_packed_bytes(h, code)
-        if nbytes < 0:
-            raise RuntimeError(f"tensor product supports float32/float64/bfloat16, got {dtype}")
-        packed = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        P6 = ctypes.c_void_p * 6
-        ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None
-        wsc = [w.detach().contiguous() if w is not None else None for w in ws]
-        nsc = [n.detach().contiguous() if n is not None else None for n in ns]
-        _lib.check(lib.e3_tp_pack_weights(h, P6(*map(ptr, wsc)), P6(*map(ptr, nsc)), code,
-                                          packed.data_ptr(), stream.cuda_stream), "e3_tp_pack_weights")
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        self._packed[(dtype, device)] = (key, packed, stream.cuda_stream, ev)
-        return packed
+        def pack(stream):
+            lib = _lib.load()
+            code = _lib.dtype_code(dtype)
+            for t in ws + ns:
+                if t is not None and t.numel() and (t.dtype != dtype or t.device != device):
+                    raise RuntimeError(f"tensor product: parameter {t.dtype}/{t.device} vs input {dtype}/{device}")
+            h = self.handle(device)
+            nbytes = lib.e3_tp_packed_bytes(h, code)
+            if nbytes < 0:
+                raise RuntimeError(f"tensor product supports float32/float64/bfloat16, got {dtype}")
+            packed = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+            P6 = ctypes.c_void_p * 6
+            ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None
+            wsc = [w.detach().contiguous() if w is not None else None for w in ws]
+            nsc = [n.detach().contiguous() if n is not None else None for n in ns]
+            _lib.call("e3_tp_pack_weights", h, P6(*map(ptr, wsc)), P6(*map(ptr, nsc)), code, packed.data_ptr(), stream)
+            return packed
+
+        return self._packed.get(ws + ns, dtype, device, pack)
 
     def invalidate_packed(self):
-        self._packed = {}
+        self._packed.invalidate()
+
+    # kernel-name suffix of the profiling records: how the MFMA kernels run the storage type
+    MODE = {torch.float32: "<fp16x3 split MFMA>", torch.bfloat16: "<bf16 storage, bf16 MFMA>"}
+
+    @staticmethod
+    def _segments(segments, B, io, strict: bool):
+        """[(tensor [R, ncols], row_index int32 [B] | None), ...] -> (``TPSegment`` array, the tensors it points into).
+        strict: a [R] column is widened, rows are made contiguous, and a segment that does not fit raises.  Lenient (the
+        update pair: whole rows only): None for anything but contiguous [B, ncols] rows of ``io`` without an index."""
+        segs = (TPSegment * len(segments))()
+        keep = []
+        for i, (t, idx) in enumerate(segments):
+            if strict:
+                if t.dtype != io or not t.is_cuda:
+                    raise RuntimeError("forward_fused: all segments must share one dtype and live on a ROCm device")
+                if t.dim() == 1:
+                    t = t.unsqueeze(1)
+                if t.stride(-1) != 1:
+                    t = t.contiguous()
+                if idx is not None:
+                    assert idx.dtype == torch.int32 and idx.numel() == B
+                    segs[i].row_index = idx.data_ptr()
+                else:
+                    assert t.shape[0] == B
+            elif idx is not None or t.dtype != io or t.dim() != 2 or t.stride(-1) != 1 or t.shape[0] != B:
+                return None
+            keep.append(t)
+            segs[i].base, segs[i].ld, segs[i].ncols = t.data_ptr(), t.stride(0), t.shape[1]
+        return segs, keep
+
+    @staticmethod
+    def _scales(keep, io, in_scale, out_scale, dev):
+        """-> (the operand scale of the segments -- ``in_scale``, or computed here in fp32 storage --, its pointer for
+        the entry (NULL outside fp32 storage), the 4-float buffer that receives the result's scale | None)."""
+        if io == torch.float32 and in_scale is None:
+            from . import ops
+            in_scale = ops.pow2_scale(keep)
+        sc4 = torch.empty(4, dtype=torch.float32, device=dev) if out_scale is not None else None
+        return in_scale, (in_scale.data_ptr() if (in_scale is not None and io == torch.float32) else None), sc4
 
     def forward_fused(self, ws, ns, segments, in2, gate: bool, tag="", scatter=None, in_scale=None, residual=None,
                       out_scale=None):
@@ -134,27 +165,12 @@ class TPPlan:
         lib = _lib.load()
         B = in2.shape[0]
         dev = in2.device
-        segs = (TPSegment * len(segments))()
-        keep = []
         io = segments[0][0].dtype
         if io not in (torch.float32, torch.bfloat16):
             raise RuntimeError(f"forward_fused: float32 / bfloat16 storage only, got {io}")
         if in2.dtype != torch.float32:
             raise RuntimeError("forward_fused: in2 (spherical harmonics) is always float32")
-        for i, (t, idx) in enumerate(segments):
-            if t.dtype != io or not t.is_cuda:
-                raise RuntimeError("forward_fused: all segments must share one dtype and live on a ROCm device")
-            if t.dim() == 1:
-                t = t.unsqueeze(1)
-            if t.stride(-1) != 1:
-                t = t.contiguous()
-            keep.append(t)
-            segs[i].base, segs[i].ld, segs[i].ncols = t.data_ptr(), t.stride(0), t.shape[1]
-            if idx is not None:
-                assert idx.dtype == torch.int32 and idx.numel() == B
-                segs[i].row_index = idx.data_ptr()
-            else:
-                assert t.shape[0] == B
+        segs, keep = self._segments(segments, B, io, strict=True)
         width = self.out_dim
         if gate:
             width = self.gated_width()
@@ -177,10 +193,7 @@ class TPPlan:
         esz = out.element_size()
         with torch.cuda.device(dev):
             packed = self.packed(ws, ns, io, dev)
-            if io == torch.float32 and in_scale is None:
-                from . import ops
-                in_scale = ops.pow2_scale(keep)
-            sc = in_scale.data_ptr() if (in_scale is not None and io == torch.float32) else None
+            in_scale, sc, sc4 = self._scales(keep, io, in_scale, out_scale, dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
             t0 = profiling.begin() if profiling.enabled() else None
             h = self.handle(dev)
@@ -189,7 +202,6 @@ class TPPlan:
                     raise RuntimeError("forward_fused: residual / out_scale do not combine with scatter")
                 if residual is not None and (residual.shape != out.shape or residual.dtype != io or residual.stride(-1) != 1):
                     raise RuntimeError(f"forward_fused: residual must be {tuple(out.shape)} {io}, contiguous rows")
-                sc4 = torch.empty(4, dtype=torch.float32, device=dev) if out_scale is not None else None
                 _lib.check(lib.e3_tp_forward_fused_epilogue(
                     h, ctypes.byref(segs), len(segments), in2.data_ptr(), in2.stride(0), packed.data_ptr(), out.data_ptr(),
                     out.stride(0), B, _lib.dtype_code(io), 1 if gate else 0, sc,
@@ -214,9 +226,8 @@ class TPPlan:
                 nb = sum((t.shape[0] * t.shape[1] * esz + (4 * B if idx is not None else 0)) for t, idx in
                          [(k, s[1]) for k, s in zip(keep, segments)]) + 4 * self.in2_dim * B + \
                      (esz * width * B if scatter is None else 4 * B + 4 * width * scatter[1])
-                mode = "<bf16 storage, bf16 MFMA>" if io == torch.bfloat16 else "<fp16x3 split MFMA>"
                 profiling.end(f"tp_fused{'+segsum' if scatter is not None else ''} {tag} B={B}", B, nb, t0, flops=self.flops_per_row * B,
-                              kernel=(lib.e3_tp_last_fused_kernel() or b"e3::tp_fwd_mfma_r16_kernel").decode() + mode)
+                              kernel=(lib.e3_tp_last_fused_kernel() or b"e3::tp_fwd_mfma_r16_kernel").decode() + self.MODE[io])
         if out_scale is not None:
             return out, sc4
         return out
@@ -232,13 +243,10 @@ class TPPlan:
         io = segments[0][0].dtype
         if io not in (torch.float32, torch.bfloat16) or in2.dtype != torch.float32 or in2.stride(-1) != 1:
             return None
-        segs = (TPSegment * len(segments))()
-        keep = []
-        for i, (t, idx) in enumerate(segments):
-            if idx is not None or t.dtype != io or t.stride(-1) != 1 or t.shape[0] != B:
-                return None
-            keep.append(t)
-            segs[i].base, segs[i].ld, segs[i].ncols = t.data_ptr(), t.stride(0), t.shape[1]
+        marshalled = self._segments(segments, B, io, strict=False)
+        if marshalled is None:
+            return None
+        segs, keep = marshalled
         out = torch.empty((B, plan2.out_dim), dtype=io, device=dev)
         if residual is not None and (residual.shape != out.shape or residual.dtype != io or residual.stride(-1) != 1):
             raise RuntimeError(f"forward_update_pair: residual must be {tuple(out.shape)} {io}, contiguous rows")
@@ -246,11 +254,7 @@ class TPPlan:
             h1, h2 = self.handle(dev), plan2.handle(dev)
             packed1 = self.packed(ws, ns, io, dev)
             packed2 = plan2.packed(ws2, ns2, io, dev)
-            if io == torch.float32 and in_scale is None:
-                from . import ops
-                in_scale = ops.pow2_scale(keep)
-            sc = in_scale.data_ptr() if (in_scale is not None and io == torch.float32) else None
-            sc4 = torch.empty(4, dtype=torch.float32, device=dev) if out_scale is not None else None
+            in_scale, sc, sc4 = self._scales(keep, io, in_scale, out_scale, dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
             t0 = profiling.begin() if profiling.enabled() else None
             st = lib.e3_tp_forward_update_pair(
@@ -264,9 +268,8 @@ class TPPlan:
             if t0 is not None:
                 esz = out.element_size()
                 nb = sum(t.numel() * esz for t in keep) + 4 * self.in2_dim * B + esz * out.numel() * (2 if residual is not None else 1)
-                mode = "<bf16 storage, bf16 MFMA>" if io == torch.bfloat16 else "<fp16x3 split MFMA>"
                 profiling.end(f"tp_update_pair B={B}", B, nb, t0, flops=(self.flops_per_row + plan2.flops_per_row) * B,
-                              kernel=(lib.e3_tp_last_fused_kernel() or b"e3::tp_update_pair_r16_kernel").decode() + mode)
+                              kernel=(lib.e3_tp_last_fused_kernel() or b"e3::tp_update_pair_r16_kernel").decode() + self.MODE[io])
         if out_scale is not None:
             return out, sc4
         return out

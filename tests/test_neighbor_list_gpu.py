@@ -327,8 +327,7 @@ def test_periodic_model_on_a_trajectory(mode, envelope, lmax):
     assert float(b[1].abs().max()) > 0 and float(b[3].abs().max()) > 0
     if envelope is None:
         # no_grad: the one-launch message kernel (the condition of SEGNN.forward), on the list's graph
-        assert all(l.fused and l.fuse_message and l.fuse_scatter and l._msg is not None and l._msg.supports(torch.float32)
-                   for l in model.net.layers)
+        assert all(l.paths(torch.float32, False)[0] == "one_launch" for l in model.net.layers)
         with torch.no_grad():
             e_nl = model(x, pd, R, neighbors=nl)
             e_direct = model(x, pd, R, **direct)
