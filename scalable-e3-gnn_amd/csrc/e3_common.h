@@ -25,6 +25,12 @@ void set_hip_error(hipError_t e, const char* what);
     }                                                        \
   } while (0)
 
+// The dynamic-LDS limit of a kernel is a per-device attribute of the function, and the library's one place that sets it:
+// E3_OK without a HIP call for bytes <= 64 KiB (the default limit); above, the limit of (fn, current device) is raised
+// monotonically under one lock -- setting the size of each launch would let two host threads with different plans lower it
+// under each other's launches.  E3_ERR_HIP (recorded through set_hip_error) on failure.  e3_l1tp.hip
+int ensure_dyn_lds(const void* fn, size_t bytes);
+
 // ---- element types --------------------------------------------------------------------------
 using bf16 = __hip_bfloat16;
 

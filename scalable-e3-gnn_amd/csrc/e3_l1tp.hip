@@ -14,13 +14,30 @@
 
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <mutex>
+#include <utility>
 
 namespace e3 {
 
 static thread_local std::string g_hip_err;
 void set_hip_error(hipError_t e, const char* what) {
   g_hip_err = std::string(hipGetErrorName(e)) + ": " + hipGetErrorString(e) + " in " + what;
+}
+
+int ensure_dyn_lds(const void* fn, size_t bytes) {
+  if (bytes <= 64 * 1024) return E3_OK;
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, size_t> have;
+  int dev = 0;
+  E3_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& cur = have[std::make_pair(fn, dev)];
+  if (bytes > cur) {
+    E3_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    cur = bytes;
+  }
+  return E3_OK;
 }
 
 
@@ -189,8 +206,7 @@ static int launch_generic(const e3_l1tp_plan* plan, const void* in1, int64_t ld1
   size_t smem = (size_t)R * (plan->dev.D1 + 4) * sizeof(A);
   if (smem > 160 * 1024) return E3_ERR_UNSUPPORTED;
   auto kern = l1tp_fwd_generic_kernel<T, R>;
-  if (smem > 64 * 1024)
-    E3_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  if (int st = ensure_dyn_lds((const void*)kern, smem); st != E3_OK) return st;
   int64_t ntiles = (B + R - 1) / R;
   int grid = (int)std::min<int64_t>(ntiles, 256 * 8);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, (const T*)in1, ld1, (const T*)in2, ld2,

@@ -424,8 +424,7 @@ static int launch_backward(const e3_l1tp_plan* plan, const void* in1, int64_t ld
 
   if (gin1 || gin2) {
     auto kern = l1tp_bwd_rows_kernel<T>;
-    if (smem > 64 * 1024)
-      E3_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (int st = ensure_dyn_lds((const void*)kern, smem); st != E3_OK) return st;
     int grid = (int)std::min<int64_t>(g.ntiles, 256 * 8);
     A* gy_rows = (gin2 && bcast) ? (A*)(ws + g.gy_off) : nullptr;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, a, (T*)gin1, ldgi, gy_rows,
@@ -445,8 +444,7 @@ static int launch_backward(const e3_l1tp_plan* plan, const void* in1, int64_t ld
   if (any_w) {
     WOffsets wo = w_offsets(plan);
     auto kern = l1tp_bwd_w_kernel<T>;
-    if (smem > 64 * 1024)
-      E3_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (int st = ensure_dyn_lds((const void*)kern, smem); st != E3_OK) return st;
     A* partial = (A*)(ws + g.part_off);
     dim3 grid(g.nchunks, (unsigned)((wo.total + kWChunk - 1) / kWChunk));
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, a, partial, wo, g.tiles_per_chunk, p);

@@ -483,11 +483,9 @@ __global__ __launch_bounds__(512) void l1tp_fwd_mfma_kernel(const float* __restr
 }
 
 int mfma_set_lds_attr() {
-  E3_HIP_CHECK(hipFuncSetAttribute((const void*)l1tp_fwd_mfma_kernel<true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
-  E3_HIP_CHECK(hipFuncSetAttribute((const void*)l1tp_fwd_mfma_kernel<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
-  return E3_OK;
+  // the budget every plan's lds_bytes stays within, once per device (at the upload of the first plan)
+  const int st = ensure_dyn_lds((const void*)l1tp_fwd_mfma_kernel<true>, kLdsBudget);
+  return st != E3_OK ? st : ensure_dyn_lds((const void*)l1tp_fwd_mfma_kernel<false>, kLdsBudget);
 }
 
 int mfma_forward(const e3_l1tp_plan* P, const void* in1, int64_t ld1, const void* in2, int64_t ld2,

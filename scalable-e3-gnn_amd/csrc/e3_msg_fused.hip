@@ -30,7 +30,8 @@ int msg_fused_setup(const MsgShape& k, PbcMode mode, int io, int dev, int* workg
     const size_t lds = fused_lds_bytes(k);
     int cus = 0, per_cu = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    if (!kern || hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+    // the occupancy query comes after the limit is raised: it answers for the limit in force
+    if (!kern || ensure_dyn_lds(kern, lds) != E3_OK ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu < 1)
       return E3_ERR_HIP;
     wg = cus * (per_cu < 4 ? per_cu : 4);

@@ -1375,14 +1375,14 @@ int msg_ws_launch(const e3_msg_plan& P, const MsgOperands& a, const MsgPbc& pbc,
   {
     std::lock_guard<std::mutex> lock(mu);
     if (dev < 0 || dev >= 64) return E3_ERR_INVALID_ARG;
-    if (cus_of[dev][io][pbc.mode] == 0) {  // once per device, storage type and box kind: the kernel needs its LDS image admitted
-      E3_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (cus_of[dev][io][pbc.mode] == 0) {  // once per device, storage type and box kind
       int n = 0;
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
       cus_of[dev][io][pbc.mode] = n;
     }
     cus = cus_of[dev][io][pbc.mode];
   }
+  if (const int st = ensure_dyn_lds(kern, lds); st != E3_OK) return st;  // the kernel needs its LDS image admitted
   const int chunk = msg_ws_chunk_edges(a.tiles_per_block);
   const int64_t nchunks = (a.E + chunk - 1) / chunk;
   int nwg = (int)std::min<int64_t>(cus, nchunks);  // one workgroup of 8 waves per CU

@@ -1,5 +1,6 @@
-// Internal declarations shared by e3_tp.hip (plan, generic kernel, C ABI) and the MFMA path (e3_tp_mfma.hip: host plan and
-// weight packing; e3_tp_mfma_r16.hip: the kernel).
+// What the MFMA forward of the general tensor product (e3_tp_mfma.hip: host plan and weight packing; e3_tp_mfma_r16.hip: the
+// kernels) shares with the plan and the forward entries (e3_tp.hip).  The plan itself and the helpers of the generic kernels
+// are in e3_tp_plan.h, which includes this file.
 #pragma once
 #include "e3_common.h"
 

@@ -1200,17 +1200,9 @@ static int r16_launch(const void* fn, const char* name, size_t lds_bytes, int wa
                       const void* in2, int64_t ld2, const void* packed, void* out, int64_t ldo, int64_t B,
                       const int32_t* ocol_tab, const float* in_scale, const PairArgs* pair, hipStream_t s) {
   if ((size_t)waves_per_simd * lds_bytes > (size_t)kFastLds) return 0;
-  {  // the dynamic-LDS limit is a per-device attribute of the function
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -E3_ERR_HIP;
-    static std::mutex mu;
-    static std::vector<std::pair<const void*, int>> configured;
-    std::lock_guard<std::mutex> lock(mu);
-    if (std::find(configured.begin(), configured.end(), std::make_pair(fn, dev)) == configured.end()) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return -E3_ERR_HIP;
-      configured.emplace_back(fn, dev);
-    }
-  }
+  // lds_bytes is no constant of `fn`: the tables grow with Dout and the out channel count, which differ between plans of one
+  // instantiation (same tile counts), so the limit has to follow the largest plan seen
+  if (const int st = ensure_dyn_lds(fn, lds_bytes); st != E3_OK) return -st;
   const int64_t ntiles = (B + 15) / 16;
   const int grid = (int)std::min<int64_t>((ntiles + kR16Waves - 1) / kR16Waves, 256 * waves_per_simd);
   const float* in2f = (const float*)in2;

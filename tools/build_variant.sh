@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/build_variant.sh NAME "-DE3_MSG_X=1 ..." [SOURCE]  -> scalable-e3-gnn_amd/lib/exp/libe3gnn_NAME.so
 # Experiment builds of one source of the library (development tool; SOURCE = e3_msg_fused (default: the launch of the
-# one-wave-per-tile message kernel) | e3_msg_fused_f32 | e3_msg_fused_bf16 (its instantiations) | e3_msg_ws | ...):
+# one-wave-per-tile message kernel) | e3_msg_fused_f32 | e3_msg_fused_bf16 (its instantiations) | e3_msg_ws | e3_tp | e3_tp_bwd | e3_tp_wgrad | ...):
 # the other objects are reused from csrc/build.
 set -e
 name=$1; flags=$2; src=${3:-e3_msg_fused}
