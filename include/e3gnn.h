@@ -724,6 +724,47 @@ int e3_segment_sum_weighted_backward(const float* g_agg, int64_t ld_gagg, const 
                                      void* stream);
 
 /* =================================================================================================
+ * Second derivatives (fp32): what the backward of the stage backwards above needs besides those entries themselves, so that
+ * a loss on the forces F = -dE/dpos has parameter gradients.  The tensor products, gather/concat and the segment sums are
+ * multilinear: their double backward is the existing entries with one argument replaced by a cotangent.  New arithmetic:
+ *
+ *   e3_edge_geometry_jvp : e3_edge_geometry_backward is linear in (g_edge_y, g_edge_d, g_node_a), so the cotangents of those
+ *       three for a cotangent v [N,3] of g_pos are the tangent of the forward along the displacement field v.  Per edge
+ *       t_e = v[src] - v[dst] (r_e, u_e, d_e as in the forward: the minimum image in a box or cell, whose shift is piecewise
+ *       constant):  d_edge_d[e] = u_e . t_e;  d_edge_y[e,k] = (dY_k/dr) t_e with du/dr = (I - u u^T) / d and the b(u) of
+ *       e3_edge_geometry_l2, d_edge_y[e,0] = 0;  d_node_a[i,k] = (1/deg_i) sum over CSR row i of d_edge_y[e,k],
+ *       d_node_a[i,0] = 0.  Edges with d = 0 and rows without edges give zeros.  Each of the three outputs may be NULL.  One
+ *       wave per row; d_node_a is one fixed-order wave reduction per row (no atomics): bit-equal from run to run.  The
+ *       derivative of g_pos w.r.t. pos itself (the Hessian of Y, d, A in r) is NOT provided.
+ *       E3_ERR_INVALID_ARG for lmax outside {1, 2}, N < 0, an invalid box / cell, or (N > 0) a NULL pos4 / rowptr / src / v.
+ *
+ *   e3_gate_blocks_backward2 : in, g_out as e3_gate_blocks_backward, c = the cotangent of its g_in (layout of in).  With
+ *       s = sigmoid, one launch writes cot_g_out (layout of g_out) and cot_in (layout of in), either may be NULL:
+ *         scalars  cot_g_out = c silu'(x),  cot_in = c g_out silu''(x),  silu'' = s' (2 + x (1 - 2 s)),  s' = s (1 - s)
+ *         gated    cot_g_out[v_m] = s(g) c[v_m] + s'(g) c[g] v_m,       cot_in[v_m] = s'(g) c[g] g_out[v_m]
+ *         gate     cot_in[g] = s'(g) sum_m c[v_m] g_out[v_m] + s''(g) c[g] sum_m v_m g_out[v_m],  s'' = s' (1 - 2 s)
+ *
+ *   e3_cutoff_envelope_backward2 : c = the cotangent of e3_cutoff_envelope_backward's g_d.  cot_g_w[e] = c du/dd,
+ *       cot_d[e] = c g_w d2u/dd2,  d2u/dd2 = -(p (p+1) (p+2) / 2) / r_c^2 * x^(p-2) (1 - x) ((p-1) (1 - x) - 2 x)  (x^0 = 1);
+ *       both EXACTLY 0 for d >= r_c.  Either output may be NULL (g_w is not read when cot_d is NULL).
+ * ================================================================================================= */
+int e3_edge_geometry_jvp(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax, const float* v,
+                         float* d_edge_y, float* d_edge_d, float* d_node_a, void* stream);
+/* periodic box: as e3_edge_geometry_pbc */
+int e3_edge_geometry_jvp_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                             const float box[3], const float* v, float* d_edge_y, float* d_edge_d, float* d_node_a,
+                             void* stream);
+/* general cell: as e3_edge_geometry_cell */
+int e3_edge_geometry_jvp_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                              const float cell[9], const float* v, float* d_edge_y, float* d_edge_d, float* d_node_a,
+                              void* stream);
+int e3_gate_blocks_backward2(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, const float* c,
+                             int64_t ld_c, float* cot_g_out, int64_t ld_cgout, float* cot_in, int64_t ld_cin, int64_t B,
+                             int ns, int nblocks, const int32_t* ls, const int32_t* muls, void* stream);
+int e3_cutoff_envelope_backward2(const float* edge_d, const float* g_w, const float* c, int64_t E, float r_c, int p,
+                                 float* cot_g_w, float* cot_d, void* stream);
+
+/* =================================================================================================
  * Verlet neighbour list (neighbor_list.NeighborList): a graph of e3_rg_* built once at the radius r + skin is cut down, on
  * the device, to the pairs within r at the current positions -- an ordinary CSR graph at radius r in the stored graph's node
  * order -- and the largest displacement since the build comes back with it.  One entry per periodicity mode (box[3] as in

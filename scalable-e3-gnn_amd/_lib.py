@@ -194,6 +194,18 @@ SIGNATURES = {
                                         c_void_p]),
     "e3_segment_sum_weighted_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
                                                  c_void_p, c_int64, c_void_p, c_void_p]),
+    # second derivatives: tangent of the edge geometry along v [N,3] (..., lmax[, box | cell], v, dY, dd, dA, stream), and the
+    # backward of the gate's and the envelope's backward
+    "e3_edge_geometry_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "e3_edge_geometry_jvp_pbc": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float3, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "e3_edge_geometry_jvp_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    "e3_gate_blocks_backward2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                         c_int64, c_int64, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]),
+    "e3_cutoff_envelope_backward2": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float, c_int, c_void_p, c_void_p,
+                                             c_void_p]),
     # Verlet neighbour list: the stored graph pruned to r at the current positions (r = float)
     "e3_nl_workspace_bytes": (c_int64, [c_int64]),
     "e3_nl_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_float, c_void_p,
@@ -350,6 +362,18 @@ class PackedCache:
         ev.record(stream)
         self._slots[(dtype, device)] = (key, packed, stream.cuda_stream, ev)
         return packed
+
+    def peek(self, tensors, dtype, device):
+        """The slot's buffer when it was packed from exactly these tensors (same ``(data_ptr, _version)``), else None; never
+        packs and never replaces the slot."""
+        import torch
+        hit = self._slots.get((dtype, device))
+        if hit is None or hit[0] != tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors):
+            return None
+        stream = torch.cuda.current_stream(device)
+        if hit[2] != stream.cuda_stream:
+            stream.wait_event(hit[3])
+        return hit[1]
 
     def invalidate(self):
         self._slots = {}

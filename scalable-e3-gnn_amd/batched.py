@@ -7,8 +7,11 @@ with the same kernels as the single-cloud path.  The neighbour search runs on th
 returned carries the ORIGINAL coordinates, so edge vectors / spherical harmonics see no shift rounding.  The energy
 head is the per-molecule sum of a scalar (`1x0e`) node readout.  The force head is -dE/dpos by reverse-mode autograd
 through the whole message pass: every stage has a HIP backward (tensor products: `e3_l1tp_backward` / `e3_tp_backward`;
-edge geometry, gather/concat, gates, segment-sum: `e3_*_backward`, csrc/e3_edge_bwd.hip).  First order only: forces can
-be predicted and energies trained on; training ON forces would need the second derivative, which is not implemented.
+edge geometry, gather/concat, gates, segment-sum: `e3_*_backward`, csrc/e3_edge_bwd.hip).  With ``create_graph=True`` the
+forces keep their graph: every stage's backward has a backward of its own (the multilinear stages by composition of the
+same entries; `e3_edge_geometry_jvp`, `e3_gate_blocks_backward2`, `e3_cutoff_envelope_backward2`), so a loss on energies
+AND forces has parameter gradients.  The derivative of the forces w.r.t. the positions (the Hessian of
+Y, d, A in r) is not built: a parameter gradient never needs it.
 Virials and stress are the derivative w.r.t. a zero strain per structure, reduced inside the same geometry backward
 (`e3_edge_geometry_backward_strained`); `PeriodicEnergyModel` is the periodic-box counterpart of `BatchedEnergyModel`.
 """
@@ -84,12 +87,32 @@ def _neighbors_graph(neighbors, pos, r, skin, defaults: dict):
     return neighbors.update(pos)
 
 
+_NO_SECOND_ORDER_STRAIN = ("create_graph=True with virial= / stress=: the strained edge geometry has no tangent kernel, so the "
+                           "virial and the stress cannot be trained on")
+
+
+def _check_create_graph(net, x, forces: bool, strained: bool):
+    """The preconditions of ``create_graph=True`` (second derivatives: a loss on the forces)."""
+    if strained:
+        raise NotImplementedError(_NO_SECOND_ORDER_STRAIN)
+    if x.dtype == torch.bfloat16:
+        raise NotImplementedError("create_graph=True with bf16 storage: bf16 runs the fused inference kernels only and has no "
+                                  "differentiable chain")
+    if not forces:
+        raise ValueError("create_graph=True keeps the graph of the forces: it needs forces=True")
+    if not any(p.requires_grad for p in net.parameters()):
+        raise ValueError("create_graph=True needs at least one parameter that requires grad: the graph of the forces leads "
+                         "to the parameters only (the derivative of the forces w.r.t. the positions is not implemented)")
+
+
 def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure, cutoff_kw=None, halo=None,
-                          split=None):
+                          split=None, create_graph=False):
     """Energy of ``net``'s scalar node readout summed per segment (``seg`` [N] graph order, ``n_seg`` segments; ``seg``
     None: the 0-d total), and from ONE backward pass through the differentiable chain dE/dpos_g [N,3] (``forces``) and
     dE/deps [n_strain,3,3] at a zero per-structure strain (``n_strain`` > 0; ``structure`` [N] graph order, None = one
     structure).  -> (energy, dE/dpos_g | None, dE/deps | None); the energy keeps its graph in training mode.
+    ``create_graph``: the backward pass is itself recorded, so dE/dpos_g carries a graph that leads to the parameters (a
+    loss on the forces can be differentiated once more), and the energy keeps its graph in eval mode too.
 
     ``halo`` / ``split`` (sharded path; ``g`` = ``split.graph``): the readout is summed over THIS rank's owned rows, the
     ghost rows are refreshed by ``halo.refresh`` in every layer, and ``halo.anchor`` is among the differentiated inputs, so
@@ -107,10 +130,13 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
         else:
             energy = torch.zeros(n_seg, dtype=e_node.dtype, device=e_node.device).index_add(0, seg, e_node[:, 0])
         leaves = ([p] if forces else []) + ([eps] if eps is not None else []) + ([] if halo is None else [halo.anchor])
-        grads = list(torch.autograd.grad(energy.sum(), leaves, retain_graph=net.training))
+        if create_graph:
+            grads = list(torch.autograd.grad(energy.sum(), leaves, create_graph=True))
+        else:
+            grads = list(torch.autograd.grad(energy.sum(), leaves, retain_graph=net.training))
     gpos = grads.pop(0) if forces else None
     geps = grads.pop(0) if eps is not None else None
-    return (energy if net.training else energy.detach()), gpos, geps
+    return (energy if (net.training or create_graph) else energy.detach()), gpos, geps
 
 
 class BatchedEnergyModel(nn.Module):
@@ -124,7 +150,7 @@ class BatchedEnergyModel(nn.Module):
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, forces: bool = False,
-                virial: bool = False, skin: float = 0.0, neighbors=None):
+                virial: bool = False, skin: float = 0.0, neighbors=None, create_graph: bool = False):
         """-> energies [n_mol]; with ``forces=True``: (energies, forces [N,3] = -dE/dpos in the caller's atom order);
         with ``virial=True`` the per-molecule virials W [n_mol,3,3] = -dE/deps (zero strain per molecule, not
         symmetrised) come last: (energies, forces, W) or (energies, W).
@@ -135,7 +161,15 @@ class BatchedEnergyModel(nn.Module):
         ``neighbors`` (a ``NeighborList(r, skin, batch=batch)``): the graph is ``neighbors.update(pos)`` -- built at the
         list's ``r + skin`` once, pruned to ``r`` on the device while no atom has moved half the skin -- for any model,
         enveloped or not; ``skin`` stays 0 and ``batch`` must be the tensor the list was made with (compared when the
-        list rebuilds)."""
+        list rebuilds).
+
+        ``create_graph=True`` (needs ``forces=True`` and a parameter that requires grad; fp32): energies and forces both
+        carry a graph, in ``train()`` and ``eval()`` mode, so ``loss(energies, forces).backward()`` fills ``p.grad`` of
+        every parameter -- training on forces.  The graph leads to the parameters only: the derivative of the forces
+        w.r.t. the positions is not built.  ``NotImplementedError`` with ``virial=True`` (no tangent kernel for the
+        strained geometry) and for bf16 storage.  False (the default) is the first-order call, unchanged."""
+        if create_graph:
+            _check_create_graph(self.net, x, forces, virial)
         if neighbors is not None:
             if neighbors.batch is None:
                 raise ValueError("neighbors= of a batched model must be a NeighborList made with batch=")
@@ -153,7 +187,8 @@ class BatchedEnergyModel(nn.Module):
             e_node = self.net(x[perm], g, **cut)
             return torch.zeros(n_mol, dtype=e_node.dtype, device=e_node.device).index_add_(0, mol, e_node[:, 0])
         energy, gpos, geps = _energy_and_gradients(self.net, x[perm], g, pos[perm], mol, n_mol, forces,
-                                                   n_mol if virial else 0, mol if virial else None, cut)
+                                                   n_mol if virial else 0, mol if virial else None, cut,
+                                                   create_graph=create_graph)
         out = [energy]
         if forces:
             f = torch.empty_like(gpos)
@@ -178,7 +213,8 @@ class PeriodicEnergyModel(nn.Module):
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, forces: bool = False,
-                virial: bool = False, stress: bool = False, cell=None, origin=None, skin: float = 0.0, neighbors=None):
+                virial: bool = False, stress: bool = False, cell=None, origin=None, skin: float = 0.0, neighbors=None,
+                create_graph: bool = False):
         """x [N, in_dim], pos [N,3] (caller order; coordinates on periodic axes may be unwrapped).  -> the 0-d energy,
         then whichever of forces [N,3] (= -dE/dpos, caller order), virial W [3,3] (= -dE/deps at eps = 0, not
         symmetrised) and stress [3,3] (= (1/V) dE/deps = -W/V, V = L_x L_y L_z) were requested, in that order; the
@@ -193,8 +229,17 @@ class PeriodicEnergyModel(nn.Module):
         ``neighbors`` (a ``NeighborList`` holding the box or cell): the graph is ``neighbors.update(pos)`` -- built at the
         list's ``r + skin`` once, pruned to ``r`` on the device while no particle has moved half the skin -- for any
         model, enveloped or not; ``lo`` / ``hi`` / ``periodic`` / ``cell`` / ``origin`` / ``skin`` then stay at their
-        defaults (ValueError otherwise) and ``stress=True`` needs a list periodic on all three axes."""
+        defaults (ValueError otherwise) and ``stress=True`` needs a list periodic on all three axes.
+
+        ``create_graph=True`` (needs ``forces=True`` and a parameter that requires grad; fp32): the energy and the forces
+        both carry a graph, in ``train()`` and ``eval()`` mode, so ``loss(energy, forces).backward()`` fills ``p.grad`` of
+        every parameter -- training on forces -- for an open box, a box and ``cell=``, with or without ``envelope=``,
+        ``skin=`` and ``neighbors=``.  The graph leads to the parameters only: the derivative of the forces w.r.t. the
+        positions is not built.  ``NotImplementedError`` with ``virial=True`` / ``stress=True`` (no tangent kernel for the
+        strained geometry) and for bf16 storage.  False (the default) is the first-order call, unchanged."""
         from .radius_graph import periodic_mask
+        if create_graph:
+            _check_create_graph(self.net, x, forces, virial or stress)
         r_env, r = r, _skin_radius(self.net, r, skin)
         cut = _cutoff_kw(self.net, r_env)
         if neighbors is not None:
@@ -214,7 +259,7 @@ class PeriodicEnergyModel(nn.Module):
         if not (forces or virial or stress):
             return self.net(x[perm], g, **cut)[:, 0].sum()
         energy, gpos, geps = _energy_and_gradients(self.net, x[perm], g, pos[perm], None, 1, forces,
-                                                   1 if (virial or stress) else 0, None, cut)
+                                                   1 if (virial or stress) else 0, None, cut, create_graph=create_graph)
         out = [energy]
         if forces:
             f = torch.empty_like(gpos)
@@ -245,7 +290,7 @@ class ShardedEnergyModel(nn.Module):
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, halo, forces: bool = False, virial: bool = False,
-                stress: bool = False, skin: float = 0.0, neighbors=None):
+                stress: bool = False, skin: float = 0.0, neighbors=None, create_graph: bool = False):
         """x [n, in_dim], pos [n,3] fp32: the particles this rank owns (``halo.owner_of``), caller order.  Every rank of
         the halo's group calls with the same flags.  -> the 0-d TOTAL energy (all-reduced), then whichever of forces
         [n,3] (= -dE_total/dpos of the owned particles, caller order), virial W [3,3] (= -dE_total/deps, all-reduced,
@@ -265,8 +310,13 @@ class ShardedEnergyModel(nn.Module):
         and graph built at the list's ``r + skin`` once, then positions sent along the stored entries and the stored
         edges pruned and split on the device while no particle on any rank has moved half the skin -- for any model,
         enveloped or not; ``r`` and ``halo`` must be the list's and ``skin`` stays 0 (ValueError otherwise).  May raise
-        ``OwnershipChanged`` (on every rank) when the list has to rebuild."""
+        ``OwnershipChanged`` (on every rank) when the list has to rebuild.
+
+        ``create_graph=True`` raises ``NotImplementedError``: the ghost refresh (``Halo.refresh``) is first order."""
         from .sharding import GridHalo, all_reduce_sum
+        if create_graph:
+            raise NotImplementedError("create_graph=True on the sharded path: the ghost refresh (Halo.refresh) is first order, "
+                                      "its backward has no backward; train on forces with PeriodicEnergyModel")
         if stress and not (isinstance(halo, GridHalo) and halo.periodic == 7):
             raise ValueError("stress is defined for a GridHalo periodic on all three axes; use virial=True otherwise")
         cut = _cutoff_kw(self.net, r)

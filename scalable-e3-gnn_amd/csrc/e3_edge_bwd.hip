@@ -229,6 +229,125 @@ __global__ __launch_bounds__(256) void gate_blocks_bwd_kernel(const float* __res
   }
 }
 
+// Backward of gate_blocks_bwd_kernel (include/e3gnn.h, e3_gate_blocks_backward2): ct = the cotangent of gin.  Same thread
+// mapping, one thread per INPUT column; a scalar / gated thread also writes the output-gradient cotangent of its own column.
+//   silu'' = sig' (2 + s (1 - 2 sig)),  sig' = sig (1 - sig),  sig'' = sig' (1 - 2 sig)
+__global__ __launch_bounds__(256) void gate_blocks_bwd2_kernel(const float* __restrict__ in, int64_t ld_in,
+                                                               const float* __restrict__ gout, int64_t ld_go,
+                                                               const float* __restrict__ ct, int64_t ld_ct,
+                                                               float* __restrict__ cgo, int64_t ld_cgo,
+                                                               float* __restrict__ cin, int64_t ld_cin, int64_t B, int ns,
+                                                               int ngates, int W, GateBlocksB gb) {
+  const int WI = W + ngates;  // input width: [ns | ngates | wide]
+  const int64_t total = B * (int64_t)WI;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = t / WI;
+    const int c = (int)(t - row * WI);
+    const float* x = in + row * ld_in;
+    const float* go = gout + row * ld_go;
+    const float* cr = ct + row * ld_ct;
+    float vin;
+    if (c < ns) {
+      const float s = x[c], sg = sigm(s), dsg = sg * (1.f - sg);
+      if (cgo) cgo[row * ld_cgo + c] = cr[c] * sg * (1.f + s * (1.f - sg));
+      vin = cr[c] * go[c] * dsg * (2.f + s * (1.f - 2.f * sg));
+    } else if (c < ns + ngates) {
+      int k = c - ns, bi = 0, col0 = ns;  // col0: first OUTPUT column of block bi
+      while (k >= gb.mul[bi]) { k -= gb.mul[bi]; col0 += gb.mul[bi] * (2 * gb.l[bi] + 1); ++bi; }
+      const int w = 2 * gb.l[bi] + 1;
+      float acc_c = 0.f, acc_v = 0.f;
+      for (int m = 0; m < w; ++m) {
+        const float g = go[col0 + k * w + m];
+        acc_c += cr[ngates + col0 + k * w + m] * g;
+        acc_v += x[ngates + col0 + k * w + m] * g;
+      }
+      const float sg = sigm(x[c]), dsg = sg * (1.f - sg);
+      vin = dsg * acc_c + dsg * (1.f - 2.f * sg) * cr[c] * acc_v;
+    } else {
+      const int oc = c - ngates;  // output column
+      int rem = oc - ns, g0 = 0, bi = 0;
+      while (rem >= gb.mul[bi] * (2 * gb.l[bi] + 1)) { rem -= gb.mul[bi] * (2 * gb.l[bi] + 1); g0 += gb.mul[bi]; ++bi; }
+      const int gc = ns + g0 + rem / (2 * gb.l[bi] + 1);  // the gate column of this channel
+      const float sg = sigm(x[gc]), dsg = sg * (1.f - sg);
+      if (cgo) cgo[row * ld_cgo + oc] = sg * cr[c] + dsg * cr[gc] * x[c];
+      vin = dsg * cr[gc] * go[oc];
+    }
+    if (cin) cin[row * ld_cin + c] = vin;
+  }
+}
+
+// Tangent of the edge geometry along a displacement field v [N,3] (include/e3gnn.h, e3_edge_geometry_jvp): the backward above
+// is linear in (gY, gd, gA), so this is its backward w.r.t. those three.  t = v[src] - v[dst];  du = (t - u (u . t)) / d;
+//   dY1 = sqrt3 du,  dY2 = sqrt5 (db/du) du  (b as above),  dd = u . t,  dA_i = (1 / deg_i) sum over the row of dY_e.
+// One wave per row, lanes over its edges; dA: per-lane sums in edge order, then a fixed butterfly -- no atomics.
+template <int LMAX, int PBC>
+__global__ __launch_bounds__(256) void edge_geometry_jvp_kernel(const float4* __restrict__ pos4,
+                                                                const int32_t* __restrict__ rowptr,
+                                                                const int32_t* __restrict__ src, int64_t N,
+                                                                const float* __restrict__ v, float* __restrict__ dY,
+                                                                float* __restrict__ dd, float* __restrict__ dA,
+                                                                const typename PbcArg<PBC>::type box) {
+  constexpr int NY = (LMAX + 1) * (LMAX + 1);
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t i = wave0; i < N; i += nw) {
+    const int b = rowptr[i], e = rowptr[i + 1];
+    if (b == e) {
+      if (dA && lane < NY) dA[i * NY + lane] = 0.f;
+      continue;
+    }
+    const float4 pi = pos4[i];
+    const float vix = v[i * 3 + 0], viy = v[i * 3 + 1], viz = v[i * 3 + 2];
+    float s[NY];
+#pragma unroll
+    for (int k = 0; k < NY; ++k) s[k] = 0.f;
+    for (int q = b + lane; q < e; q += 64) {
+      const int j = src[q];
+      const float4 pj = pos4[j];
+      float rx, ry, rz;
+      edge_rel<PBC>(pj, pi, box, rx, ry, rz);
+      const float d = sqrtf(rx * rx + ry * ry + rz * rz);
+      float o[NY], ddv = 0.f;
+#pragma unroll
+      for (int k = 0; k < NY; ++k) o[k] = 0.f;
+      if (d > 0.f) {
+        const float inv = 1.0f / d;
+        const float x = rx * inv, y = ry * inv, z = rz * inv;
+        const float tx = v[(int64_t)j * 3 + 0] - vix, ty = v[(int64_t)j * 3 + 1] - viy, tz = v[(int64_t)j * 3 + 2] - viz;
+        ddv = x * tx + y * ty + z * tz;
+        const float ux = (tx - x * ddv) * inv, uy = (ty - y * ddv) * inv, uz = (tz - z * ddv) * inv;
+        o[1] = kS3 * ux; o[2] = kS3 * uy; o[3] = kS3 * uz;
+        if constexpr (LMAX == 2) {
+          o[4] = kS5 * kS3 * (y * ux + x * uy);
+          o[5] = kS5 * kS3 * (z * uy + y * uz);
+          o[6] = kS5 * (2.f * z * uz - x * ux - y * uy);
+          o[7] = kS5 * kS3 * (x * uz + z * ux);
+          o[8] = kS5 * kS3 * (x * ux - y * uy);
+        }
+      }
+      if (dY) {
+#pragma unroll
+        for (int k = 0; k < NY; ++k) dY[(int64_t)q * NY + k] = o[k];
+      }
+      if (dd) dd[q] = ddv;
+#pragma unroll
+      for (int k = 1; k < NY; ++k) s[k] += o[k];
+    }
+    if (dA) {
+      const float invdeg = 1.0f / (float)(e - b);
+#pragma unroll
+      for (int k = 1; k < NY; ++k)
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o);
+      if (lane == 0) {
+        dA[i * NY] = 0.f;
+#pragma unroll
+        for (int k = 1; k < NY; ++k) dA[i * NY + k] = s[k] * invdeg;
+      }
+    }
+  }
+}
+
 // agg[i] = sum over the row of msg[e]  ->  gmsg[e] = gagg[dst(e)]
 __global__ __launch_bounds__(256) void segment_sum_bwd_kernel(const float* __restrict__ gagg, int64_t ld_ga,
                                                               const int32_t* __restrict__ rowptr, int64_t N, int D,
@@ -290,7 +409,70 @@ static int edge_geometry_backward(const float* pos4, const int32_t* rowptr, cons
                                              g_strain, gpart, stream);
 }
 
+// one periodicity mode (box: the mode's kernel argument, validated by the caller)
+template <int PBC>
+static int edge_geometry_jvp(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                             const float* v, float* d_edge_y, float* d_edge_d, float* d_node_a,
+                             const typename PbcArg<PBC>::type& b, void* stream) {
+  if (N < 0 || (lmax != 1 && lmax != 2)) return E3_ERR_INVALID_ARG;
+  if (N == 0 || (!d_edge_y && !d_edge_d && !d_node_a)) return E3_OK;
+  if (!pos4 || !rowptr || !src || !v) return E3_ERR_INVALID_ARG;
+  auto kern = lmax == 1 ? edge_geometry_jvp_kernel<1, PBC> : edge_geometry_jvp_kernel<2, PBC>;
+  hipLaunchKernelGGL(kern, dim3(wave_grid_b(N)), dim3(256), 0, (hipStream_t)stream, (const float4*)pos4, rowptr, src, N, v,
+                     d_edge_y, d_edge_d, d_node_a, b);
+  E3_HIP_CHECK(hipGetLastError());
+  return E3_OK;
+}
+
 extern "C" {
+
+int e3_edge_geometry_jvp(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax, const float* v,
+                         float* d_edge_y, float* d_edge_d, float* d_node_a, void* stream) {
+  return edge_geometry_jvp<kOpen>(pos4, rowptr, src, N, lmax, v, d_edge_y, d_edge_d, d_node_a, make_box(nullptr), stream);
+}
+
+int e3_edge_geometry_jvp_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                             const float box[3], const float* v, float* d_edge_y, float* d_edge_d, float* d_node_a,
+                             void* stream) {
+  if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_jvp<kBox>(pos4, rowptr, src, N, lmax, v, d_edge_y, d_edge_d, d_node_a, make_box(box), stream);
+}
+
+int e3_edge_geometry_jvp_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                              const float cell[9], const float* v, float* d_edge_y, float* d_edge_d, float* d_node_a,
+                              void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_jvp<kCell>(pos4, rowptr, src, N, lmax, v, d_edge_y, d_edge_d, d_node_a, c, stream);
+}
+
+int e3_gate_blocks_backward2(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, const float* c,
+                             int64_t ld_c, float* cot_g_out, int64_t ld_cgout, float* cot_in, int64_t ld_cin, int64_t B,
+                             int ns, int nblocks, const int32_t* ls, const int32_t* muls, void* stream) {
+  if (B < 0 || ns < 0 || nblocks < 0 || nblocks > 8 || (nblocks > 0 && (!ls || !muls))) return E3_ERR_INVALID_ARG;
+  GateBlocksB gb;
+  gb.nblocks = nblocks;
+  int ngates = 0, wide = 0;
+  for (int i = 0; i < 8; ++i) { gb.l[i] = 0; gb.mul[i] = 1 << 30; }
+  for (int i = 0; i < nblocks; ++i) {
+    if (ls[i] < 0 || ls[i] > 2 || muls[i] < 0) return E3_ERR_INVALID_ARG;
+    gb.l[i] = ls[i]; gb.mul[i] = muls[i];
+    ngates += muls[i];
+    wide += muls[i] * (2 * ls[i] + 1);
+  }
+  const int W = ns + wide;
+  if (ld_in < W + ngates || ld_gout < W || ld_c < W + ngates || (cot_g_out && ld_cgout < W) ||
+      (cot_in && ld_cin < W + ngates))
+    return E3_ERR_INVALID_ARG;
+  if (B == 0 || W == 0 || (!cot_g_out && !cot_in)) return E3_OK;
+  if (!in || !g_out || !c) return E3_ERR_INVALID_ARG;
+  const int64_t total = B * (int64_t)(W + ngates);
+  const int grid = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(gate_blocks_bwd2_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, ld_in, g_out, ld_gout, c,
+                     ld_c, cot_g_out, ld_cgout, cot_in, ld_cin, B, ns, ngates, W, gb);
+  E3_HIP_CHECK(hipGetLastError());
+  return E3_OK;
+}
 
 int e3_edge_geometry_backward(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                               const float* g_edge_y, const float* g_edge_d, const float* g_node_a, float* g_pos,

@@ -45,6 +45,29 @@ __global__ __launch_bounds__(256) void cutoff_envelope_bwd_kernel(const float* _
   }
 }
 
+// backward of the backward, c = the cotangent of g_d:  cot_g_w = c du/dd,  cot_d = c g_w d2u/dd2,
+// d2u/dd2 = -(p (p+1) (p+2) / 2) x^(p-2) (1 - x) ((p-1) (1 - x) - 2 x) / r_c^2   (x^0 = 1: p = 2 has no x factor)
+__global__ __launch_bounds__(256) void cutoff_envelope_bwd2_kernel(const float* __restrict__ edge_d,
+                                                                   const float* __restrict__ g_w,
+                                                                   const float* __restrict__ cot, int64_t E, float r_c,
+                                                                   float inv_rc, int p, float* __restrict__ cot_g_w,
+                                                                   float* __restrict__ cot_d) {
+  const float c = -(float)(p * (p + 1) * (p + 2) / 2);
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < E; t += (int64_t)gridDim.x * blockDim.x) {
+    const float d = edge_d[t];
+    const float x = envelope_x(d, inv_rc);
+    float xq = 1.0f;  // x^(p-2)
+    for (int k = 2; k < p; ++k) xq *= x;
+    const float t1 = 1.0f - x;
+    const float du = (c * (xq * x)) * (t1 * t1) * inv_rc;
+    const float d2u = (c * xq) * (t1 * ((float)(p - 1) * t1 - 2.0f * x)) * (inv_rc * inv_rc);
+    const bool out = d >= r_c;
+    const float cv = cot[t];
+    if (cot_g_w) cot_g_w[t] = out ? 0.0f : cv * du;
+    if (cot_d) cot_d[t] = out ? 0.0f : (cv * g_w[t]) * d2u;
+  }
+}
+
 // ---- 4-byte / 16-byte column groups ---------------------------------------------------------------------------------
 template <typename V> __device__ __forceinline__ V vzero();
 template <> __device__ __forceinline__ float vzero<float>() { return 0.f; }
@@ -250,6 +273,18 @@ int e3_cutoff_envelope_backward(const float* edge_d, const float* g_w, int64_t E
   if (!edge_d || !g_w || !g_d) return E3_ERR_INVALID_ARG;
   hipLaunchKernelGGL(cutoff_envelope_bwd_kernel, dim3(flat_grid(E)), dim3(256), 0, (hipStream_t)stream, edge_d, g_w, E, r_c,
                      inv, p, g_d);
+  E3_HIP_CHECK(hipGetLastError());
+  return E3_OK;
+}
+
+int e3_cutoff_envelope_backward2(const float* edge_d, const float* g_w, const float* c, int64_t E, float r_c, int p,
+                                 float* cot_g_w, float* cot_d, void* stream) {
+  float inv;
+  if (E < 0 || !envelope_args(r_c, p, &inv) || !(inv * inv < 3.0e38f)) return E3_ERR_INVALID_ARG;
+  if (E == 0 || (!cot_g_w && !cot_d)) return E3_OK;
+  if (!edge_d || !c || (cot_d && !g_w)) return E3_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(cutoff_envelope_bwd2_kernel, dim3(flat_grid(E)), dim3(256), 0, (hipStream_t)stream, edge_d, g_w, c, E,
+                     r_c, inv, p, cot_g_w, cot_d);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }

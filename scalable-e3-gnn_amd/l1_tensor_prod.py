@@ -65,15 +65,27 @@ class _L1TPFunction(torch.autograd.Function):
     def backward(ctx, grad_out: Tensor):
         mod = ctx.mod
         in1, in2, *saved_w = ctx.saved_tensors
-        it = iter(saved_w)
-        ws = [next(it) if present else None for present in ctx.wpresent]
-        need_in1, need_in2 = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        need_w = any(ctx.needs_input_grad[3:])
-        g_in1, g_in2, g_w = mod._hip_backward(in1, in2, grad_out.contiguous(), need_in1, need_in2, need_w, weights=ws)
-        gw_out = []
-        for i, c in enumerate(_CLS):
-            gw_out.append(g_w[c] if (ctx.needs_input_grad[3 + i] and g_w is not None) else None)
-        return (None, g_in1, g_in2, *gw_out)
+        wpresent = ctx.wpresent
+        slots = tuple(i for i, present in enumerate(wpresent) if present)
+
+        def first(in1, in2, grad_out, weights, needs):
+            """-> (g_in1, g_in2, one g_W per PRESENT weight); needs: (in1, in2, the present weights)"""
+            it = iter(weights)
+            ws = [next(it) if present else None for present in wpresent]
+            g_in1, g_in2, g_w = mod._hip_backward(in1, in2, grad_out, needs[0], needs[1], any(needs[2:]), weights=ws)
+            gw_out = [g_w[_CLS[i]] if (n and g_w is not None) else None for i, n in zip(slots, needs[2:])]
+            return (g_in1, g_in2, *gw_out)
+
+        needs = (ctx.needs_input_grad[1], ctx.needs_input_grad[2]) + tuple(ctx.needs_input_grad[3 + i] for i in slots)
+        grad_out = grad_out.contiguous()
+        if torch.is_grad_enabled():  # create_graph: the backward is differentiated (second derivatives), on the general plan
+            from .tensor_product import _TPBackwardFn
+            out = _TPBackwardFn.apply(first, mod._fused_plan(), mod._norms() + [None, None], slots, needs, in1, in2,
+                                      grad_out, *saved_w)
+        else:
+            out = first(in1, in2, grad_out, saved_w, needs)
+        it = iter(out[2:])
+        return (None, out[0], out[1], *[next(it) if present else None for present in wpresent])
 
 
 class L1TensorProduct(Module):

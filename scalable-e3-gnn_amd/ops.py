@@ -1,10 +1,15 @@
 """Edge / node stages of the SEGNN forward (host side of ``e3_edge_geometry``, ``e3_gather_concat``,
 ``e3_gate``, ``e3_segment_sum`` and their ``*_backward`` in include/e3gnn.h).  Builder-defined,
 fp32.  Every op is differentiable (torch.autograd.Function over the HIP backward kernels): with the tensor products'
-own backward a whole SEGNN layer has parameter gradients and forces.  ROCm tensors only; no CPU path."""
+own backward a whole SEGNN layer has parameter gradients and forces.  With grad mode on inside a backward
+(``create_graph=True``) the same backward call runs as a second Function (``_*BackwardFn``) that has a backward of its own --
+the linear stages by composition (gather <-> its backward, segment sum <-> its backward), the gate, the edge geometry and the
+envelope on ``e3_gate_blocks_backward2``, ``e3_edge_geometry_jvp`` and ``e3_cutoff_envelope_backward2`` -- so a loss on the
+forces has parameter gradients; those Functions are once differentiable.  ROCm tensors only; no CPU path."""
 from __future__ import annotations
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .radius_graph import RadiusGraph
@@ -89,27 +94,77 @@ class _EdgeGeometryFn(torch.autograd.Function):
     def backward(ctx, gY, gd, gA):
         pos4, strain = ctx.saved_tensors
         g = ctx.g
-        N = pos4.shape[0]
-        gpos = torch.empty((N, 3), dtype=torch.float32, device=pos4.device)
-        c = lambda t: t.contiguous() if t is not None else None
-        gY, gd, gA = c(gY), c(gd), c(gA)
-        p = lambda t: t.data_ptr() if t is not None else None
-        gstrain = None
-        if g.num_edges == 0:  # no edge: the outputs do not depend on pos or strain
-            return gpos.zero_(), (torch.zeros_like(strain) if strain is not None else None), None, None, None
-        with torch.cuda.device(pos4.device):
-            head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, ctx.lmax)
+        if torch.is_grad_enabled():  # create_graph: the backward itself is differentiated (in gY, gd, gA; not in pos)
             if strain is not None:
-                gstrain = torch.empty_like(strain)
-                ws = torch.empty(max(1, _lib.load().e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
-                                 device=pos4.device)
-                name, pbc = g.entry("e3_edge_geometry_backward_strained", strained=True)
-                _lib.call(name, *head, *pbc, strain.data_ptr(), p(ctx.structure), strain.shape[0], p(gY), p(gd), p(gA),
-                          gpos.data_ptr(), gstrain.data_ptr(), ws.data_ptr(), ws.numel(), _stream(pos4))
-            else:
-                name, pbc = g.entry("e3_edge_geometry_backward")
-                _lib.call(name, *head, *pbc, p(gY), p(gd), p(gA), gpos.data_ptr(), _stream(pos4))
+                raise NotImplementedError("second derivatives through a strained edge geometry (virial / stress under "
+                                          "create_graph): the strained geometry has no tangent kernel")
+            return _EdgeGeometryBackwardFn.apply(pos4, gY, gd, gA, g, ctx.lmax), None, None, None, None
+        gpos, gstrain = _edge_geometry_backward_raw(pos4, strain, g, ctx.lmax, ctx.structure, gY, gd, gA)
         return gpos, gstrain, None, None, None
+
+
+def _edge_geometry_backward_raw(pos4, strain, g, lmax, structure, gY, gd, gA):
+    """-> (g_pos [N,3], g_strain | None): e3_edge_geometry_backward, or its strained form with a strain"""
+    N = pos4.shape[0]
+    gpos = torch.empty((N, 3), dtype=torch.float32, device=pos4.device)
+    c = lambda t: t.contiguous() if t is not None else None
+    gY, gd, gA = c(gY), c(gd), c(gA)
+    p = lambda t: t.data_ptr() if t is not None else None
+    gstrain = None
+    if g.num_edges == 0:  # no edge: the outputs do not depend on pos or strain
+        return gpos.zero_(), (torch.zeros_like(strain) if strain is not None else None)
+    with torch.cuda.device(pos4.device):
+        head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax)
+        if strain is not None:
+            gstrain = torch.empty_like(strain)
+            ws = torch.empty(max(1, _lib.load().e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
+                             device=pos4.device)
+            name, pbc = g.entry("e3_edge_geometry_backward_strained", strained=True)
+            _lib.call(name, *head, *pbc, strain.data_ptr(), p(structure), strain.shape[0], p(gY), p(gd), p(gA),
+                      gpos.data_ptr(), gstrain.data_ptr(), ws.data_ptr(), ws.numel(), _stream(pos4))
+        else:
+            name, pbc = g.entry("e3_edge_geometry_backward")
+            _lib.call(name, *head, *pbc, p(gY), p(gd), p(gA), gpos.data_ptr(), _stream(pos4))
+    return gpos, gstrain
+
+
+def _edge_geometry_jvp_raw(pos4, g, lmax, v, want_y=True, want_d=True, want_a=True):
+    """Tangent of (Y, d, A) along the displacement field v [N,3] (e3_edge_geometry_jvp) -> dY | None, dd | None, dA | None."""
+    N, E, dev = pos4.shape[0], g.num_edges, pos4.device
+    ny = (lmax + 1) ** 2
+    if E == 0:  # nothing to launch on: no output depends on the positions
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        return (z(0, ny) if want_y else None), (z(0) if want_d else None), (z(N, ny) if want_a else None)
+    dY = torch.empty((E, ny), dtype=torch.float32, device=dev) if want_y else None
+    dd = torch.empty(E, dtype=torch.float32, device=dev) if want_d else None
+    dA = torch.empty((N, ny), dtype=torch.float32, device=dev) if want_a else None
+    v = v.to(torch.float32).contiguous()
+    p = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        name, pbc = g.entry("e3_edge_geometry_jvp")
+        _lib.call(name, pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, *pbc, v.data_ptr(), p(dY), p(dd),
+                  p(dA), _stream(pos4))
+    return dY, dd, dA
+
+
+class _EdgeGeometryBackwardFn(torch.autograd.Function):
+    """The unstrained backward of ``_EdgeGeometryFn`` as a differentiable op of (gY, gd, gA): it is linear in them, so its
+    backward is the tangent of the forward along the cotangent of g_pos (``e3_edge_geometry_jvp``).  The derivative w.r.t.
+    the positions themselves (the Hessian of Y, d, A in r) is not implemented: ``pos4`` gets no gradient from here, which a
+    parameter gradient of a loss on energies and forces never needs."""
+
+    @staticmethod
+    def forward(ctx, pos4, gY, gd, gA, g, lmax):
+        ctx.g, ctx.lmax = g, lmax
+        ctx.save_for_backward(pos4)
+        return _edge_geometry_backward_raw(pos4, None, g, lmax, None, gY, gd, gA)[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        (pos4,) = ctx.saved_tensors
+        dY, dd, dA = _edge_geometry_jvp_raw(pos4, ctx.g, ctx.lmax, v, *ctx.needs_input_grad[1:4])
+        return None, dY, dd, dA, None, None
 
 
 def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int = 1, pos: torch.Tensor | None = None,
@@ -121,6 +176,12 @@ def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int
     differentiable w.r.t. it (forces = -dE/dpos); otherwise the graph's own ``pos4`` is used.  A periodic graph
     (``g.box``, or a general cell ``g.cell``) takes the minimum image of every edge vector, so ``pos`` may be the
     unwrapped coordinates (moved by whole periods / lattice vectors).
+
+    Second derivatives: under ``create_graph=True`` the gradient w.r.t. ``pos`` is itself differentiable w.r.t. the
+    gradients of Y, d and A that produced it (``e3_edge_geometry_jvp``) -- what the parameter gradient of a loss on the forces
+    needs -- but NOT w.r.t. ``pos``: the Hessian of Y, d, A in the edge vector is not implemented, and differentiating that
+    gradient once more w.r.t. ``pos`` gives only the part that flows through those three gradients, without the Hessian
+    term and without an error.  Do not take d(forces)/d(pos) from it.  With a ``strain`` it raises ``NotImplementedError``.
 
     ``strain`` [S,3,3] (or [3,3]: one structure), fp32 on the device, and ``structure`` [N] integer structure id of every
     row (graph order; None = every row is structure 0): every edge vector r of structure s (the structure of its dst row)
@@ -161,20 +222,42 @@ class _GatherConcatFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gm):
         g, D, nx = ctx.g, ctx.D, ctx.nx
-        gm = gm.contiguous()
-        N = g.rowptr.numel() - 1
-        gh = torch.empty((N, D), dtype=torch.float32, device=gm.device)
-        gx = torch.empty((g.num_edges, nx), dtype=torch.float32, device=gm.device) if nx else None
-        if g.num_edges == 0:  # no edge: nothing reaches h (an empty tensor has no address to hand to the library)
-            return gh.zero_(), gx, None
-        with torch.cuda.device(gm.device):
-            _lib.check(_lib.load().e3_gather_concat_backward(gm.data_ptr(), gm.stride(0), D, g.rowptr.data_ptr(),
-                                                             g.src.data_ptr(), N, nx, gh.data_ptr(), gh.stride(0),
-                                                             gx.data_ptr() if gx is not None else None, _stream(gm)),
-                       "e3_gather_concat_backward")
-        if gx is not None and nx == 1:
-            gx = gx  # [E,1]; reshaped to the caller's shape by autograd below
+        if torch.is_grad_enabled():  # create_graph: the (linear) backward is differentiated in gm
+            gh, gx = _GatherConcatBackwardFn.apply(gm, g, D, nx)
+            return gh, gx, None
+        gh, gx = _gather_concat_backward_raw(gm, g, D, nx)
         return gh, gx, None
+
+
+def _gather_concat_backward_raw(gm, g, D, nx):
+    """gm [E, 2D+nx] -> (g_h [N,D], g_extra [E,nx] | None): e3_gather_concat_backward"""
+    gm = gm.contiguous()
+    N = g.rowptr.numel() - 1
+    gh = torch.empty((N, D), dtype=torch.float32, device=gm.device)
+    gx = torch.empty((g.num_edges, nx), dtype=torch.float32, device=gm.device) if nx else None
+    if g.num_edges == 0:  # no edge: nothing reaches h (an empty tensor has no address to hand to the library)
+        return gh.zero_(), gx
+    with torch.cuda.device(gm.device):
+        _lib.check(_lib.load().e3_gather_concat_backward(gm.data_ptr(), gm.stride(0), D, g.rowptr.data_ptr(),
+                                                         g.src.data_ptr(), N, nx, gh.data_ptr(), gh.stride(0),
+                                                         gx.data_ptr() if gx is not None else None, _stream(gm)),
+                   "e3_gather_concat_backward")
+    return gh, gx  # gx [E, nx]: the shape _GatherConcatFn was given
+
+
+class _GatherConcatBackwardFn(torch.autograd.Function):
+    """gm -> (g_h, g_extra | None), linear: its backward is the forward gather on the cotangents,
+    cot(gm) = [c_gh[dst] | c_gh[src] | c_gx]."""
+
+    @staticmethod
+    def forward(ctx, gm, g, D, nx):
+        ctx.g, ctx.nx = g, nx
+        return _gather_concat_backward_raw(gm, g, D, nx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, c_gh, c_gx):
+        return _gather_concat_raw(c_gh.contiguous(), ctx.g, c_gx if ctx.nx else None), None, None, None
 
 
 def _extra_columns(extra, E):
@@ -226,18 +309,63 @@ class _GateBlocksFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, go):
-        import ctypes
         (x,) = ctx.saved_tensors
+        if torch.is_grad_enabled():  # create_graph: the backward is differentiated in x and go
+            return _GateBlocksBackwardFn.apply(x, go, ctx.ns, ctx.blocks), None, None
+        return _gate_blocks_backward_raw(x, go, ctx.ns, ctx.blocks), None, None
+
+
+def _gate_blocks_backward_raw(x, go, ns, blocks):
+    import ctypes
+    go = go.contiguous()
+    gi = torch.empty_like(x)
+    ls = (ctypes.c_int32 * len(blocks))(*[l for l, _ in blocks])
+    ms = (ctypes.c_int32 * len(blocks))(*[m for _, m in blocks])
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().e3_gate_blocks_backward(x.data_ptr(), x.stride(0), go.data_ptr(), go.stride(0),
+                                                       gi.data_ptr(), gi.stride(0), x.shape[0], ns, len(blocks),
+                                                       ls, ms, _stream(x)), "e3_gate_blocks_backward")
+    return gi
+
+
+def _gate_blocks_backward2_raw(x, go, c, ns, blocks, want_go=True, want_x=True):
+    """-> (cot(go) | None, cot(x) | None) for the cotangent ``c`` of the gate backward's g_in, in one launch
+    (e3_gate_blocks_backward2).  Row strides may exceed the widths (``x``, ``go``, ``c``: last dimension contiguous)."""
+    import ctypes
+    B = x.shape[0]
+    wide = sum(m * (2 * l + 1) for l, m in blocks)
+    ng = sum(m for _, m in blocks)
+    cgo = torch.empty((B, ns + wide), dtype=torch.float32, device=x.device) if want_go else None
+    cx = torch.empty((B, ns + ng + wide), dtype=torch.float32, device=x.device) if want_x else None
+    ls = (ctypes.c_int32 * len(blocks))(*[l for l, _ in blocks])
+    ms = (ctypes.c_int32 * len(blocks))(*[m for _, m in blocks])
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().e3_gate_blocks_backward2(
+            x.data_ptr(), x.stride(0), go.data_ptr(), go.stride(0), c.data_ptr(), c.stride(0),
+            cgo.data_ptr() if want_go else None, cgo.stride(0) if want_go else 0,
+            cx.data_ptr() if want_x else None, cx.stride(0) if want_x else 0, B, ns, len(blocks), ls, ms, _stream(x)),
+            "e3_gate_blocks_backward2")
+    return cgo, cx
+
+
+class _GateBlocksBackwardFn(torch.autograd.Function):
+    """(x, go) -> g_in = e3_gate_blocks_backward; its backward is e3_gate_blocks_backward2 (silu'', sigmoid'')."""
+
+    @staticmethod
+    def forward(ctx, x, go, ns, blocks):
+        ctx.ns, ctx.blocks = ns, blocks
         go = go.contiguous()
-        gi = torch.empty_like(x)
-        blocks = ctx.blocks
-        ls = (ctypes.c_int32 * len(blocks))(*[l for l, _ in blocks])
-        ms = (ctypes.c_int32 * len(blocks))(*[m for _, m in blocks])
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().e3_gate_blocks_backward(x.data_ptr(), x.stride(0), go.data_ptr(), go.stride(0),
-                                                           gi.data_ptr(), gi.stride(0), x.shape[0], ctx.ns, len(blocks),
-                                                           ls, ms, _stream(x)), "e3_gate_blocks_backward")
-        return gi, None, None
+        ctx.save_for_backward(x, go)
+        return _gate_blocks_backward_raw(x, go, ns, blocks)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, c):
+        x, go = ctx.saved_tensors
+        if c.stride(-1) != 1:
+            c = c.contiguous()
+        cgo, cx = _gate_blocks_backward2_raw(x, go, c, ctx.ns, ctx.blocks, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return cx, cgo, None, None
 
 
 def gate(x: torch.Tensor, ns: int, nv: int) -> torch.Tensor:
@@ -264,17 +392,36 @@ class _SegmentSumFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ga):
-        g = ctx.g
-        ga = ga.contiguous()
-        N, D = ga.shape
-        gm = torch.empty((g.num_edges, D), dtype=torch.float32, device=ga.device)
-        if g.num_edges == 0:
-            return gm, None
-        with torch.cuda.device(ga.device):
-            _lib.check(_lib.load().e3_segment_sum_backward(ga.data_ptr(), ga.stride(0), g.rowptr.data_ptr(), N, D,
-                                                           gm.data_ptr(), max(gm.stride(0), D), _stream(ga)),
-                       "e3_segment_sum_backward")
-        return gm, None
+        if torch.is_grad_enabled():  # create_graph: the (linear) backward is differentiated in ga
+            return _SegmentSumBackwardFn.apply(ga, ctx.g), None
+        return _segment_sum_backward_raw(ga, ctx.g), None
+
+
+def _segment_sum_backward_raw(ga, g):
+    ga = ga.contiguous()
+    N, D = ga.shape
+    gm = torch.empty((g.num_edges, D), dtype=torch.float32, device=ga.device)
+    if g.num_edges == 0:
+        return gm
+    with torch.cuda.device(ga.device):
+        _lib.check(_lib.load().e3_segment_sum_backward(ga.data_ptr(), ga.stride(0), g.rowptr.data_ptr(), N, D,
+                                                       gm.data_ptr(), max(gm.stride(0), D), _stream(ga)),
+                   "e3_segment_sum_backward")
+    return gm
+
+
+class _SegmentSumBackwardFn(torch.autograd.Function):
+    """ga -> g_msg[e] = ga[dst(e)], linear: its backward is the segment sum of the cotangent."""
+
+    @staticmethod
+    def forward(ctx, ga, g):
+        ctx.g = g
+        return _segment_sum_backward_raw(ga, g)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, c_gm):
+        return _segment_sum_raw(c_gm, ctx.g), None
 
 
 def _segment_sum_raw(msg, g):
@@ -314,17 +461,53 @@ class _SegmentSumWeightedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ga):
         msg, w = ctx.saved_tensors
-        g = ctx.g
-        ga = ga.contiguous()
-        N, D = ga.shape
-        gm = torch.empty((g.num_edges, D), dtype=torch.float32, device=ga.device)
-        gw = torch.empty(g.num_edges, dtype=torch.float32, device=ga.device) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(ga.device):
-            _lib.check(_lib.load().e3_segment_sum_weighted_backward(
-                ga.data_ptr(), ga.stride(0), msg.data_ptr(), msg.stride(0), w.data_ptr(), g.rowptr.data_ptr(), N, D,
-                gm.data_ptr(), max(gm.stride(0), D), gw.data_ptr() if gw is not None else None, _stream(ga)),
-                "e3_segment_sum_weighted_backward")
+        if torch.is_grad_enabled():  # create_graph: the (bilinear) backward is differentiated in ga, msg and w
+            gm, gw = _SegmentSumWeightedBackwardFn.apply(ga, msg, w, ctx.g, ctx.needs_input_grad[1])
+            return gm, gw, None
+        gm, gw = _segment_sum_weighted_backward_raw(ga, msg, w, ctx.g, ctx.needs_input_grad[1])
         return gm, gw, None
+
+
+def _segment_sum_weighted_backward_raw(ga, msg, w, g, need_w):
+    """-> (g_msg[e] = w[e] ga[dst(e)], g_w[e] = <msg[e], ga[dst(e)]> | None): e3_segment_sum_weighted_backward"""
+    ga = ga.contiguous()
+    N, D = ga.shape
+    gm = torch.empty((g.num_edges, D), dtype=torch.float32, device=ga.device)
+    gw = torch.empty(g.num_edges, dtype=torch.float32, device=ga.device) if need_w else None
+    with torch.cuda.device(ga.device):
+        _lib.check(_lib.load().e3_segment_sum_weighted_backward(
+            ga.data_ptr(), ga.stride(0), msg.data_ptr(), msg.stride(0), w.data_ptr(), g.rowptr.data_ptr(), N, D,
+            gm.data_ptr(), max(gm.stride(0), D), gw.data_ptr() if gw is not None else None, _stream(ga)),
+            "e3_segment_sum_weighted_backward")
+    return gm, gw
+
+
+class _SegmentSumWeightedBackwardFn(torch.autograd.Function):
+    """(ga, msg, w) -> (g_msg, g_w | None), bilinear.  For the cotangents (c_gm, c_gw):
+    cot(ga) = sum_e w_e c_gm_e + sum_e c_gw_e msg_e (two weighted sums), and (cot(msg), cot(w)) = (c_gw_e ga[dst],
+    <c_gm_e, ga[dst]>) is ONE e3_segment_sum_weighted_backward call with msg := c_gm and w := c_gw."""
+
+    @staticmethod
+    def forward(ctx, ga, msg, w, g, need_w):
+        ctx.g, ctx.need_w = g, need_w
+        ga = ga.contiguous()
+        ctx.save_for_backward(ga, msg, w)
+        return _segment_sum_weighted_backward_raw(ga, msg, w, g, need_w)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, c_gm, c_gw):
+        ga, msg, w = ctx.saved_tensors
+        g = ctx.g
+        c_gm = c_gm.contiguous()
+        cot_ga = _segment_sum_weighted_raw(c_gm, w, g)
+        if ctx.need_w:
+            c_gw = c_gw.contiguous()
+            cot_ga = cot_ga + _segment_sum_weighted_raw(msg, c_gw, g)
+            cot_msg, cot_w = _segment_sum_weighted_backward_raw(ga, c_gm, c_gw, g, True)
+        else:  # no g_w was formed (w does not require grad): g_msg = w ga[dst] does not depend on msg
+            cot_msg, cot_w = None, None
+        return cot_ga, cot_msg, cot_w, None, None
 
 
 def segment_sum(msg: torch.Tensor, g: RadiusGraph, weight: torch.Tensor | None = None) -> torch.Tensor:
@@ -379,12 +562,44 @@ class _CutoffEnvelopeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gw):
         (d,) = ctx.saved_tensors
+        if torch.is_grad_enabled():  # create_graph: the backward is differentiated in d and gw
+            return _CutoffEnvelopeBackwardFn.apply(d, gw, ctx.r_c, ctx.p), None, None
+        return _cutoff_envelope_backward_raw(d, gw, ctx.r_c, ctx.p), None, None
+
+
+def _cutoff_envelope_backward_raw(d, gw, r_c, p):
+    gw = gw.contiguous()
+    gd = torch.empty_like(d)
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().e3_cutoff_envelope_backward(d.data_ptr(), gw.data_ptr(), d.numel(), r_c, p,
+                                                           gd.data_ptr(), _stream(d)), "e3_cutoff_envelope_backward")
+    return gd
+
+
+class _CutoffEnvelopeBackwardFn(torch.autograd.Function):
+    """(d, gw) -> g_d = gw u'(d); its backward is e3_cutoff_envelope_backward2: cot(gw) = c u'(d), cot(d) = c gw u''(d)."""
+
+    @staticmethod
+    def forward(ctx, d, gw, r_c, p):
+        ctx.r_c, ctx.p = r_c, p
         gw = gw.contiguous()
-        gd = torch.empty_like(d)
+        ctx.save_for_backward(d, gw)
+        return _cutoff_envelope_backward_raw(d, gw, r_c, p)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, c):
+        d, gw = ctx.saved_tensors
+        c = c.contiguous()
+        need_d, need_gw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        cot_gw = torch.empty_like(d) if need_gw else None
+        cot_d = torch.empty_like(d) if need_d else None
         with torch.cuda.device(d.device):
-            _lib.check(_lib.load().e3_cutoff_envelope_backward(d.data_ptr(), gw.data_ptr(), d.numel(), ctx.r_c, ctx.p,
-                                                               gd.data_ptr(), _stream(d)), "e3_cutoff_envelope_backward")
-        return gd, None, None
+            _lib.check(_lib.load().e3_cutoff_envelope_backward2(
+                d.data_ptr(), gw.data_ptr(), c.data_ptr(), d.numel(), ctx.r_c, ctx.p,
+                cot_gw.data_ptr() if need_gw else None, cot_d.data_ptr() if need_d else None, _stream(d)),
+                "e3_cutoff_envelope_backward2")
+        return cot_d, cot_gw, None, None
 
 
 def _cutoff_envelope_raw(d, r_c, p):

@@ -13,6 +13,7 @@ from math import sqrt
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib, profiling
 from .irreps import Irreps, as_blocks
@@ -92,25 +93,44 @@ class TPPlan:
         """ws / ns: 6-entry lists (per class) of optional tensors.  The packed buffer is rebuilt when a parameter or
         buffer was replaced or modified through autograd-visible ops (``_version``); in-place edits through ``.data``
         do not bump the version counter -- call ``invalidate_packed()`` after those."""
-        def pack(stream):
-            lib = _lib.load()
-            code = _lib.dtype_code(dtype)
-            for t in ws + ns:
-                if t is not None and t.numel() and (t.dtype != dtype or t.device != device):
-                    raise RuntimeError(f"tensor product: parameter {t.dtype}/{t.device} vs input {dtype}/{device}")
-            h = self.handle(device)
-            nbytes = lib.e3_tp_packed_bytes(h, code)
-            if nbytes < 0:
-                raise RuntimeError(f"tensor product supports float32/float64/bfloat16, got {dtype}")
-            packed = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-            P6 = ctypes.c_void_p * 6
-            ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None
-            wsc = [w.detach().contiguous() if w is not None else None for w in ws]
-            nsc = [n.detach().contiguous() if n is not None else None for n in ns]
-            _lib.call("e3_tp_pack_weights", h, P6(*map(ptr, wsc)), P6(*map(ptr, nsc)), code, packed.data_ptr(), stream)
-            return packed
+        return self._packed.get(ws + ns, dtype, device, lambda stream: self._pack(ws, ns, dtype, device, stream))
 
-        return self._packed.get(ws + ns, dtype, device, pack)
+    def _pack(self, ws, ns, dtype, device, stream):
+        lib = _lib.load()
+        code = _lib.dtype_code(dtype)
+        for t in ws + ns:
+            if t is not None and t.numel() and (t.dtype != dtype or t.device != device):
+                raise RuntimeError(f"tensor product: parameter {t.dtype}/{t.device} vs input {dtype}/{device}")
+        h = self.handle(device)
+        nbytes = lib.e3_tp_packed_bytes(h, code)
+        if nbytes < 0:
+            raise RuntimeError(f"tensor product supports float32/float64/bfloat16, got {dtype}")
+        packed = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        P6 = ctypes.c_void_p * 6
+        ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None
+        wsc = [w.detach().contiguous() if w is not None else None for w in ws]
+        nsc = [n.detach().contiguous() if n is not None else None for n in ns]
+        _lib.call("e3_tp_pack_weights", h, P6(*map(ptr, wsc)), P6(*map(ptr, nsc)), code, packed.data_ptr(), stream)
+        return packed
+
+    def pack_private(self, ws, ns, dtype, device):
+        """A packed buffer of its own for ``ws`` (e.g. cotangents in the weights' slots) with the norms ``ns``, on the
+        current stream: the cache slot of the module's real weights is not replaced."""
+        with torch.cuda.device(device):
+            return self._pack(ws, ns, dtype, device, torch.cuda.current_stream(device).cuda_stream)
+
+    def forward_exact(self, packed, in1, in2):
+        """``e3_tp_forward`` on the generic fp32 / fp64 kernel (``exact = 1``, never the fp16-split MFMA path) with the
+        packed weights given -> [B, out_dim]."""
+        B = in1.shape[0]
+        out = torch.empty((B, self.out_dim), dtype=in1.dtype, device=in1.device)
+        if B == 0:
+            return out
+        with torch.cuda.device(in1.device):
+            _lib.call("e3_tp_forward", self.handle(in1.device), in1.data_ptr(), in1.stride(0), in2.data_ptr(), in2.stride(0),
+                      packed.data_ptr(), out.data_ptr(), out.stride(0), B, _lib.dtype_code(in1.dtype), None, 1,
+                      torch.cuda.current_stream(in1.device).cuda_stream)
+        return out
 
     def invalidate_packed(self):
         self._packed.invalidate()
@@ -388,8 +408,94 @@ def tp_backward(plan: "TPPlan", packed, in1, in2, grad_out, weights, need1, need
     return g1, g2, gws
 
 
+class _TPBackwardFn(torch.autograd.Function):
+    """The first-order backward of a tensor product as a differentiable op: (in1, in2, grad_out, W...) -> (grad_in1,
+    grad_in2, grad_W...), used by ``_SHTPFunction`` and ``_L1TPFunction`` when grad mode is on inside their backward
+    (``create_graph=True``).  ``forward`` is the operator's own first-order call (``first``), so first-order results are
+    bit-identical with or without a graph.
+
+    The product is multilinear in (x, y, W), so with Phi(x, y, W, g) = <g, TP(x, y; W)> and cotangents (c1, c2, cW) of
+    (grad_in1, grad_in2, grad_W):
+        cot(g) = TP(c1, y; W) + TP(x, c2; W) + TP(x, y; cW)              (three generic-kernel forwards)
+        backward(c1, y, W, g) -> cot(y), cot(W);  backward(x, c2, W, g) -> cot(x), cot(W);
+        backward(x, y, cW, g) -> cot(x), cot(y)                          (three ``tp_backward`` calls)
+    on the general plan ``plan`` (``L1TensorProduct``: its lmax_sh = 1 plan, as ``_general_backward``).  A call whose
+    cotangent is None or whose results nobody needs is skipped.  A substituted weight gets a packed buffer of its own
+    (``TPPlan.pack_private``); the real weights' image is read from the cache slot when it holds them: it is never replaced.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, first, plan, ns6, slots, needs, in1, in2, grad_out, *weights):
+        """first(in1, in2, grad_out, weights, needs) -> (g1 | None, g2 | None, *gW | None), one gW per entry of
+        ``weights``; slots[i] = the class (0..5) of weights[i] in ``plan``; ns6 = the six norm buffers; needs = the
+        ``needs_input_grad`` of (in1, in2, *weights) in the first-order Function."""
+        ctx.set_materialize_grads(False)
+        ctx.plan, ctx.ns6, ctx.slots = plan, ns6, slots
+        ctx.save_for_backward(in1, in2, grad_out, *weights)
+        return first(in1, in2, grad_out, weights, needs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, c1, c2, *cws):
+        x, y, g, *weights = ctx.saved_tensors
+        plan, ns6, slots = ctx.plan, ctx.ns6, ctx.slots
+        need_x, need_y, need_g = ctx.needs_input_grad[5:8]
+        need_w = list(ctx.needs_input_grad[8:])
+        B, dt, dev = x.shape[0], x.dtype, x.device
+        if y.shape[0] == 1 and B != 1:
+            raise NotImplementedError("second derivatives of a tensor product with in2 broadcast over the rows ([1, D2]) are "
+                                      "not implemented: expand in2 to [B, D2]")
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        y = y if y.stride(-1) == 1 else y.contiguous()
+        ws6, nw6 = [None] * 6, [False] * 6
+        for s, w, n in zip(slots, weights, need_w):
+            ws6[s], nw6[s] = w.detach(), bool(n)
+        any_w = any(nw6)
+        packed_w = None  # packed image of the saved weights, found on first use
+
+        def real():  # the plan's cached image when it was packed from these very weights (read, never replaced), else a private one
+            nonlocal packed_w
+            if packed_w is None:
+                packed_w = plan._packed.peek(ws6 + ns6, dt, dev)
+            if packed_w is None:
+                packed_w = plan.pack_private(ws6, ns6, dt, dev)
+            return packed_w
+
+        add = lambda a, b: b if a is None else (a if b is None else a + b)
+        add6 = lambda a, b: b if a is None else [add(p, q) for p, q in zip(a, b)]
+        cot_x = cot_y = cot_g = cot_w6 = None
+        if c1 is not None:
+            c1 = c1.to(dt).contiguous()
+            if need_g:
+                cot_g = add(cot_g, plan.forward_exact(real(), c1, y))
+            if need_y or any_w:
+                _, gy, gw = tp_backward(plan, real(), c1, y, g, ws6, False, need_y, nw6)
+                cot_y, cot_w6 = add(cot_y, gy), add6(cot_w6, gw)
+        if c2 is not None:
+            c2 = c2.to(dt).contiguous()
+            if need_g:
+                cot_g = add(cot_g, plan.forward_exact(real(), x, c2))
+            if need_x or any_w:
+                gx, _, gw = tp_backward(plan, real(), x, c2, g, ws6, need_x, False, nw6)
+                cot_x, cot_w6 = add(cot_x, gx), add6(cot_w6, gw)
+        if any(c is not None for c in cws) and (need_g or need_x or need_y):
+            cw6 = [None] * 6
+            for s, w, c in zip(slots, weights, cws):
+                cw6[s] = c.detach().to(w.dtype).contiguous() if c is not None else torch.zeros_like(w)
+            packed_c = plan.pack_private(cw6, ns6, dt, dev)
+            if need_g:
+                cot_g = add(cot_g, plan.forward_exact(packed_c, x, y))
+            if need_x or need_y:
+                gx, gy, _ = tp_backward(plan, packed_c, x, y, g, cw6, need_x, need_y, [False] * 6)
+                cot_x, cot_y = add(cot_x, gx), add(cot_y, gy)
+        if cot_y is not None:
+            cot_y = cot_y.to(y.dtype)
+        cot_w = [None if (cot_w6 is None or cot_w6[s] is None) else cot_w6[s].to(w.dtype) for s, w in zip(slots, weights)]
+        return (None, None, None, None, None, cot_x, cot_y, cot_g, *cot_w)
+
+
 class _SHTPFunction(torch.autograd.Function):
-    """autograd bridge: forward = e3_tp_forward, backward = ``tp_backward`` (fp32 / fp64)."""
+    """autograd bridge: forward = e3_tp_forward, backward = ``tp_backward`` (fp32 / fp64); with grad mode on inside the
+    backward (``create_graph=True``) the same call runs as ``_TPBackwardFn``, which has a backward of its own."""
 
     @staticmethod
     def forward(ctx, mod, in1, in2, *weights):
@@ -405,16 +511,24 @@ class _SHTPFunction(torch.autograd.Function):
         if grad_out.stride(-1) != 1 or grad_out.dtype != in1.dtype:
             grad_out = grad_out.to(in1.dtype).contiguous()
         present = [hasattr(mod, "weights_" + c) for c in CLASSES]
-        it, ni = iter(weights), iter(ctx.needs_input_grad[3:])
-        ws = [next(it) if pr else None for pr in present]
-        nw = [next(ni) if pr else False for pr in present]
-        with torch.cuda.device(in1.device):
-            packed = mod._packed_weights(in1.dtype, in1.device)
-        g1, g2, gws = tp_backward(mod._plan, packed, in1, in2, grad_out, ws, ctx.needs_input_grad[1],
-                                  ctx.needs_input_grad[2], nw)
-        out = [None, g1, g2.to(in2.dtype) if g2 is not None else None]
-        out += [gw.to(w.dtype) if gw is not None else None for gw, w, pr in zip(gws, ws, present) if pr]
-        return tuple(out)
+
+        def first(in1, in2, grad_out, weights, needs):
+            it, ni = iter(weights), iter(needs[2:])
+            ws = [next(it) if pr else None for pr in present]
+            nw = [next(ni) if pr else False for pr in present]
+            with torch.cuda.device(in1.device):
+                packed = mod._packed_weights(in1.dtype, in1.device)
+            g1, g2, gws = tp_backward(mod._plan, packed, in1, in2, grad_out, ws, needs[0], needs[1], nw)
+            out = [g1, g2.to(in2.dtype) if g2 is not None else None]
+            out += [gw.to(w.dtype) if gw is not None else None for gw, w, pr in zip(gws, ws, present) if pr]
+            return tuple(out)
+
+        needs = tuple(ctx.needs_input_grad[1:])
+        if torch.is_grad_enabled():  # create_graph: the backward is differentiated (second derivatives)
+            slots = tuple(ci for ci, pr in enumerate(present) if pr)
+            return (None,) + _TPBackwardFn.apply(first, mod._plan, mod._tensors()[1], slots, needs, in1, in2, grad_out,
+                                                 *weights)
+        return (None,) + first(in1, in2, grad_out, weights, needs)
 
 
 class SHTensorProduct(nn.Module):
