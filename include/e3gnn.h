@@ -735,8 +735,25 @@ int e3_segment_sum_weighted_backward(const float* g_agg, int64_t ld_gagg, const 
  *       e3_edge_geometry_l2, d_edge_y[e,0] = 0;  d_node_a[i,k] = (1/deg_i) sum over CSR row i of d_edge_y[e,k],
  *       d_node_a[i,0] = 0.  Edges with d = 0 and rows without edges give zeros.  Each of the three outputs may be NULL.  One
  *       wave per row; d_node_a is one fixed-order wave reduction per row (no atomics): bit-equal from run to run.  The
- *       derivative of g_pos w.r.t. pos itself (the Hessian of Y, d, A in r) is NOT provided.
+ *       derivative of g_pos w.r.t. pos itself is e3_edge_geometry_hvp below.
  *       E3_ERR_INVALID_ARG for lmax outside {1, 2}, N < 0, an invalid box / cell, or (N > 0) a NULL pos4 / rowptr / src / v.
+ *
+ *   e3_edge_geometry_hvp : the other half of the backward of e3_edge_geometry_backward, its vector-Jacobian product in the
+ *       positions: h_pos = d<v, g_pos(pos; g_edge_y, g_edge_d, g_node_a)>/dpos for a cotangent v [N,3] of g_pos -- with the
+ *       cotangents above, everything a Hessian-vector product of the energy needs.  Per edge (r_e the minimum image, whose
+ *       shift is piecewise constant; d = |r|, u = r / d; g = g_edge_y[e] + g_node_a[dst] / deg on the components >= 1) the
+ *       first-order edge gradient is grad phi_e, phi_e(r) = <g, Y(r)> + g_edge_d[e] |r|, and
+ *         h_e = (Hess phi_e) t_e,  t_e = v[src] - v[dst];   h_pos[src] += h_e,  h_pos[dst] -= h_e.
+ *       On the unit sphere <g, Y> = a1 . u + u^T Q u / 2 with a1 = sqrt3 (g1, g2, g3) and (l_max = 2; Q = 0 at l_max = 1)
+ *         Q = sqrt5 [[-g6 + sqrt3 g8, sqrt3 g4, sqrt3 g7], [sqrt3 g4, -g6 - sqrt3 g8, sqrt3 g5], [sqrt3 g7, sqrt3 g5, 2 g6]],
+ *       so with psi = a1 + Q u (the g_u of e3_edge_geometry_backward), P = I - u u^T, du = P t / d and dd = u . t:
+ *         h_e = [ -(du (u . psi) + u (du . psi)) + P Q du ] / d  -  P psi dd / d^2  +  g_edge_d[e] du.
+ *       Each of g_edge_y, g_edge_d, g_node_a may be NULL (zeros), as in e3_edge_geometry_backward.  Edges with d = 0 and rows
+ *       without edges contribute nothing.  h_pos [N,3] is zero-filled by the call.  One wave per dst row, lanes over its
+ *       edges: fp32 atomics into h_pos[src], a wave reduction and one atomic per component for the dst row -- like g_pos, the
+ *       result is NOT bit-reproducible on a general cloud (order of arrival).  There is no strained form.
+ *       E3_ERR_INVALID_ARG before any launch for lmax outside {1, 2}, N < 0, a NULL v or h_pos, an invalid box / cell, or
+ *       (N > 0) a NULL rowptr, or a NULL pos4 with a src; N = 0, or a NULL src (a graph without edges): zero-fill only.
  *
  *   e3_gate_blocks_backward2 : in, g_out as e3_gate_blocks_backward, c = the cotangent of its g_in (layout of in).  With
  *       s = sigmoid, one launch writes cot_g_out (layout of g_out) and cot_in (layout of in), either may be NULL:
@@ -758,6 +775,17 @@ int e3_edge_geometry_jvp_pbc(const float* pos4, const int32_t* rowptr, const int
 int e3_edge_geometry_jvp_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                               const float cell[9], const float* v, float* d_edge_y, float* d_edge_d, float* d_node_a,
                               void* stream);
+int e3_edge_geometry_hvp(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                         const float* g_edge_y, const float* g_edge_d, const float* g_node_a, const float* v, float* h_pos,
+                         void* stream);
+/* periodic box: as e3_edge_geometry_pbc */
+int e3_edge_geometry_hvp_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                             const float box[3], const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
+                             const float* v, float* h_pos, void* stream);
+/* general cell: as e3_edge_geometry_cell */
+int e3_edge_geometry_hvp_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                              const float cell[9], const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
+                              const float* v, float* h_pos, void* stream);
 int e3_gate_blocks_backward2(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, const float* c,
                              int64_t ld_c, float* cot_g_out, int64_t ld_cgout, float* cot_in, int64_t ld_cin, int64_t B,
                              int ns, int nblocks, const int32_t* ls, const int32_t* muls, void* stream);

@@ -202,6 +202,13 @@ SIGNATURES = {
                                          c_void_p, c_void_p]),
     "e3_edge_geometry_jvp_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    # ... and its backward in the positions (..., lmax[, box | cell], gY, gd, gA, v, h_pos, stream)
+    "e3_edge_geometry_hvp": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "e3_edge_geometry_hvp_pbc": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float3, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "e3_edge_geometry_hvp_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
     "e3_gate_blocks_backward2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                          c_int64, c_int64, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]),
     "e3_cutoff_envelope_backward2": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float, c_int, c_void_p, c_void_p,

@@ -10,8 +10,9 @@ through the whole message pass: every stage has a HIP backward (tensor products:
 edge geometry, gather/concat, gates, segment-sum: `e3_*_backward`, csrc/e3_edge_bwd.hip).  With ``create_graph=True`` the
 forces keep their graph: every stage's backward has a backward of its own (the multilinear stages by composition of the
 same entries; `e3_edge_geometry_jvp`, `e3_gate_blocks_backward2`, `e3_cutoff_envelope_backward2`), so a loss on energies
-AND forces has parameter gradients.  The derivative of the forces w.r.t. the positions (the Hessian of
-Y, d, A in r) is not built: a parameter gradient never needs it.
+AND forces has parameter gradients.  The derivative of the forces w.r.t. the positions needs one kernel
+more, the Hessian of Y, d, A in the edge vector (`e3_edge_geometry_hvp`): a parameter gradient never needs it and the
+force-loss step does not launch it; `hessian_vector_product` / `hessian` of the two models below do.
 Virials and stress are the derivative w.r.t. a zero strain per structure, reduced inside the same geometry backward
 (`e3_edge_geometry_backward_strained`); `PeriodicEnergyModel` is the periodic-box counterpart of `BatchedEnergyModel`.
 """
@@ -102,7 +103,8 @@ def _check_create_graph(net, x, forces: bool, strained: bool):
         raise ValueError("create_graph=True keeps the graph of the forces: it needs forces=True")
     if not any(p.requires_grad for p in net.parameters()):
         raise ValueError("create_graph=True needs at least one parameter that requires grad: the graph of the forces leads "
-                         "to the parameters only (the derivative of the forces w.r.t. the positions is not implemented)")
+                         "to the parameters only (the derivative of the forces w.r.t. the positions is "
+                         "hessian_vector_product)")
 
 
 def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, structure, cutoff_kw=None, halo=None,
@@ -121,7 +123,9 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
     with torch.enable_grad():
         p = pos_g.detach().float().requires_grad_(forces)
         eps = torch.zeros((n_strain, 3, 3), dtype=torch.float32, device=p.device, requires_grad=True) if n_strain else None
-        geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p, strain=eps, structure=structure)  # differentiable Y, d, A
+        # differentiable Y, d, A.  pos_hessian=False: under create_graph the graph of the forces is wanted for the parameters
+        # only, so the geometry backward gets no position edge (no Hessian launch, no unused .grad on the leaf p)
+        geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p, strain=eps, structure=structure, pos_hessian=False)
         e_node = net(x_g, g, geometry=geometry, halo=halo, split=split, **(cutoff_kw or {}))
         if halo is not None:
             e_node = e_node[halo.owned_new]
@@ -139,6 +143,58 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
     return (energy if (net.training or create_graph) else energy.detach()), gpos, geps
 
 
+HESSIAN_MAX_ATOMS = 256   # hessian(): 3 N second backwards and a dense [N,3,N,3] result -- molecules and small cells
+
+
+def _hessian_vector_products(net, x_g, g, pos_g, v_g, cutoff_kw):
+    """H v for every v of ``v_g`` [K,N,3] (graph order) -> [K,N,3], H = d2(sum of the scalar node readout)/dpos_g^2 on the
+    edge set of ``g``.  One forward, one first backward with ``create_graph=True`` -- the geometry with its position edge
+    (``ops.edge_geometry(pos_hessian=True)``) -- and one second backward per vector on the retained graph.  Only the
+    position leaf is differentiated: the parameters may be frozen and none of them gets a ``.grad``."""
+    from . import ops
+    if x_g.dtype == torch.bfloat16:
+        raise NotImplementedError("hessian_vector_product with bf16 storage: bf16 runs the fused inference kernels only and "
+                                  "has no differentiable chain")
+    v_g = v_g.to(torch.float32)
+    # the parameters are constants of H v: frozen for the length of the call, so that no backward forms a weight gradient
+    # or a weight cotangent that nobody reads (the Functions decide from requires_grad at forward time)
+    trainable = [q for q in net.parameters() if q.requires_grad]
+    for q in trainable:
+        q.requires_grad_(False)
+    try:
+        with torch.enable_grad():
+            p = pos_g.detach().float().requires_grad_(True)
+            geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p)
+            e_node = net(x_g, g, geometry=geometry, **(cutoff_kw or {}))
+            (gpos,) = torch.autograd.grad(e_node[:, 0].sum(), [p], create_graph=True)
+        out = [torch.autograd.grad(gpos, [p], v, retain_graph=k + 1 < len(v_g))[0] for k, v in enumerate(v_g)]
+    finally:
+        for q in trainable:
+            q.requires_grad_(True)
+    return torch.stack(out) if out else torch.zeros_like(v_g)
+
+
+def _check_vectors(v, pos):
+    """v [N,3] or [K,N,3] for pos [N,3] -> v as [K,N,3]; ValueError otherwise"""
+    if v is None:
+        raise ValueError("hessian_vector_product needs v= ([N,3] or [K,N,3])")
+    if tuple(v.shape[-2:]) != tuple(pos.shape) or v.dim() not in (2, 3):
+        raise ValueError(f"v must be [N,3] or [K,N,3] with N = {pos.shape[0]}, got {tuple(v.shape)}")
+    return v.reshape(-1, *pos.shape)
+
+
+def _dense_hessian(hvp, pos, chunk: int = 96):
+    """[N,3,N,3] from ``hvp(v [K,N,3]) -> [K,N,3]`` on the 3 N unit vectors, ``chunk`` at a time"""
+    N = pos.shape[0]
+    if N > HESSIAN_MAX_ATOMS:
+        raise ValueError(f"hessian() is meant for molecules and small cells: N = {N} > {HESSIAN_MAX_ATOMS} atoms "
+                         "(HESSIAN_MAX_ATOMS); use hessian_vector_product")
+    eye = torch.eye(3 * N, dtype=torch.float32, device=pos.device).view(3 * N, N, 3)
+    cols = [hvp(eye[k:k + chunk]) for k in range(0, 3 * N, chunk)]
+    H = torch.cat(cols) if cols else eye
+    return H.view(N, 3, N, 3).permute(2, 3, 0, 1).contiguous()   # H[i, a, j, b] = (H e_jb)[i, a]
+
+
 class BatchedEnergyModel(nn.Module):
     """SEGNN with a scalar node readout summed per molecule: energies [n_mol].  ``envelope`` (the exponent p, e.g. 6;
     ``SEGNN(envelope=)``): every pair is weighted by a smooth cutoff envelope of radius ``r``, so the energy is a smooth
@@ -148,6 +204,18 @@ class BatchedEnergyModel(nn.Module):
                  envelope: int | None = None):
         super().__init__()
         self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
+
+    def _graph(self, pos, batch, r, skin, neighbors):
+        """The graph of a forward -> (RadiusGraph, molecule of every node in graph order)"""
+        if neighbors is not None:
+            if neighbors.batch is None:
+                raise ValueError("neighbors= of a batched model must be a NeighborList made with batch=")
+            g = _neighbors_graph(neighbors, pos, r, skin, {})
+            if neighbors.rebuilt and not (neighbors.batch.shape == batch.shape and
+                                          torch.equal(neighbors.batch.to(batch.device).long(), batch.long())):
+                raise ValueError("batch= is not the tensor neighbors= was made with")
+            return g, neighbors.mol_of_node
+        return batched_radius_graph(pos, batch, _skin_radius(self.net, r, skin))
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, forces: bool = False,
                 virial: bool = False, skin: float = 0.0, neighbors=None, create_graph: bool = False):
@@ -166,20 +234,11 @@ class BatchedEnergyModel(nn.Module):
         ``create_graph=True`` (needs ``forces=True`` and a parameter that requires grad; fp32): energies and forces both
         carry a graph, in ``train()`` and ``eval()`` mode, so ``loss(energies, forces).backward()`` fills ``p.grad`` of
         every parameter -- training on forces.  The graph leads to the parameters only: the derivative of the forces
-        w.r.t. the positions is not built.  ``NotImplementedError`` with ``virial=True`` (no tangent kernel for the
+        w.r.t. the positions is ``hessian_vector_product``.  ``NotImplementedError`` with ``virial=True`` (no tangent kernel for the
         strained geometry) and for bf16 storage.  False (the default) is the first-order call, unchanged."""
         if create_graph:
             _check_create_graph(self.net, x, forces, virial)
-        if neighbors is not None:
-            if neighbors.batch is None:
-                raise ValueError("neighbors= of a batched model must be a NeighborList made with batch=")
-            g = _neighbors_graph(neighbors, pos, r, skin, {})
-            if neighbors.rebuilt and not (neighbors.batch.shape == batch.shape and
-                                          torch.equal(neighbors.batch.to(batch.device).long(), batch.long())):
-                raise ValueError("batch= is not the tensor neighbors= was made with")
-            mol = neighbors.mol_of_node
-        else:
-            g, mol = batched_radius_graph(pos, batch, _skin_radius(self.net, r, skin))
+        g, mol = self._graph(pos, batch, r, skin, neighbors)
         cut = _cutoff_kw(self.net, r)
         n_mol = int(batch.max().item()) + 1 if batch.numel() else 0
         perm = g.perm.long()
@@ -197,6 +256,28 @@ class BatchedEnergyModel(nn.Module):
         if virial:
             out.append(-geps)
         return tuple(out)
+
+    def hessian_vector_product(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, v: torch.Tensor,
+                               skin: float = 0.0, neighbors=None) -> torch.Tensor:
+        """H v, H = d2(sum of the energies)/dpos2 on the edge set of the current graph (block diagonal over the molecules);
+        ``v`` [N,3] or [K,N,3] in the caller's atom order -> a detached tensor of the shape of ``v``.  ``r`` / ``skin`` /
+        ``neighbors`` select the graph exactly as in ``forward``.  One forward and one first backward with
+        ``create_graph=True``, then one second backward per vector (``e3_edge_geometry_hvp`` closes the chain, DESIGN.md
+        §4.6).  Works on a frozen model in ``eval()``; no parameter gets a ``.grad``.  fp32: bf16 storage raises
+        ``NotImplementedError``."""
+        vs = _check_vectors(v, pos)
+        g, _ = self._graph(pos, batch, r, skin, neighbors)
+        perm = g.perm.long()
+        hv = _hessian_vector_products(self.net, x[perm], g, pos[perm], vs[:, perm], _cutoff_kw(self.net, r))
+        out = torch.empty_like(hv)
+        out[:, perm] = hv
+        return out.reshape(v.shape)
+
+    def hessian(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, skin: float = 0.0,
+                neighbors=None) -> torch.Tensor:
+        """The dense H [N,3,N,3] (``H[i,a,j,b]`` = d2E/dpos[i,a] dpos[j,b]): ``hessian_vector_product`` on the 3 N unit vectors
+        in chunks.  ``ValueError`` above ``HESSIAN_MAX_ATOMS`` = 256 atoms: it is meant for molecules and small cells."""
+        return _dense_hessian(lambda vs: self.hessian_vector_product(x, pos, batch, r, vs, skin=skin, neighbors=neighbors), pos)
 
 
 class PeriodicEnergyModel(nn.Module):
@@ -235,26 +316,11 @@ class PeriodicEnergyModel(nn.Module):
         both carry a graph, in ``train()`` and ``eval()`` mode, so ``loss(energy, forces).backward()`` fills ``p.grad`` of
         every parameter -- training on forces -- for an open box, a box and ``cell=``, with or without ``envelope=``,
         ``skin=`` and ``neighbors=``.  The graph leads to the parameters only: the derivative of the forces w.r.t. the
-        positions is not built.  ``NotImplementedError`` with ``virial=True`` / ``stress=True`` (no tangent kernel for the
+        positions is ``hessian_vector_product``.  ``NotImplementedError`` with ``virial=True`` / ``stress=True`` (no tangent kernel for the
         strained geometry) and for bf16 storage.  False (the default) is the first-order call, unchanged."""
-        from .radius_graph import periodic_mask
         if create_graph:
             _check_create_graph(self.net, x, forces, virial or stress)
-        r_env, r = r, _skin_radius(self.net, r, skin)
-        cut = _cutoff_kw(self.net, r_env)
-        if neighbors is not None:
-            if stress and not neighbors.fully_periodic:  # from the list's box: refused before the list is touched
-                raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
-            g = _neighbors_graph(neighbors, pos, r, skin, {"lo": (lo, None), "hi": (hi, None), "periodic": (periodic, True),
-                                                          "cell": (cell, None), "origin": (origin, None)})
-        elif cell is not None:
-            if lo is not None or hi is not None or periodic is not True:
-                raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
-            g = radius_graph(pos, r, cell=cell, origin=origin)
-        else:
-            if stress and periodic_mask(periodic, r, lo, hi) != 7:
-                raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
-            g = radius_graph(pos, r, lo, hi, periodic=periodic)
+        g, cut = self._graph(pos, r, lo, hi, periodic, cell, origin, skin, neighbors, stress)
         perm = g.perm.long()
         if not (forces or virial or stress):
             return self.net(x[perm], g, **cut)[:, 0].sum()
@@ -271,6 +337,50 @@ class PeriodicEnergyModel(nn.Module):
             V = float(g.volume) if g.cell is not None else float(g.box[0]) * float(g.box[1]) * float(g.box[2])
             out.append((geps[0].double() / V).float())
         return tuple(out)
+
+    def _graph(self, pos, r, lo, hi, periodic, cell, origin, skin, neighbors, stress=False):
+        """The graph of a forward -> (RadiusGraph, the cutoff= of the net's forward)"""
+        from .radius_graph import periodic_mask
+        r_env, r = r, _skin_radius(self.net, r, skin)
+        cut = _cutoff_kw(self.net, r_env)
+        if neighbors is not None:
+            if stress and not neighbors.fully_periodic:  # from the list's box: refused before the list is touched
+                raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
+            g = _neighbors_graph(neighbors, pos, r, skin, {"lo": (lo, None), "hi": (hi, None), "periodic": (periodic, True),
+                                                          "cell": (cell, None), "origin": (origin, None)})
+        elif cell is not None:
+            if lo is not None or hi is not None or periodic is not True:
+                raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
+            g = radius_graph(pos, r, cell=cell, origin=origin)
+        else:
+            if stress and periodic_mask(periodic, r, lo, hi) != 7:
+                raise ValueError("stress is defined for a box periodic on all three axes; use virial=True for an open axis")
+            g = radius_graph(pos, r, lo, hi, periodic=periodic)
+        return g, cut
+
+    def hessian_vector_product(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, cell=None,
+                               origin=None, v: torch.Tensor | None = None, skin: float = 0.0, neighbors=None) -> torch.Tensor:
+        """H v, H = d2E/dpos2 on the edge set of the current graph (the lattice shift of every edge held fixed); ``v`` [N,3]
+        or [K,N,3] in the caller's order -> a detached tensor of the shape of ``v``.  ``lo`` / ``hi`` / ``periodic`` /
+        ``cell`` / ``origin`` / ``skin`` / ``neighbors`` select the graph exactly as in ``forward``: open box, box, cell,
+        envelope, skin, Verlet list.  One forward and one first backward with ``create_graph=True``, then one second backward
+        per vector (``e3_edge_geometry_hvp`` closes the chain) -- what vibrational frequencies, phonons at
+        Gamma, dimer / Lanczos saddle searches and Newton-type relaxations consume.  Works on a frozen model in ``eval()``;
+        no parameter gets a ``.grad``.  fp32: bf16 storage raises ``NotImplementedError``."""
+        vs = _check_vectors(v, pos)
+        g, cut = self._graph(pos, r, lo, hi, periodic, cell, origin, skin, neighbors)
+        perm = g.perm.long()
+        hv = _hessian_vector_products(self.net, x[perm], g, pos[perm], vs[:, perm], cut)
+        out = torch.empty_like(hv)
+        out[:, perm] = hv
+        return out.reshape(v.shape)
+
+    def hessian(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, cell=None, origin=None,
+                skin: float = 0.0, neighbors=None) -> torch.Tensor:
+        """The dense H [N,3,N,3] (``H[i,a,j,b]`` = d2E/dpos[i,a] dpos[j,b]): ``hessian_vector_product`` on the 3 N unit vectors
+        in chunks.  ``ValueError`` above ``HESSIAN_MAX_ATOMS`` = 256 atoms: it is meant for molecules and small cells."""
+        return _dense_hessian(lambda vs: self.hessian_vector_product(x, pos, r, lo, hi, periodic, cell, origin, vs, skin=skin,
+                                                                     neighbors=neighbors), pos)
 
 
 class ShardedEnergyModel(nn.Module):

@@ -348,6 +348,88 @@ __global__ __launch_bounds__(256) void edge_geometry_jvp_kernel(const float4* __
   }
 }
 
+// Backward of edge_geometry_bwd_kernel in the positions (include/e3gnn.h, e3_edge_geometry_hvp): hpos = d<v, gpos>/dpos.  Per
+// edge gpos gets +-grad phi, phi(r) = <g, Y(r)> + gd |r| with g as above, so hpos gets +-(Hess phi) t, t = v[src] - v[dst].
+// On the sphere <g, Y> = a1 . u + u^T Q u / 2 (a1 = sqrt3 g[1..3], Q the symmetric matrix of the l = 2 components of g), and
+// psi = a1 + Q u is the (ux, uy, uz) of the kernel above.  With P = I - u u^T, du = P t / d, dd = u . t:
+//   h = [ -(du (u . psi) + u (du . psi)) + P Q du ] / d  -  P psi dd / d^2  +  gd du
+// Same shape as the first-order kernel: one wave per row, atomics into hpos[src], one wave reduction per row for hpos[dst].
+template <int LMAX, int PBC>
+__global__ __launch_bounds__(256) void edge_geometry_hvp_kernel(const float4* __restrict__ pos4,
+                                                                const int32_t* __restrict__ rowptr,
+                                                                const int32_t* __restrict__ src, int64_t N,
+                                                                const float* __restrict__ gY, const float* __restrict__ gd,
+                                                                const float* __restrict__ gA, const float* __restrict__ v,
+                                                                float* __restrict__ hpos,
+                                                                const typename PbcArg<PBC>::type box) {
+  constexpr int NY = (LMAX + 1) * (LMAX + 1);
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t i = wave0; i < N; i += nw) {
+    const int b = rowptr[i], e = rowptr[i + 1];
+    if (b == e) continue;
+    const float4 pi = pos4[i];
+    const float vix = v[i * 3 + 0], viy = v[i * 3 + 1], viz = v[i * 3 + 2];
+    const float invdeg = 1.0f / (float)(e - b);
+    float ga[NY];
+#pragma unroll
+    for (int k = 1; k < NY; ++k) ga[k] = gA ? gA[i * NY + k] * invdeg : 0.f;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int q = b + lane; q < e; q += 64) {
+      const int j = src[q];
+      const float4 pj = pos4[j];
+      float rx, ry, rz;
+      edge_rel<PBC>(pj, pi, box, rx, ry, rz);
+      const float d = sqrtf(rx * rx + ry * ry + rz * rz);
+      if (!(d > 0.f)) continue;
+      const float inv = 1.0f / d;
+      const float x = rx * inv, y = ry * inv, z = rz * inv;
+      float g[NY];
+#pragma unroll
+      for (int k = 1; k < NY; ++k) g[k] = (gY ? gY[(int64_t)q * NY + k] : 0.f) + ga[k];
+      const float tx = v[(int64_t)j * 3 + 0] - vix, ty = v[(int64_t)j * 3 + 1] - viy, tz = v[(int64_t)j * 3 + 2] - viz;
+      const float dd = x * tx + y * ty + z * tz;
+      const float dux = (tx - x * dd) * inv, duy = (ty - y * dd) * inv, duz = (tz - z * dd) * inv;
+      float px = kS3 * g[1], py = kS3 * g[2], pz = kS3 * g[3];  // psi
+      float wx = 0.f, wy = 0.f, wz = 0.f;                       // Q du
+      if constexpr (LMAX == 2) {
+        const float qxx = kS5 * (kS3 * g[8] - g[6]), qyy = -kS5 * (kS3 * g[8] + g[6]), qzz = 2.f * kS5 * g[6];
+        const float qxy = kS5 * kS3 * g[4], qyz = kS5 * kS3 * g[5], qzx = kS5 * kS3 * g[7];
+        px += qxx * x + qxy * y + qzx * z;
+        py += qxy * x + qyy * y + qyz * z;
+        pz += qzx * x + qyz * y + qzz * z;
+        wx = qxx * dux + qxy * duy + qzx * duz;
+        wy = qxy * dux + qyy * duy + qyz * duz;
+        wz = qzx * dux + qyz * duy + qzz * duz;
+      }
+      const float up = x * px + y * py + z * pz;         // u . psi
+      const float dp = dux * px + duy * py + duz * pz;   // du . psi
+      const float uw = x * wx + y * wy + z * wz;         // u . Q du
+      const float gdv = gd ? gd[q] : 0.f;
+      const float c = gdv - up * inv, s = dd * inv * inv;
+      // [P Q du - du (u . psi) - u (du . psi)] / d - (psi - u (u . psi)) dd / d^2 + gd du
+      const float hx = (wx - x * (uw + dp)) * inv + c * dux - (px - x * up) * s;
+      const float hy = (wy - y * (uw + dp)) * inv + c * duy - (py - y * up) * s;
+      const float hz = (wz - z * (uw + dp)) * inv + c * duz - (pz - z * up) * s;
+      atomicAdd(hpos + (int64_t)j * 3 + 0, hx);
+      atomicAdd(hpos + (int64_t)j * 3 + 1, hy);
+      atomicAdd(hpos + (int64_t)j * 3 + 2, hz);
+      sx += hx; sy += hy; sz += hz;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      sx += __shfl_xor(sx, o);
+      sy += __shfl_xor(sy, o);
+      sz += __shfl_xor(sz, o);
+    }
+    if (lane == 0) {
+      atomicAdd(hpos + i * 3 + 0, -sx);
+      atomicAdd(hpos + i * 3 + 1, -sy);
+      atomicAdd(hpos + i * 3 + 2, -sz);
+    }
+  }
+}
+
 // agg[i] = sum over the row of msg[e]  ->  gmsg[e] = gagg[dst(e)]
 __global__ __launch_bounds__(256) void segment_sum_bwd_kernel(const float* __restrict__ gagg, int64_t ld_ga,
                                                               const int32_t* __restrict__ rowptr, int64_t N, int D,
@@ -424,7 +506,47 @@ static int edge_geometry_jvp(const float* pos4, const int32_t* rowptr, const int
   return E3_OK;
 }
 
+// one periodicity mode (box: the mode's kernel argument, validated by the caller)
+template <int PBC>
+static int edge_geometry_hvp(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                             const float* g_edge_y, const float* g_edge_d, const float* g_node_a, const float* v,
+                             float* h_pos, const typename PbcArg<PBC>::type& b, void* stream) {
+  if (N < 0 || (lmax != 1 && lmax != 2) || !v || !h_pos) return E3_ERR_INVALID_ARG;
+  if (N == 0) return E3_OK;
+  if (!rowptr || (src && !pos4)) return E3_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  E3_HIP_CHECK(hipMemsetAsync(h_pos, 0, (size_t)N * 3 * sizeof(float), s));
+  if (!src) return E3_OK;  // a graph without edges has no src to hand over: every row is empty
+  auto kern = lmax == 1 ? edge_geometry_hvp_kernel<1, PBC> : edge_geometry_hvp_kernel<2, PBC>;
+  hipLaunchKernelGGL(kern, dim3(wave_grid_b(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
+                     g_node_a, v, h_pos, b);
+  E3_HIP_CHECK(hipGetLastError());
+  return E3_OK;
+}
+
 extern "C" {
+
+int e3_edge_geometry_hvp(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                         const float* g_edge_y, const float* g_edge_d, const float* g_node_a, const float* v, float* h_pos,
+                         void* stream) {
+  return edge_geometry_hvp<kOpen>(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, v, h_pos, make_box(nullptr),
+                                  stream);
+}
+
+int e3_edge_geometry_hvp_pbc(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                             const float box[3], const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
+                             const float* v, float* h_pos, void* stream) {
+  if (!box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_hvp<kBox>(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, v, h_pos, make_box(box), stream);
+}
+
+int e3_edge_geometry_hvp_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                              const float cell[9], const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
+                              const float* v, float* h_pos, void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_hvp<kCell>(pos4, rowptr, src, N, lmax, g_edge_y, g_edge_d, g_node_a, v, h_pos, c, stream);
+}
 
 int e3_edge_geometry_jvp(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax, const float* v,
                          float* d_edge_y, float* d_edge_d, float* d_node_a, void* stream) {

@@ -4,8 +4,9 @@ fp32.  Every op is differentiable (torch.autograd.Function over the HIP backward
 own backward a whole SEGNN layer has parameter gradients and forces.  With grad mode on inside a backward
 (``create_graph=True``) the same backward call runs as a second Function (``_*BackwardFn``) that has a backward of its own --
 the linear stages by composition (gather <-> its backward, segment sum <-> its backward), the gate, the edge geometry and the
-envelope on ``e3_gate_blocks_backward2``, ``e3_edge_geometry_jvp`` and ``e3_cutoff_envelope_backward2`` -- so a loss on the
-forces has parameter gradients; those Functions are once differentiable.  ROCm tensors only; no CPU path."""
+envelope on ``e3_gate_blocks_backward2``, ``e3_edge_geometry_jvp`` / ``e3_edge_geometry_hvp`` and
+``e3_cutoff_envelope_backward2`` -- so a loss on the forces has parameter gradients and the energy has Hessian-vector products
+in the positions; those Functions are once differentiable.  ROCm tensors only; no CPU path."""
 from __future__ import annotations
 
 import torch
@@ -82,25 +83,29 @@ class _EdgeGeometryFn(torch.autograd.Function):
     (e3_edge_geometry_backward_strained) returns the gradients of both pos and strain."""
 
     @staticmethod
-    def forward(ctx, pos, strain, g, lmax, structure):
+    def forward(ctx, pos, strain, g, lmax, structure, pos_hessian=True):
         pos4 = torch.zeros((pos.shape[0], 4), dtype=torch.float32, device=pos.device)
         pos4[:, :3] = pos
         Y, d, A = _edge_geometry_raw(pos4, g, True, True, lmax, strain=strain, structure=structure)
         ctx.g, ctx.lmax, ctx.structure = g, lmax, structure
-        ctx.save_for_backward(pos4, strain)
+        # the caller's pos itself (with its graph) is kept only where a second backward can use it
+        ctx.pos_hessian = bool(pos_hessian) and strain is None and ctx.needs_input_grad[0]
+        ctx.save_for_backward(pos4, strain, pos if ctx.pos_hessian else None)
         return Y, d, A
 
     @staticmethod
     def backward(ctx, gY, gd, gA):
-        pos4, strain = ctx.saved_tensors
+        pos4, strain, pos = ctx.saved_tensors
         g = ctx.g
-        if torch.is_grad_enabled():  # create_graph: the backward itself is differentiated (in gY, gd, gA; not in pos)
+        if torch.is_grad_enabled():  # create_graph: the backward itself is differentiated, in gY, gd, gA and -- unless the
+            # caller declined (pos_hessian=False) -- in pos: the saved input is the caller's tensor, with its graph
             if strain is not None:
                 raise NotImplementedError("second derivatives through a strained edge geometry (virial / stress under "
                                           "create_graph): the strained geometry has no tangent kernel")
-            return _EdgeGeometryBackwardFn.apply(pos4, gY, gd, gA, g, ctx.lmax), None, None, None, None
+            p = pos if ctx.pos_hessian else pos4  # pos4: a constant, no position edge
+            return _EdgeGeometryBackwardFn.apply(p, pos4, gY, gd, gA, g, ctx.lmax), None, None, None, None, None
         gpos, gstrain = _edge_geometry_backward_raw(pos4, strain, g, ctx.lmax, ctx.structure, gY, gd, gA)
-        return gpos, gstrain, None, None, None
+        return gpos, gstrain, None, None, None, None
 
 
 def _edge_geometry_backward_raw(pos4, strain, g, lmax, structure, gY, gd, gA):
@@ -147,28 +152,53 @@ def _edge_geometry_jvp_raw(pos4, g, lmax, v, want_y=True, want_d=True, want_a=Tr
     return dY, dd, dA
 
 
+def _edge_geometry_hvp_raw(pos4, g, lmax, gY, gd, gA, v):
+    """h_pos [N,3] = d<v, g_pos>/dpos of the unstrained geometry backward at (gY, gd, gA), each of them a tensor or None
+    (e3_edge_geometry_hvp): the Hessian of Y, d and A in the edge vector, applied to the displacement field v [N,3]."""
+    N = pos4.shape[0]
+    if g.num_edges == 0:  # no edge: g_pos does not depend on the positions
+        return torch.zeros((N, 3), dtype=torch.float32, device=pos4.device)
+    hpos = torch.empty((N, 3), dtype=torch.float32, device=pos4.device)
+    c = lambda t: t.contiguous() if t is not None else None
+    gY, gd, gA, v = c(gY), c(gd), c(gA), v.to(torch.float32).contiguous()
+    p = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(pos4.device):
+        name, pbc = g.entry("e3_edge_geometry_hvp")
+        _lib.call(name, pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, *pbc, p(gY), p(gd), p(gA),
+                  v.data_ptr(), hpos.data_ptr(), _stream(pos4))
+    return hpos
+
+
 class _EdgeGeometryBackwardFn(torch.autograd.Function):
-    """The unstrained backward of ``_EdgeGeometryFn`` as a differentiable op of (gY, gd, gA): it is linear in them, so its
-    backward is the tangent of the forward along the cotangent of g_pos (``e3_edge_geometry_jvp``).  The derivative w.r.t.
-    the positions themselves (the Hessian of Y, d, A in r) is not implemented: ``pos4`` gets no gradient from here, which a
-    parameter gradient of a loss on energies and forces never needs."""
+    """The unstrained backward of ``_EdgeGeometryFn`` as a differentiable op of (pos, gY, gd, gA).  It is linear in the three
+    gradients, so its backward in them is the tangent of the forward along the cotangent of g_pos
+    (``e3_edge_geometry_jvp``); in the positions it is the Hessian of Y, d and A in the edge vector applied to that cotangent
+    (``e3_edge_geometry_hvp``), launched only when ``pos`` requires grad -- a parameter gradient of a loss on energies and
+    forces never needs it, and the force-loss path (``pos_hessian=False``) hands in a constant in its place.  ``pos4`` is
+    the padded copy of ``pos`` the kernels read."""
 
     @staticmethod
-    def forward(ctx, pos4, gY, gd, gA, g, lmax):
+    def forward(ctx, pos, pos4, gY, gd, gA, g, lmax):
         ctx.g, ctx.lmax = g, lmax
-        ctx.save_for_backward(pos4)
+        gY, gd, gA = gY.contiguous(), gd.contiguous(), gA.contiguous()  # autograd hands in zeros for an unused output
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(pos4, gY, gd, gA)
+        else:
+            ctx.save_for_backward(pos4)
         return _edge_geometry_backward_raw(pos4, None, g, lmax, None, gY, gd, gA)[0]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, v):
-        (pos4,) = ctx.saved_tensors
-        dY, dd, dA = _edge_geometry_jvp_raw(pos4, ctx.g, ctx.lmax, v, *ctx.needs_input_grad[1:4])
-        return None, dY, dd, dA, None, None
+        pos4, *grads = ctx.saved_tensors
+        dY, dd, dA = _edge_geometry_jvp_raw(pos4, ctx.g, ctx.lmax, v, *ctx.needs_input_grad[2:5])
+        hpos = _edge_geometry_hvp_raw(pos4, ctx.g, ctx.lmax, *grads, v) if ctx.needs_input_grad[0] else None
+        return hpos, None, dY, dd, dA, None, None
 
 
 def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int = 1, pos: torch.Tensor | None = None,
-                  want_edge=True, strain: torch.Tensor | None = None, structure: torch.Tensor | None = None):
+                  want_edge=True, strain: torch.Tensor | None = None, structure: torch.Tensor | None = None,
+                  pos_hessian: bool = True):
     """-> Y [E,(lmax+1)^2] | None, d [E] | None, A [N,(lmax+1)^2] | None.  ``want_edge=False``: only the node attribute
     (the fused message kernel computes the spherical harmonics of its edges itself).
 
@@ -177,11 +207,14 @@ def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int
     (``g.box``, or a general cell ``g.cell``) takes the minimum image of every edge vector, so ``pos`` may be the
     unwrapped coordinates (moved by whole periods / lattice vectors).
 
-    Second derivatives: under ``create_graph=True`` the gradient w.r.t. ``pos`` is itself differentiable w.r.t. the
+    Second derivatives: under ``create_graph=True`` the gradient w.r.t. ``pos`` is itself differentiable, once: w.r.t. the
     gradients of Y, d and A that produced it (``e3_edge_geometry_jvp``) -- what the parameter gradient of a loss on the forces
-    needs -- but NOT w.r.t. ``pos``: the Hessian of Y, d, A in the edge vector is not implemented, and differentiating that
-    gradient once more w.r.t. ``pos`` gives only the part that flows through those three gradients, without the Hessian
-    term and without an error.  Do not take d(forces)/d(pos) from it.  With a ``strain`` it raises ``NotImplementedError``.
+    needs -- and w.r.t. ``pos`` (``e3_edge_geometry_hvp``: the Hessian of Y, d, A in the edge vector), so d(forces)/d(pos)
+    taken through it is the full second derivative on the edge set of ``g``.  ``pos_hessian=False`` declines the second of
+    the two: the gradient is then treated as a function of the three gradients alone and ``pos`` receives only what flows
+    through them -- for a caller that differentiates w.r.t. parameters only and has no use for a gradient in its position
+    leaf (the force-loss step of the energy models).  With a ``strain`` the second derivative raises
+    ``NotImplementedError``.
 
     ``strain`` [S,3,3] (or [3,3]: one structure), fp32 on the device, and ``structure`` [N] integer structure id of every
     row (graph order; None = every row is structure 0): every edge vector r of structure s (the structure of its dst row)
@@ -194,7 +227,7 @@ def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int
             raise ValueError("structure= is the structure of each row for a strain=; it needs strain=")
         if pos is not None and _wants_grad(pos):
             _check(pos, "pos")
-            return _EdgeGeometryFn.apply(pos, None, g, lmax, None)
+            return _EdgeGeometryFn.apply(pos, None, g, lmax, None, pos_hessian)
         pos4 = g.pos4
         if pos is not None:
             pos4 = torch.zeros_like(g.pos4)
@@ -204,7 +237,7 @@ def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int
     if pos is not None:
         _check(pos, "pos")
     if _wants_grad(pos, strain):
-        return _EdgeGeometryFn.apply(pos if pos is not None else g.pos4[:, :3], eps, g, lmax, sid)
+        return _EdgeGeometryFn.apply(pos if pos is not None else g.pos4[:, :3], eps, g, lmax, sid, pos_hessian)
     pos4 = g.pos4
     if pos is not None:
         pos4 = torch.zeros_like(g.pos4)

@@ -281,7 +281,8 @@ class SEGNN(nn.Module):
             return self._forward_enveloped(x, g, geometry, halo, split, cutoff)
         if x.dtype == torch.bfloat16 and self.lmax != 2:
             raise RuntimeError("bf16 storage is implemented for l_max = 2 (BASELINE config 3)")
-        needs_grad = torch.is_grad_enabled() and _needs_grad(self, x)
+        # a differentiable geometry needs the chain also when no parameter does (forces / Hessian of a frozen model)
+        needs_grad = torch.is_grad_enabled() and _needs_grad(self, x, *(t for t in geometry or () if t is not None))
         if split is not None:
             g = split.graph
         if geometry is not None:
