@@ -751,7 +751,8 @@ int e3_segment_sum_weighted_backward(const float* g_agg, int64_t ld_gagg, const 
  *       Each of g_edge_y, g_edge_d, g_node_a may be NULL (zeros), as in e3_edge_geometry_backward.  Edges with d = 0 and rows
  *       without edges contribute nothing.  h_pos [N,3] is zero-filled by the call.  One wave per dst row, lanes over its
  *       edges: fp32 atomics into h_pos[src], a wave reduction and one atomic per component for the dst row -- like g_pos, the
- *       result is NOT bit-reproducible on a general cloud (order of arrival).  There is no strained form.
+ *       result is NOT bit-reproducible on a general cloud (order of arrival).  The strained form is
+ *       e3_edge_geometry_hvp_strained below.
  *       E3_ERR_INVALID_ARG before any launch for lmax outside {1, 2}, N < 0, a NULL v or h_pos, an invalid box / cell, or
  *       (N > 0) a NULL rowptr, or a NULL pos4 with a src; N = 0, or a NULL src (a graph without edges): zero-fill only.
  *
@@ -786,6 +787,46 @@ int e3_edge_geometry_hvp_pbc(const float* pos4, const int32_t* rowptr, const int
 int e3_edge_geometry_hvp_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
                               const float cell[9], const float* g_edge_y, const float* g_edge_d, const float* g_node_a,
                               const float* v, float* h_pos, void* stream);
+/* The two entries above for the strained geometry: the backward of e3_edge_geometry_backward_strained (conventions of
+ * e3_edge_geometry_strained: r the unstrained edge vector, s the structure of the dst row, M = I + eps_s, r' = M r; box NULL
+ * = open box).  Cotangents v [N,3] of g_pos and xi [S,9] of g_strain (row-major as strain); either may be NULL (zeros), not
+ * both.  With t_e = v[src] - v[dst] the tangent of r' is
+ *   t'_e = M t_e + xi_s r_e.
+ *   e3_edge_geometry_jvp_strained : the cotangents of (g_edge_y, g_edge_d, g_node_a) are the outputs of e3_edge_geometry_jvp
+ *       with u, d taken at r' and t := t'.  Same NULL outputs, zeros and reproducibility as that entry.
+ *   e3_edge_geometry_hvp_strained : with g' = grad phi_e(r') (the first-order edge gradient) and w_e = (Hess phi_e)(r') t'_e
+ *       (the h_e formula of e3_edge_geometry_hvp at r'),
+ *         h_e = M^T w_e + xi_s^T g'_e;   h_pos[src] += h_e,  h_pos[dst] -= h_e;
+ *         h_strain[s][3 a + b] += (w_e)_a (r_e)_b + (g'_e)_a (t_e)_b.
+ *       h_pos [N,3] and h_strain [S,9] are zero-filled by the call; either may be NULL (not formed), not both.  h_strain is
+ *       reduced as g_strain is: S = 1 through `workspace` (e3_edge_geometry_backward_strained_workspace_bytes(N): the grid is
+ *       that of the strained backward) in a fixed order -- bit-equal from run to run; S > 1 one wave reduction per row and one
+ *       9-lane atomic (order of arrival).  h_pos: atomics, as e3_edge_geometry_hvp.
+ * A row whose structure id is outside [0, S) is computed unstrained (M = I, no xi r term) and adds nothing to h_strain; edges
+ * with d' = 0 and rows without edges contribute nothing and give zeros in the tangent.  At eps = 0 and xi = NULL the outputs
+ * equal the unstrained entries' (h_strain beside them: the derivative of <v, g_pos> in the strain).
+ * E3_ERR_INVALID_ARG before any launch for what the unstrained entries refuse (apart from a NULL v), strain NULL, S < 1, v and
+ * xi both NULL, (hvp) h_pos and h_strain both NULL, or, when S = 1, N > 0 and h_strain is given, a workspace that is NULL or
+ * too small.  N = 0, or (hvp) a NULL src: zero-fill only. */
+int e3_edge_geometry_jvp_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float* box, const float* strain, const int32_t* structure, int S, const float* v,
+                                  const float* xi, float* d_edge_y, float* d_edge_d, float* d_node_a, void* stream);
+/* general cell: as e3_edge_geometry_strained_cell */
+int e3_edge_geometry_jvp_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                       const float cell[9], const float* strain, const int32_t* structure, int S,
+                                       const float* v, const float* xi, float* d_edge_y, float* d_edge_d, float* d_node_a,
+                                       void* stream);
+int e3_edge_geometry_hvp_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float* box, const float* strain, const int32_t* structure, int S,
+                                  const float* g_edge_y, const float* g_edge_d, const float* g_node_a, const float* v,
+                                  const float* xi, float* h_pos, float* h_strain, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+/* general cell: as e3_edge_geometry_strained_cell */
+int e3_edge_geometry_hvp_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                       const float cell[9], const float* strain, const int32_t* structure, int S,
+                                       const float* g_edge_y, const float* g_edge_d, const float* g_node_a, const float* v,
+                                       const float* xi, float* h_pos, float* h_strain, void* workspace,
+                                       int64_t workspace_bytes, void* stream);
 int e3_gate_blocks_backward2(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, const float* c,
                              int64_t ld_c, float* cot_g_out, int64_t ld_cgout, float* cot_in, int64_t ld_cin, int64_t B,
                              int ns, int nblocks, const int32_t* ls, const int32_t* muls, void* stream);

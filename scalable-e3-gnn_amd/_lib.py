@@ -209,6 +209,18 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p]),
     "e3_edge_geometry_hvp_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p]),
+    # the strained pair (..., lmax, box | NULL or cell, strain, structure, S, [gY, gd, gA,] v, xi, outputs[, workspace, bytes],
+    # stream)
+    "e3_edge_geometry_jvp_strained": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ctypes.c_float), c_void_p,
+                                              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e3_edge_geometry_jvp_strained_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p,
+                                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e3_edge_geometry_hvp_strained": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ctypes.c_float), c_void_p,
+                                              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_edge_geometry_hvp_strained_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, Float9, c_void_p, c_void_p,
+                                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_int64, c_void_p]),
     "e3_gate_blocks_backward2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                          c_int64, c_int64, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]),
     "e3_cutoff_envelope_backward2": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float, c_int, c_void_p, c_void_p,

@@ -12,7 +12,9 @@ forces keep their graph: every stage's backward has a backward of its own (the m
 same entries; `e3_edge_geometry_jvp`, `e3_gate_blocks_backward2`, `e3_cutoff_envelope_backward2`), so a loss on energies
 AND forces has parameter gradients.  The derivative of the forces w.r.t. the positions needs one kernel
 more, the Hessian of Y, d, A in the edge vector (`e3_edge_geometry_hvp`): a parameter gradient never needs it and the
-force-loss step does not launch it; `hessian_vector_product` / `hessian` of the two models below do.
+force-loss step does not launch it; `hessian_vector_product` / `hessian` of the two models below do.  The strained forms of
+both kernels (`e3_edge_geometry_jvp_strained` / `_hvp_strained`) give the second derivative in the joint coordinates
+(pos, strain): `PeriodicEnergyModel.strain_hessian_vector_product` / `elastic_tensor` (Born term and force-strain coupling).
 Virials and stress are the derivative w.r.t. a zero strain per structure, reduced inside the same geometry backward
 (`e3_edge_geometry_backward_strained`); `PeriodicEnergyModel` is the periodic-box counterpart of `BatchedEnergyModel`.
 """
@@ -88,8 +90,9 @@ def _neighbors_graph(neighbors, pos, r, skin, defaults: dict):
     return neighbors.update(pos)
 
 
-_NO_SECOND_ORDER_STRAIN = ("create_graph=True with virial= / stress=: the strained edge geometry has no tangent kernel, so the "
-                           "virial and the stress cannot be trained on")
+_NO_SECOND_ORDER_STRAIN = ("create_graph=True with virial= / stress=: the tangent kernel of the strained edge geometry exists at "
+                           "ops.edge_geometry(strain=), but the stress loss is not wired at model level, so the virial and the "
+                           "stress cannot be trained on here")
 
 
 def _check_create_graph(net, x, forces: bool, strained: bool):
@@ -146,16 +149,22 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
 HESSIAN_MAX_ATOMS = 256   # hessian(): 3 N second backwards and a dense [N,3,N,3] result -- molecules and small cells
 
 
-def _hessian_vector_products(net, x_g, g, pos_g, v_g, cutoff_kw):
+def _hessian_vector_products(net, x_g, g, pos_g, v_g, cutoff_kw, xi=None, strained=False):
     """H v for every v of ``v_g`` [K,N,3] (graph order) -> [K,N,3], H = d2(sum of the scalar node readout)/dpos_g^2 on the
     edge set of ``g``.  One forward, one first backward with ``create_graph=True`` -- the geometry with its position edge
     (``ops.edge_geometry(pos_hessian=True)``) -- and one second backward per vector on the retained graph.  Only the
-    position leaf is differentiated: the parameters may be frozen and none of them gets a ``.grad``."""
+    position leaf is differentiated: the parameters may be frozen and none of them gets a ``.grad``.
+
+    ``strained`` (or an ``xi`` [K,3,3]): the same in the joint coordinates (pos_g, eps) at a zero strain eps of the whole graph
+    -> (h_pos [K,N,3], h_strain [K,3,3]) = the Hessian applied to (v, xi), either of which may be None (zero), not both."""
     from . import ops
     if x_g.dtype == torch.bfloat16:
         raise NotImplementedError("hessian_vector_product with bf16 storage: bf16 runs the fused inference kernels only and "
                                   "has no differentiable chain")
-    v_g = v_g.to(torch.float32)
+    strained = strained or xi is not None
+    v_g = v_g.to(torch.float32) if v_g is not None else None
+    xi = xi.to(torch.float32) if xi is not None else None
+    K = len(v_g) if v_g is not None else len(xi)
     # the parameters are constants of H v: frozen for the length of the call, so that no backward forms a weight gradient
     # or a weight cotangent that nobody reads (the Functions decide from requires_grad at forward time)
     trainable = [q for q in net.parameters() if q.requires_grad]
@@ -164,14 +173,23 @@ def _hessian_vector_products(net, x_g, g, pos_g, v_g, cutoff_kw):
     try:
         with torch.enable_grad():
             p = pos_g.detach().float().requires_grad_(True)
-            geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p)
+            eps = torch.zeros((1, 3, 3), dtype=torch.float32, device=p.device, requires_grad=True) if strained else None
+            leaves = [p] + ([eps] if strained else [])
+            geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p, strain=eps)
             e_node = net(x_g, g, geometry=geometry, **(cutoff_kw or {}))
-            (gpos,) = torch.autograd.grad(e_node[:, 0].sum(), [p], create_graph=True)
-        out = [torch.autograd.grad(gpos, [p], v, retain_graph=k + 1 < len(v_g))[0] for k, v in enumerate(v_g)]
+            first = torch.autograd.grad(e_node[:, 0].sum(), leaves, create_graph=True)
+        out = []
+        for k in range(K):
+            pairs = [(f, c[k]) for f, c in zip(first, (v_g, xi[:, None] if xi is not None else None)) if c is not None]
+            out.append(torch.autograd.grad([f for f, _ in pairs], leaves, [c for _, c in pairs], retain_graph=k + 1 < K))
     finally:
         for q in trainable:
             q.requires_grad_(True)
-    return torch.stack(out) if out else torch.zeros_like(v_g)
+    if not strained:
+        return torch.stack([o[0] for o in out]) if out else torch.zeros_like(v_g)
+    if not out:
+        return torch.zeros((0, *pos_g.shape), device=p.device), torch.zeros((0, 3, 3), device=p.device)
+    return torch.stack([o[0] for o in out]), torch.stack([o[1][0] for o in out])
 
 
 def _check_vectors(v, pos):
@@ -181,6 +199,38 @@ def _check_vectors(v, pos):
     if tuple(v.shape[-2:]) != tuple(pos.shape) or v.dim() not in (2, 3):
         raise ValueError(f"v must be [N,3] or [K,N,3] with N = {pos.shape[0]}, got {tuple(v.shape)}")
     return v.reshape(-1, *pos.shape)
+
+
+def _check_strain_vectors(v, strain_v, pos):
+    """v [N,3] | [K,N,3] | None and strain_v [3,3] | [K,3,3] | None -> (v [K,N,3] | None, strain_v [K,3,3] | None, whether the
+    caller's tensors carry no K); ValueError when both are None, a shape is wrong or the K's differ"""
+    if v is None and strain_v is None:
+        raise ValueError("strain_hessian_vector_product needs v= ([N,3] or [K,N,3]) or strain_v= ([3,3] or [K,3,3])")
+    if strain_v is not None and (tuple(strain_v.shape[-2:]) != (3, 3) or strain_v.dim() not in (2, 3)):
+        raise ValueError(f"strain_v must be [3,3] or [K,3,3], got {tuple(strain_v.shape)}")
+    vs = _check_vectors(v, pos) if v is not None else None
+    xs = strain_v.reshape(-1, 3, 3) if strain_v is not None else None
+    if vs is not None and xs is not None and (len(vs) != len(xs) or (v.dim() == 2) != (strain_v.dim() == 2)):
+        raise ValueError(f"v {tuple(v.shape)} and strain_v {tuple(strain_v.shape)} must hold the same number K of vectors")
+    single = (v if v is not None else strain_v).dim() == 2
+    return vs, xs, single
+
+
+VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
+
+
+def voigt(born: torch.Tensor) -> torch.Tensor:
+    """born [3,3,3,3] -> [6,6]: ``C[I,J] = sum_abcd born[a,b,c,d] S_I[a,b] S_J[c,d]`` with the symmetric strain basis
+    ``S_I = (e_a e_b^T + e_b e_a^T) / 2`` of the Voigt pair I = (a, b) in the order xx, yy, zz, yz, xz, xy -- the second
+    derivative in the Voigt strains with engineering shears (eps_ab = eps_ba = gamma / 2), i.e. the average of the four
+    index permutations of a shear entry."""
+    if tuple(born.shape) != (3, 3, 3, 3):
+        raise ValueError(f"born must be [3,3,3,3], got {tuple(born.shape)}")
+    basis = torch.zeros((6, 3, 3), dtype=born.dtype, device=born.device)
+    for i, (a, b) in enumerate(VOIGT):
+        basis[i, a, b] += 0.5
+        basis[i, b, a] += 0.5
+    return torch.einsum("iab,abcd,jcd->ij", basis, born, basis)
 
 
 def _dense_hessian(hvp, pos, chunk: int = 96):
@@ -234,8 +284,9 @@ class BatchedEnergyModel(nn.Module):
         ``create_graph=True`` (needs ``forces=True`` and a parameter that requires grad; fp32): energies and forces both
         carry a graph, in ``train()`` and ``eval()`` mode, so ``loss(energies, forces).backward()`` fills ``p.grad`` of
         every parameter -- training on forces.  The graph leads to the parameters only: the derivative of the forces
-        w.r.t. the positions is ``hessian_vector_product``.  ``NotImplementedError`` with ``virial=True`` (no tangent kernel for the
-        strained geometry) and for bf16 storage.  False (the default) is the first-order call, unchanged."""
+        w.r.t. the positions is ``hessian_vector_product``.  ``NotImplementedError`` with ``virial=True`` (the tangent kernel of the
+        strained geometry exists, ``ops.edge_geometry(strain=)``, but a loss on the virial is not wired at model level) and for
+        bf16 storage.  False (the default) is the first-order call, unchanged."""
         if create_graph:
             _check_create_graph(self.net, x, forces, virial)
         g, mol = self._graph(pos, batch, r, skin, neighbors)
@@ -316,8 +367,9 @@ class PeriodicEnergyModel(nn.Module):
         both carry a graph, in ``train()`` and ``eval()`` mode, so ``loss(energy, forces).backward()`` fills ``p.grad`` of
         every parameter -- training on forces -- for an open box, a box and ``cell=``, with or without ``envelope=``,
         ``skin=`` and ``neighbors=``.  The graph leads to the parameters only: the derivative of the forces w.r.t. the
-        positions is ``hessian_vector_product``.  ``NotImplementedError`` with ``virial=True`` / ``stress=True`` (no tangent kernel for the
-        strained geometry) and for bf16 storage.  False (the default) is the first-order call, unchanged."""
+        positions is ``hessian_vector_product``.  ``NotImplementedError`` with ``virial=True`` / ``stress=True`` (the tangent kernel of
+        the strained geometry exists, ``ops.edge_geometry(strain=)``, but a loss on the stress is not wired at model level) and
+        for bf16 storage.  False (the default) is the first-order call, unchanged."""
         if create_graph:
             _check_create_graph(self.net, x, forces, virial or stress)
         g, cut = self._graph(pos, r, lo, hi, periodic, cell, origin, skin, neighbors, stress)
@@ -374,6 +426,52 @@ class PeriodicEnergyModel(nn.Module):
         out = torch.empty_like(hv)
         out[:, perm] = hv
         return out.reshape(v.shape)
+
+    def _strain_hvp(self, x, pos, r, lo, hi, periodic, cell, origin, v, strain_v, skin, neighbors, stress):
+        """-> (h_pos [K,N,3] caller order, h_strain [K,3,3], whether the caller's vectors carry no K, the graph);
+        ``stress``: refuse an open axis as ``forward(stress=True)`` does"""
+        vs, xs, single = _check_strain_vectors(v, strain_v, pos)
+        g, cut = self._graph(pos, r, lo, hi, periodic, cell, origin, skin, neighbors, stress)
+        perm = g.perm.long()
+        hp, hs = _hessian_vector_products(self.net, x[perm], g, pos[perm], vs[:, perm] if vs is not None else None, cut,
+                                          xi=xs, strained=True)
+        out = torch.empty_like(hp)
+        out[:, perm] = hp
+        return out, hs, single, g
+
+    def strain_hessian_vector_product(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True,
+                                      cell=None, origin=None, v: torch.Tensor | None = None,
+                                      strain_v: torch.Tensor | None = None, skin: float = 0.0, neighbors=None):
+        """The Hessian of E in the joint coordinates (pos, eps) at eps = 0 -- eps the 3x3 strain of ``forward``'s virial, every
+        edge vector r of the current graph becoming r + eps r -- applied to (v, Xi):
+            h_pos = H v + Lambda Xi,   h_strain = Lambda^T v + B Xi,
+        H = d2E/dpos2 (``hessian_vector_product``), Lambda = d2E/dpos deps (the force-strain coupling) and B = d2E/deps deps
+        (the Born term, not divided by the volume).  ``v`` [N,3] or [K,N,3] (caller order), ``strain_v`` [3,3] or [K,3,3]; a
+        None is zero; ``ValueError`` if both are None or their K differ.  -> (h_pos [N,3], h_strain [3,3]), or ([K,N,3],
+        [K,3,3]) when the vectors carry a K; detached.  The graph arguments are those of ``forward``.  One forward, one first
+        backward with ``create_graph=True``, one second backward per pair (``e3_edge_geometry_jvp_strained`` /
+        ``e3_edge_geometry_hvp_strained`` close the chain).  Works on a frozen model in ``eval()``; no
+        parameter gets a ``.grad``.  fp32: bf16 storage raises ``NotImplementedError``."""
+        hp, hs, single, _ = self._strain_hvp(x, pos, r, lo, hi, periodic, cell, origin, v, strain_v, skin, neighbors, False)
+        return (hp[0], hs[0]) if single else (hp, hs)
+
+    def elastic_tensor(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, cell=None,
+                       origin=None, skin: float = 0.0, neighbors=None):
+        """-> (born [3,3,3,3], coupling [N,3,3,3]) of the current graph (the graph arguments of ``forward``):
+            born[a,b,c,d]     = (1/V) d2E/deps_ab deps_cd    the Born (clamped-ion) elastic tensor,
+            coupling[i,k,a,b] = d2E/dpos_ik deps_ab          the force-strain coupling (internal-strain tensor), caller order,
+        from ``strain_hessian_vector_product`` on the nine unit Xi: one forward, one first backward, nine second backwards.
+        All three axes must be periodic, as for ``stress=True`` (the same ``ValueError``); V as in ``forward`` (L_x L_y L_z or
+        |det cell|).  What it is NOT: it is the plain second derivative in the full 3x3 eps (nine independent components), not
+        symmetrised -- ``voigt(born)`` contracts it with the symmetric strain basis -- and at a stressed state it differs from
+        the stress-strain coefficients by terms in the stress.  The relaxed-ion constants are born - Lambda^T H^+ Lambda / V
+        with ``hessian()``, left to the caller."""
+        unit = torch.eye(9, dtype=torch.float32, device=pos.device).view(9, 3, 3)
+        hp, hs, _, g = self._strain_hvp(x, pos, r, lo, hi, periodic, cell, origin, None, unit, skin, neighbors, True)
+        V = float(g.volume) if g.cell is not None else float(g.box[0]) * float(g.box[1]) * float(g.box[2])
+        born = (hs.double() / V).float().view(3, 3, 3, 3).permute(2, 3, 0, 1).contiguous()   # hs[(c, d), a, b]
+        coupling = hp.view(3, 3, pos.shape[0], 3).permute(2, 3, 0, 1).contiguous()             # hp[(a, b), i, k]
+        return born, coupling
 
     def hessian(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, cell=None, origin=None,
                 skin: float = 0.0, neighbors=None) -> torch.Tensor:

@@ -280,13 +280,42 @@ __global__ __launch_bounds__(256) void gate_blocks_bwd2_kernel(const float* __re
 // is linear in (gY, gd, gA), so this is its backward w.r.t. those three.  t = v[src] - v[dst];  du = (t - u (u . t)) / d;
 //   dY1 = sqrt3 du,  dY2 = sqrt5 (db/du) du  (b as above),  dd = u . t,  dA_i = (1 / deg_i) sum over the row of dY_e.
 // One wave per row, lanes over its edges; dA: per-lane sums in edge order, then a fixed butterfly -- no atomics.
-template <int LMAX, int PBC>
+// STRAIN (e3_edge_geometry_jvp_strained): u and d are those of r' = (I + eps_s) r and the tangent of r' is
+// t' = (I + eps_s) t + Xi_s r, Xi [S,9] the cotangent of g_strain (r unstrained); v or Xi may be NULL (zeros).  eps_s and Xi_s
+// are read once per row with a wave-uniform structure id; a row outside [0, S) has eps = Xi = 0.
+//
+// What the strained tangent and Hessian kernels take besides the arguments of the unstrained ones.  It is passed as a
+// parameter pack that is empty in the unstrained kernels: a trailing parameter, even one of an empty type, would move their
+// hidden arguments, and they are to stay the code they were before the strained forms existed.
+struct StrainTangent {
+  StrainArg st;
+  const float* xi;   // [S,9] cotangent of g_strain | NULL
+  float* hstrain;    // hvp: [S,9] | NULL
+  float* hpart;      // hvp, S = 1: one 9-float partial per block
+};
+__device__ __forceinline__ const StrainTangent& only(const StrainTangent& sa) { return sa; }
+// Xi of structure s into registers (zero for s = -1 or without a Xi: no read)
+__device__ __forceinline__ void load_strain_cotangent(const float* xi, const int s, float x[9]) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) x[k] = (xi && s >= 0) ? xi[(int64_t)s * 9 + k] : 0.f;
+}
+// t <- (I + eps) t + Xi r
+__device__ __forceinline__ void strain_tangent(const float e[9], const float xi[9], const float rx, const float ry,
+                                               const float rz, float& tx, float& ty, float& tz) {
+  apply_strain(e, tx, ty, tz);
+  tx += xi[0] * rx + xi[1] * ry + xi[2] * rz;
+  ty += xi[3] * rx + xi[4] * ry + xi[5] * rz;
+  tz += xi[6] * rx + xi[7] * ry + xi[8] * rz;
+}
+
+template <int LMAX, int PBC, bool STRAIN, class... SA>
 __global__ __launch_bounds__(256) void edge_geometry_jvp_kernel(const float4* __restrict__ pos4,
                                                                 const int32_t* __restrict__ rowptr,
                                                                 const int32_t* __restrict__ src, int64_t N,
                                                                 const float* __restrict__ v, float* __restrict__ dY,
                                                                 float* __restrict__ dd, float* __restrict__ dA,
-                                                                const typename PbcArg<PBC>::type box) {
+                                                                const typename PbcArg<PBC>::type box, const SA... tail) {
+  static_assert(sizeof...(SA) == (STRAIN ? 1 : 0), "the strained kernels take one StrainTangent, the others nothing");
   constexpr int NY = (LMAX + 1) * (LMAX + 1);
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
@@ -298,7 +327,19 @@ __global__ __launch_bounds__(256) void edge_geometry_jvp_kernel(const float4* __
       continue;
     }
     const float4 pi = pos4[i];
-    const float vix = v[i * 3 + 0], viy = v[i * 3 + 1], viz = v[i * 3 + 2];
+    float vix, viy, viz;
+    if constexpr (STRAIN) {
+      vix = v ? v[i * 3 + 0] : 0.f; viy = v ? v[i * 3 + 1] : 0.f; viz = v ? v[i * 3 + 2] : 0.f;
+    } else {
+      vix = v[i * 3 + 0]; viy = v[i * 3 + 1]; viz = v[i * 3 + 2];
+    }
+    float eps[9], xi[9];
+    if constexpr (STRAIN) {
+      const StrainTangent& sa = only(tail...);
+      const int srow = row_structure(sa.st, i);
+      load_strain(sa.st, srow, eps);
+      load_strain_cotangent(sa.xi, srow, xi);
+    }
     float s[NY];
 #pragma unroll
     for (int k = 0; k < NY; ++k) s[k] = 0.f;
@@ -307,6 +348,8 @@ __global__ __launch_bounds__(256) void edge_geometry_jvp_kernel(const float4* __
       const float4 pj = pos4[j];
       float rx, ry, rz;
       edge_rel<PBC>(pj, pi, box, rx, ry, rz);
+      const float r0x = rx, r0y = ry, r0z = rz;
+      if constexpr (STRAIN) apply_strain(eps, rx, ry, rz);
       const float d = sqrtf(rx * rx + ry * ry + rz * rz);
       float o[NY], ddv = 0.f;
 #pragma unroll
@@ -314,7 +357,16 @@ __global__ __launch_bounds__(256) void edge_geometry_jvp_kernel(const float4* __
       if (d > 0.f) {
         const float inv = 1.0f / d;
         const float x = rx * inv, y = ry * inv, z = rz * inv;
-        const float tx = v[(int64_t)j * 3 + 0] - vix, ty = v[(int64_t)j * 3 + 1] - viy, tz = v[(int64_t)j * 3 + 2] - viz;
+        float tx, ty, tz;
+        if constexpr (STRAIN) {
+          tx = (v ? v[(int64_t)j * 3 + 0] : 0.f) - vix;
+          ty = (v ? v[(int64_t)j * 3 + 1] : 0.f) - viy;
+          tz = (v ? v[(int64_t)j * 3 + 2] : 0.f) - viz;
+          strain_tangent(eps, xi, r0x, r0y, r0z, tx, ty, tz);
+        } else {
+          (void)r0x; (void)r0y; (void)r0z;
+          tx = v[(int64_t)j * 3 + 0] - vix; ty = v[(int64_t)j * 3 + 1] - viy; tz = v[(int64_t)j * 3 + 2] - viz;
+        }
         ddv = x * tx + y * ty + z * tz;
         const float ux = (tx - x * ddv) * inv, uy = (ty - y * ddv) * inv, uz = (tz - z * ddv) * inv;
         o[1] = kS3 * ux; o[2] = kS3 * uy; o[3] = kS3 * uz;
@@ -354,33 +406,59 @@ __global__ __launch_bounds__(256) void edge_geometry_jvp_kernel(const float4* __
 // psi = a1 + Q u is the (ux, uy, uz) of the kernel above.  With P = I - u u^T, du = P t / d, dd = u . t:
 //   h = [ -(du (u . psi) + u (du . psi)) + P Q du ] / d  -  P psi dd / d^2  +  gd du
 // Same shape as the first-order kernel: one wave per row, atomics into hpos[src], one wave reduction per row for hpos[dst].
-template <int LMAX, int PBC>
+// STRAIN (e3_edge_geometry_hvp_strained; M = I + eps_s, Xi the cotangent of g_strain, r unstrained): the formula above at
+// r' = M r applied to t' = M t + Xi_s r gives w = (Hess phi)(r') t', and with g' = grad phi(r') = P psi / d + gd u
+//   h_e = M^T w + Xi_s^T g'  (into hpos as above),   hstrain[s] += w (x) r + g' (x) t  (t = v[src] - v[dst], unstrained),
+// reduced exactly as the first-order kernel reduces g_strain (S = 1: registers, LDS, one partial per block; S > 1: one wave
+// reduction per row and a 9-lane atomic).  v or Xi may be NULL (zeros), hpos or hstrain may be NULL (not formed).
+template <int LMAX, int PBC, bool STRAIN, class... SA>
 __global__ __launch_bounds__(256) void edge_geometry_hvp_kernel(const float4* __restrict__ pos4,
                                                                 const int32_t* __restrict__ rowptr,
                                                                 const int32_t* __restrict__ src, int64_t N,
                                                                 const float* __restrict__ gY, const float* __restrict__ gd,
                                                                 const float* __restrict__ gA, const float* __restrict__ v,
                                                                 float* __restrict__ hpos,
-                                                                const typename PbcArg<PBC>::type box) {
+                                                                const typename PbcArg<PBC>::type box, const SA... tail) {
+  static_assert(sizeof...(SA) == (STRAIN ? 1 : 0), "the strained kernels take one StrainTangent, the others nothing");
   constexpr int NY = (LMAX + 1) * (LMAX + 1);
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  float G[9];
+  if constexpr (STRAIN) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = 0.f;
+  }
   for (int64_t i = wave0; i < N; i += nw) {
     const int b = rowptr[i], e = rowptr[i + 1];
     if (b == e) continue;
     const float4 pi = pos4[i];
-    const float vix = v[i * 3 + 0], viy = v[i * 3 + 1], viz = v[i * 3 + 2];
+    float vix, viy, viz;
+    if constexpr (STRAIN) {
+      vix = v ? v[i * 3 + 0] : 0.f; viy = v ? v[i * 3 + 1] : 0.f; viz = v ? v[i * 3 + 2] : 0.f;
+    } else {
+      vix = v[i * 3 + 0]; viy = v[i * 3 + 1]; viz = v[i * 3 + 2];
+    }
     const float invdeg = 1.0f / (float)(e - b);
     float ga[NY];
 #pragma unroll
     for (int k = 1; k < NY; ++k) ga[k] = gA ? gA[i * NY + k] * invdeg : 0.f;
+    int srow = 0;
+    float eps[9], xi[9];
+    if constexpr (STRAIN) {
+      const StrainTangent& sa = only(tail...);
+      srow = row_structure(sa.st, i);
+      load_strain(sa.st, srow, eps);
+      load_strain_cotangent(sa.xi, srow, xi);
+    }
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int q = b + lane; q < e; q += 64) {
       const int j = src[q];
       const float4 pj = pos4[j];
       float rx, ry, rz;
       edge_rel<PBC>(pj, pi, box, rx, ry, rz);
+      const float r0x = rx, r0y = ry, r0z = rz;
+      if constexpr (STRAIN) apply_strain(eps, rx, ry, rz);
       const float d = sqrtf(rx * rx + ry * ry + rz * rz);
       if (!(d > 0.f)) continue;
       const float inv = 1.0f / d;
@@ -388,7 +466,17 @@ __global__ __launch_bounds__(256) void edge_geometry_hvp_kernel(const float4* __
       float g[NY];
 #pragma unroll
       for (int k = 1; k < NY; ++k) g[k] = (gY ? gY[(int64_t)q * NY + k] : 0.f) + ga[k];
-      const float tx = v[(int64_t)j * 3 + 0] - vix, ty = v[(int64_t)j * 3 + 1] - viy, tz = v[(int64_t)j * 3 + 2] - viz;
+      float tx, ty, tz;
+      float t0x = 0.f, t0y = 0.f, t0z = 0.f;  // STRAIN: the unstrained t
+      if constexpr (STRAIN) {
+        tx = t0x = (v ? v[(int64_t)j * 3 + 0] : 0.f) - vix;
+        ty = t0y = (v ? v[(int64_t)j * 3 + 1] : 0.f) - viy;
+        tz = t0z = (v ? v[(int64_t)j * 3 + 2] : 0.f) - viz;
+        strain_tangent(eps, xi, r0x, r0y, r0z, tx, ty, tz);
+      } else {
+        (void)r0x; (void)r0y; (void)r0z; (void)t0x; (void)t0y; (void)t0z;
+        tx = v[(int64_t)j * 3 + 0] - vix; ty = v[(int64_t)j * 3 + 1] - viy; tz = v[(int64_t)j * 3 + 2] - viz;
+      }
       const float dd = x * tx + y * ty + z * tz;
       const float dux = (tx - x * dd) * inv, duy = (ty - y * dd) * inv, duz = (tz - z * dd) * inv;
       float px = kS3 * g[1], py = kS3 * g[2], pz = kS3 * g[3];  // psi
@@ -409,12 +497,33 @@ __global__ __launch_bounds__(256) void edge_geometry_hvp_kernel(const float4* __
       const float gdv = gd ? gd[q] : 0.f;
       const float c = gdv - up * inv, s = dd * inv * inv;
       // [P Q du - du (u . psi) - u (du . psi)] / d - (psi - u (u . psi)) dd / d^2 + gd du
-      const float hx = (wx - x * (uw + dp)) * inv + c * dux - (px - x * up) * s;
-      const float hy = (wy - y * (uw + dp)) * inv + c * duy - (py - y * up) * s;
-      const float hz = (wz - z * (uw + dp)) * inv + c * duz - (pz - z * up) * s;
-      atomicAdd(hpos + (int64_t)j * 3 + 0, hx);
-      atomicAdd(hpos + (int64_t)j * 3 + 1, hy);
-      atomicAdd(hpos + (int64_t)j * 3 + 2, hz);
+      float hx = (wx - x * (uw + dp)) * inv + c * dux - (px - x * up) * s;
+      float hy = (wy - y * (uw + dp)) * inv + c * duy - (py - y * up) * s;
+      float hz = (wz - z * (uw + dp)) * inv + c * duz - (pz - z * up) * s;
+      if constexpr (STRAIN) {
+        // g' = grad phi at r': (psi - u (u . psi)) / d + gd u
+        const float gx = (px - x * up) * inv + gdv * x, gy = (py - y * up) * inv + gdv * y,
+                    gz = (pz - z * up) * inv + gdv * z;
+        if (srow >= 0) {
+          G[0] += hx * r0x + gx * t0x; G[1] += hx * r0y + gx * t0y; G[2] += hx * r0z + gx * t0z;
+          G[3] += hy * r0x + gy * t0x; G[4] += hy * r0y + gy * t0y; G[5] += hy * r0z + gy * t0z;
+          G[6] += hz * r0x + gz * t0x; G[7] += hz * r0y + gz * t0y; G[8] += hz * r0z + gz * t0z;
+        }
+        // M^T w + Xi^T g'
+        const float mx = hx + (eps[0] * hx + eps[3] * hy + eps[6] * hz) + (xi[0] * gx + xi[3] * gy + xi[6] * gz);
+        const float my = hy + (eps[1] * hx + eps[4] * hy + eps[7] * hz) + (xi[1] * gx + xi[4] * gy + xi[7] * gz);
+        const float mz = hz + (eps[2] * hx + eps[5] * hy + eps[8] * hz) + (xi[2] * gx + xi[5] * gy + xi[8] * gz);
+        hx = mx; hy = my; hz = mz;
+        if (hpos) {
+          atomicAdd(hpos + (int64_t)j * 3 + 0, hx);
+          atomicAdd(hpos + (int64_t)j * 3 + 1, hy);
+          atomicAdd(hpos + (int64_t)j * 3 + 2, hz);
+        }
+      } else {
+        atomicAdd(hpos + (int64_t)j * 3 + 0, hx);
+        atomicAdd(hpos + (int64_t)j * 3 + 1, hy);
+        atomicAdd(hpos + (int64_t)j * 3 + 2, hz);
+      }
       sx += hx; sy += hy; sz += hz;
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -422,10 +531,39 @@ __global__ __launch_bounds__(256) void edge_geometry_hvp_kernel(const float4* __
       sy += __shfl_xor(sy, o);
       sz += __shfl_xor(sz, o);
     }
-    if (lane == 0) {
+    if (lane == 0 && (!STRAIN || hpos)) {
       atomicAdd(hpos + i * 3 + 0, -sx);
       atomicAdd(hpos + i * 3 + 1, -sy);
       atomicAdd(hpos + i * 3 + 2, -sz);
+    }
+    if constexpr (STRAIN) {
+      const StrainTangent& sa = only(tail...);
+      if (sa.st.S > 1 && srow >= 0 && sa.hstrain) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          for (int o = 32; o > 0; o >>= 1) G[k] += __shfl_xor(G[k], o);
+          if (lane == k) a = G[k];
+          G[k] = 0.f;
+        }
+        if (lane < 9) atomicAdd(sa.hstrain + (int64_t)srow * 9 + lane, a);
+      }
+    }
+  }
+  if constexpr (STRAIN) {
+    const StrainTangent& sa = only(tail...);
+    if (sa.st.S == 1 && sa.hstrain) {
+      __shared__ float part[4][9];
+      const int w = threadIdx.x >> 6;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        for (int o = 32; o > 0; o >>= 1) G[k] += __shfl_xor(G[k], o);
+        if (lane == 0) part[w][k] = G[k];
+      }
+      __syncthreads();
+      if (threadIdx.x < 9)
+        sa.hpart[(int64_t)blockIdx.x * 9 + threadIdx.x] =
+            ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
     }
   }
 }
@@ -499,9 +637,26 @@ static int edge_geometry_jvp(const float* pos4, const int32_t* rowptr, const int
   if (N < 0 || (lmax != 1 && lmax != 2)) return E3_ERR_INVALID_ARG;
   if (N == 0 || (!d_edge_y && !d_edge_d && !d_node_a)) return E3_OK;
   if (!pos4 || !rowptr || !src || !v) return E3_ERR_INVALID_ARG;
-  auto kern = lmax == 1 ? edge_geometry_jvp_kernel<1, PBC> : edge_geometry_jvp_kernel<2, PBC>;
+  auto kern = lmax == 1 ? edge_geometry_jvp_kernel<1, PBC, false> : edge_geometry_jvp_kernel<2, PBC, false>;
   hipLaunchKernelGGL(kern, dim3(wave_grid_b(N)), dim3(256), 0, (hipStream_t)stream, (const float4*)pos4, rowptr, src, N, v,
                      d_edge_y, d_edge_d, d_node_a, b);
+  E3_HIP_CHECK(hipGetLastError());
+  return E3_OK;
+}
+
+// the strained tangent in one periodicity mode (box: the mode's kernel argument, validated by the caller)
+template <int PBC>
+static int edge_geometry_jvp_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                      const float* strain, const int32_t* structure, int S, const float* v, const float* xi,
+                                      float* d_edge_y, float* d_edge_d, float* d_node_a,
+                                      const typename PbcArg<PBC>::type& b, void* stream) {
+  if (N < 0 || (lmax != 1 && lmax != 2) || !strain || S < 1 || (!v && !xi)) return E3_ERR_INVALID_ARG;
+  if (N == 0 || (!d_edge_y && !d_edge_d && !d_node_a)) return E3_OK;
+  if (!pos4 || !rowptr || !src) return E3_ERR_INVALID_ARG;
+  auto kern = lmax == 1 ? edge_geometry_jvp_kernel<1, PBC, true, StrainTangent>
+                        : edge_geometry_jvp_kernel<2, PBC, true, StrainTangent>;
+  hipLaunchKernelGGL(kern, dim3(wave_grid_b(N)), dim3(256), 0, (hipStream_t)stream, (const float4*)pos4, rowptr, src, N, v,
+                     d_edge_y, d_edge_d, d_node_a, b, StrainTangent{{strain, structure, S}, xi, nullptr, nullptr});
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }
@@ -517,10 +672,42 @@ static int edge_geometry_hvp(const float* pos4, const int32_t* rowptr, const int
   hipStream_t s = (hipStream_t)stream;
   E3_HIP_CHECK(hipMemsetAsync(h_pos, 0, (size_t)N * 3 * sizeof(float), s));
   if (!src) return E3_OK;  // a graph without edges has no src to hand over: every row is empty
-  auto kern = lmax == 1 ? edge_geometry_hvp_kernel<1, PBC> : edge_geometry_hvp_kernel<2, PBC>;
+  auto kern = lmax == 1 ? edge_geometry_hvp_kernel<1, PBC, false> : edge_geometry_hvp_kernel<2, PBC, false>;
   hipLaunchKernelGGL(kern, dim3(wave_grid_b(N)), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d,
                      g_node_a, v, h_pos, b);
   E3_HIP_CHECK(hipGetLastError());
+  return E3_OK;
+}
+
+// the strained Hessian in one periodicity mode (box: the mode's kernel argument, validated by the caller); the grid is the
+// one of the strained backward, so its workspace serves
+template <int PBC>
+static int edge_geometry_hvp_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                      const float* strain, const int32_t* structure, int S, const float* g_edge_y,
+                                      const float* g_edge_d, const float* g_node_a, const float* v, const float* xi,
+                                      float* h_pos, float* h_strain, void* workspace, int64_t workspace_bytes,
+                                      const typename PbcArg<PBC>::type& b, void* stream) {
+  if (N < 0 || (lmax != 1 && lmax != 2) || !strain || S < 1 || (!v && !xi) || (!h_pos && !h_strain))
+    return E3_ERR_INVALID_ARG;
+  if (S == 1 && N > 0 && h_strain &&
+      (!workspace || workspace_bytes < e3_edge_geometry_backward_strained_workspace_bytes(N)))
+    return E3_ERR_INVALID_ARG;
+  if (N > 0 && (!rowptr || (src && !pos4))) return E3_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (h_strain) E3_HIP_CHECK(hipMemsetAsync(h_strain, 0, (size_t)S * 9 * sizeof(float), s));
+  if (N == 0) return E3_OK;
+  if (h_pos) E3_HIP_CHECK(hipMemsetAsync(h_pos, 0, (size_t)N * 3 * sizeof(float), s));
+  if (!src) return E3_OK;  // a graph without edges has no src to hand over: every row is empty
+  const int grid = wave_grid_b(N);
+  auto kern = lmax == 1 ? edge_geometry_hvp_kernel<1, PBC, true, StrainTangent>
+                        : edge_geometry_hvp_kernel<2, PBC, true, StrainTangent>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const float4*)pos4, rowptr, src, N, g_edge_y, g_edge_d, g_node_a, v,
+                     h_pos, b, StrainTangent{{strain, structure, S}, xi, h_strain, (float*)workspace});
+  E3_HIP_CHECK(hipGetLastError());
+  if (S == 1 && h_strain) {
+    hipLaunchKernelGGL(strain_partial_sum_kernel, dim3(1), dim3(576), 0, s, (const float*)workspace, grid, h_strain);
+    E3_HIP_CHECK(hipGetLastError());
+  }
   return E3_OK;
 }
 
@@ -566,6 +753,51 @@ int e3_edge_geometry_jvp_cell(const float* pos4, const int32_t* rowptr, const in
   PbcCell c;
   if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
   return edge_geometry_jvp<kCell>(pos4, rowptr, src, N, lmax, v, d_edge_y, d_edge_d, d_node_a, c, stream);
+}
+
+int e3_edge_geometry_jvp_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float* box, const float* strain, const int32_t* structure, int S, const float* v,
+                                  const float* xi, float* d_edge_y, float* d_edge_d, float* d_node_a, void* stream) {
+  if (box && !box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
+  const PbcBox b = make_box(box);
+  return box ? edge_geometry_jvp_strained<kBox>(pos4, rowptr, src, N, lmax, strain, structure, S, v, xi, d_edge_y, d_edge_d,
+                                                d_node_a, b, stream)
+             : edge_geometry_jvp_strained<kOpen>(pos4, rowptr, src, N, lmax, strain, structure, S, v, xi, d_edge_y, d_edge_d,
+                                                 d_node_a, b, stream);
+}
+
+int e3_edge_geometry_jvp_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                       const float cell[9], const float* strain, const int32_t* structure, int S,
+                                       const float* v, const float* xi, float* d_edge_y, float* d_edge_d, float* d_node_a,
+                                       void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_jvp_strained<kCell>(pos4, rowptr, src, N, lmax, strain, structure, S, v, xi, d_edge_y, d_edge_d,
+                                           d_node_a, c, stream);
+}
+
+int e3_edge_geometry_hvp_strained(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                  const float* box, const float* strain, const int32_t* structure, int S,
+                                  const float* g_edge_y, const float* g_edge_d, const float* g_node_a, const float* v,
+                                  const float* xi, float* h_pos, float* h_strain, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+  if (box && !box_valid(box, 0.0f)) return E3_ERR_INVALID_ARG;
+  const PbcBox b = make_box(box);
+  return box ? edge_geometry_hvp_strained<kBox>(pos4, rowptr, src, N, lmax, strain, structure, S, g_edge_y, g_edge_d,
+                                                g_node_a, v, xi, h_pos, h_strain, workspace, workspace_bytes, b, stream)
+             : edge_geometry_hvp_strained<kOpen>(pos4, rowptr, src, N, lmax, strain, structure, S, g_edge_y, g_edge_d,
+                                                 g_node_a, v, xi, h_pos, h_strain, workspace, workspace_bytes, b, stream);
+}
+
+int e3_edge_geometry_hvp_strained_cell(const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, int lmax,
+                                       const float cell[9], const float* strain, const int32_t* structure, int S,
+                                       const float* g_edge_y, const float* g_edge_d, const float* g_node_a, const float* v,
+                                       const float* xi, float* h_pos, float* h_strain, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+  PbcCell c;
+  if (!make_cell(cell, 0.0f, &c)) return E3_ERR_INVALID_ARG;
+  return edge_geometry_hvp_strained<kCell>(pos4, rowptr, src, N, lmax, strain, structure, S, g_edge_y, g_edge_d, g_node_a,
+                                           v, xi, h_pos, h_strain, workspace, workspace_bytes, c, stream);
 }
 
 int e3_gate_blocks_backward2(const float* in, int64_t ld_in, const float* g_out, int64_t ld_gout, const float* c,

@@ -4,9 +4,9 @@ fp32.  Every op is differentiable (torch.autograd.Function over the HIP backward
 own backward a whole SEGNN layer has parameter gradients and forces.  With grad mode on inside a backward
 (``create_graph=True``) the same backward call runs as a second Function (``_*BackwardFn``) that has a backward of its own --
 the linear stages by composition (gather <-> its backward, segment sum <-> its backward), the gate, the edge geometry and the
-envelope on ``e3_gate_blocks_backward2``, ``e3_edge_geometry_jvp`` / ``e3_edge_geometry_hvp`` and
-``e3_cutoff_envelope_backward2`` -- so a loss on the forces has parameter gradients and the energy has Hessian-vector products
-in the positions; those Functions are once differentiable.  ROCm tensors only; no CPU path."""
+envelope on ``e3_gate_blocks_backward2``, ``e3_edge_geometry_jvp`` / ``e3_edge_geometry_hvp`` (and their ``_strained`` forms)
+and ``e3_cutoff_envelope_backward2`` -- so a loss on the forces has parameter gradients and the energy has Hessian-vector
+products in the positions and in a strain; those Functions are once differentiable.  ROCm tensors only; no CPU path."""
 from __future__ import annotations
 
 import torch
@@ -89,8 +89,8 @@ class _EdgeGeometryFn(torch.autograd.Function):
         Y, d, A = _edge_geometry_raw(pos4, g, True, True, lmax, strain=strain, structure=structure)
         ctx.g, ctx.lmax, ctx.structure = g, lmax, structure
         # the caller's pos itself (with its graph) is kept only where a second backward can use it
-        ctx.pos_hessian = bool(pos_hessian) and strain is None and ctx.needs_input_grad[0]
-        ctx.save_for_backward(pos4, strain, pos if ctx.pos_hessian else None)
+        ctx.pos_hessian = bool(pos_hessian)
+        ctx.save_for_backward(pos4, strain, pos if (ctx.pos_hessian and ctx.needs_input_grad[0]) else None)
         return Y, d, A
 
     @staticmethod
@@ -98,12 +98,12 @@ class _EdgeGeometryFn(torch.autograd.Function):
         pos4, strain, pos = ctx.saved_tensors
         g = ctx.g
         if torch.is_grad_enabled():  # create_graph: the backward itself is differentiated, in gY, gd, gA and -- unless the
-            # caller declined (pos_hessian=False) -- in pos: the saved input is the caller's tensor, with its graph
-            if strain is not None:
-                raise NotImplementedError("second derivatives through a strained edge geometry (virial / stress under "
-                                          "create_graph): the strained geometry has no tangent kernel")
-            p = pos if ctx.pos_hessian else pos4  # pos4: a constant, no position edge
-            return _EdgeGeometryBackwardFn.apply(p, pos4, gY, gd, gA, g, ctx.lmax), None, None, None, None, None
+            # caller declined (pos_hessian=False) -- in pos and strain: the saved inputs are the caller's tensors, with
+            # their graph
+            p = pos if pos is not None else pos4  # pos4: a constant, no position edge
+            eps = strain if (strain is None or ctx.pos_hessian) else strain.detach()
+            gpos, gstrain = _EdgeGeometryBackwardFn.apply(p, eps, pos4, gY, gd, gA, g, ctx.lmax, ctx.structure)
+            return gpos, gstrain, None, None, None, None
         gpos, gstrain = _edge_geometry_backward_raw(pos4, strain, g, ctx.lmax, ctx.structure, gY, gd, gA)
         return gpos, gstrain, None, None, None, None
 
@@ -122,8 +122,7 @@ def _edge_geometry_backward_raw(pos4, strain, g, lmax, structure, gY, gd, gA):
         head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax)
         if strain is not None:
             gstrain = torch.empty_like(strain)
-            ws = torch.empty(max(1, _lib.load().e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
-                             device=pos4.device)
+            ws = _strain_workspace(N, pos4.device)
             name, pbc = g.entry("e3_edge_geometry_backward_strained", strained=True)
             _lib.call(name, *head, *pbc, strain.data_ptr(), p(structure), strain.shape[0], p(gY), p(gd), p(gA),
                       gpos.data_ptr(), gstrain.data_ptr(), ws.data_ptr(), ws.numel(), _stream(pos4))
@@ -133,8 +132,17 @@ def _edge_geometry_backward_raw(pos4, strain, g, lmax, structure, gY, gd, gA):
     return gpos, gstrain
 
 
-def _edge_geometry_jvp_raw(pos4, g, lmax, v, want_y=True, want_d=True, want_a=True):
-    """Tangent of (Y, d, A) along the displacement field v [N,3] (e3_edge_geometry_jvp) -> dY | None, dd | None, dA | None."""
+def _strain_workspace(N, device):
+    """the workspace of the strained backward and of the strained Hessian (one 9-float partial per workgroup)"""
+    return torch.empty(max(1, _lib.load().e3_edge_geometry_backward_strained_workspace_bytes(N)), dtype=torch.uint8,
+                       device=device)
+
+
+def _edge_geometry_jvp_raw(pos4, g, lmax, v, want_y=True, want_d=True, want_a=True, strain=None, structure=None,
+                           xi=None):
+    """Tangent of (Y, d, A) along the displacement field v [N,3] (e3_edge_geometry_jvp) -> dY | None, dd | None, dA | None.
+    With a ``strain`` [S,3,3] (``structure`` int32 [N] | None): the tangent of the strained geometry along v and the strain
+    tangent ``xi`` [S,3,3], either of them None = zero (e3_edge_geometry_jvp_strained)."""
     N, E, dev = pos4.shape[0], g.num_edges, pos4.device
     ny = (lmax + 1) ** 2
     if E == 0:  # nothing to launch on: no output depends on the positions
@@ -143,12 +151,18 @@ def _edge_geometry_jvp_raw(pos4, g, lmax, v, want_y=True, want_d=True, want_a=Tr
     dY = torch.empty((E, ny), dtype=torch.float32, device=dev) if want_y else None
     dd = torch.empty(E, dtype=torch.float32, device=dev) if want_d else None
     dA = torch.empty((N, ny), dtype=torch.float32, device=dev) if want_a else None
-    v = v.to(torch.float32).contiguous()
+    c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
+    v, xi = c(v), c(xi)
     p = lambda t: t.data_ptr() if t is not None else None
     with torch.cuda.device(dev):
-        name, pbc = g.entry("e3_edge_geometry_jvp")
-        _lib.call(name, pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, *pbc, v.data_ptr(), p(dY), p(dd),
-                  p(dA), _stream(pos4))
+        head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax)
+        if strain is not None:
+            name, pbc = g.entry("e3_edge_geometry_jvp_strained", strained=True)
+            _lib.call(name, *head, *pbc, strain.data_ptr(), p(structure), strain.shape[0], p(v), p(xi), p(dY), p(dd), p(dA),
+                      _stream(pos4))
+        else:
+            name, pbc = g.entry("e3_edge_geometry_jvp")
+            _lib.call(name, *head, *pbc, v.data_ptr(), p(dY), p(dd), p(dA), _stream(pos4))
     return dY, dd, dA
 
 
@@ -169,31 +183,67 @@ def _edge_geometry_hvp_raw(pos4, g, lmax, gY, gd, gA, v):
     return hpos
 
 
+def _edge_geometry_hvp_strained_raw(pos4, strain, g, lmax, structure, gY, gd, gA, v, xi, want_pos=True, want_strain=True):
+    """(h_pos [N,3] | None, h_strain [S,3,3] | None) = the derivative of <v, g_pos> + <xi, g_strain> of the strained geometry
+    backward at (gY, gd, gA) in (pos, strain) (e3_edge_geometry_hvp_strained); ``v`` [N,3] or ``xi`` [S,3,3] may be None
+    (zero), not both."""
+    N, dev = pos4.shape[0], pos4.device
+    hpos = torch.empty((N, 3), dtype=torch.float32, device=dev) if want_pos else None
+    hstrain = torch.empty_like(strain) if want_strain else None
+    if g.num_edges == 0:  # no edge: neither gradient depends on pos or strain
+        return (hpos.zero_() if want_pos else None), (hstrain.zero_() if want_strain else None)
+    c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
+    gY, gd, gA, v, xi = c(gY), c(gd), c(gA), c(v), c(xi)
+    p = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        ws = _strain_workspace(N, dev)
+        name, pbc = g.entry("e3_edge_geometry_hvp_strained", strained=True)
+        _lib.call(name, pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, *pbc, strain.data_ptr(), p(structure),
+                  strain.shape[0], p(gY), p(gd), p(gA), p(v), p(xi), p(hpos), p(hstrain), ws.data_ptr(), ws.numel(),
+                  _stream(pos4))
+    return hpos, hstrain
+
+
 class _EdgeGeometryBackwardFn(torch.autograd.Function):
-    """The unstrained backward of ``_EdgeGeometryFn`` as a differentiable op of (pos, gY, gd, gA).  It is linear in the three
-    gradients, so its backward in them is the tangent of the forward along the cotangent of g_pos
-    (``e3_edge_geometry_jvp``); in the positions it is the Hessian of Y, d and A in the edge vector applied to that cotangent
-    (``e3_edge_geometry_hvp``), launched only when ``pos`` requires grad -- a parameter gradient of a loss on energies and
-    forces never needs it, and the force-loss path (``pos_hessian=False``) hands in a constant in its place.  ``pos4`` is
-    the padded copy of ``pos`` the kernels read."""
+    """The backward of ``_EdgeGeometryFn``, unstrained (``strain`` None) or strained, as a differentiable op of (pos, strain,
+    gY, gd, gA) -> (g_pos, g_strain | None).  It is linear in the three gradients, so its backward in them is the tangent of
+    the forward along the cotangents (v, Xi) of (g_pos, g_strain) (``e3_edge_geometry_jvp`` / ``_jvp_strained``); in the
+    positions and the strain it is the Hessian of Y, d and A in the edge vector applied to those cotangents
+    (``e3_edge_geometry_hvp`` / ``_hvp_strained``), launched only when ``pos`` or ``strain`` requires grad -- a parameter
+    gradient of a loss on energies, forces and stress never needs it, and that path (``pos_hessian=False``) hands in constants
+    in their place.  Either cotangent may be absent (None: zeros).  ``pos4`` is the padded copy of ``pos`` the kernels read."""
 
     @staticmethod
-    def forward(ctx, pos, pos4, gY, gd, gA, g, lmax):
-        ctx.g, ctx.lmax = g, lmax
+    def forward(ctx, pos, strain, pos4, gY, gd, gA, g, lmax, structure):
+        ctx.g, ctx.lmax, ctx.structure = g, lmax, structure
+        ctx.set_materialize_grads(False)
         gY, gd, gA = gY.contiguous(), gd.contiguous(), gA.contiguous()  # autograd hands in zeros for an unused output
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(pos4, gY, gd, gA)
+        ctx.hessian = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        if ctx.hessian:
+            ctx.save_for_backward(pos4, strain, gY, gd, gA)
         else:
-            ctx.save_for_backward(pos4)
-        return _edge_geometry_backward_raw(pos4, None, g, lmax, None, gY, gd, gA)[0]
+            ctx.save_for_backward(pos4, strain)
+        return _edge_geometry_backward_raw(pos4, strain, g, lmax, structure, gY, gd, gA)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, v):
-        pos4, *grads = ctx.saved_tensors
-        dY, dd, dA = _edge_geometry_jvp_raw(pos4, ctx.g, ctx.lmax, v, *ctx.needs_input_grad[2:5])
-        hpos = _edge_geometry_hvp_raw(pos4, ctx.g, ctx.lmax, *grads, v) if ctx.needs_input_grad[0] else None
-        return hpos, None, dY, dd, dA, None, None
+    def backward(ctx, v, xi):
+        pos4, strain, *grads = ctx.saved_tensors
+        g, lmax, sid = ctx.g, ctx.lmax, ctx.structure
+        if v is None and xi is None:
+            return (None,) * 9
+        want = ctx.needs_input_grad
+        hpos = hstrain = None
+        if strain is None:
+            dY, dd, dA = _edge_geometry_jvp_raw(pos4, g, lmax, v, *want[3:6])
+            if want[0]:
+                hpos = _edge_geometry_hvp_raw(pos4, g, lmax, *grads, v)
+        else:
+            strain = strain.detach()
+            dY, dd, dA = _edge_geometry_jvp_raw(pos4, g, lmax, v, *want[3:6], strain=strain, structure=sid, xi=xi)
+            if ctx.hessian:
+                hpos, hstrain = _edge_geometry_hvp_strained_raw(pos4, strain, g, lmax, sid, *grads, v, xi, want[0], want[1])
+        return hpos, hstrain, None, dY, dd, dA, None, None, None
 
 
 def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int = 1, pos: torch.Tensor | None = None,
@@ -213,8 +263,12 @@ def edge_geometry(g: RadiusGraph, want_dist=True, want_node_attr=True, lmax: int
     taken through it is the full second derivative on the edge set of ``g``.  ``pos_hessian=False`` declines the second of
     the two: the gradient is then treated as a function of the three gradients alone and ``pos`` receives only what flows
     through them -- for a caller that differentiates w.r.t. parameters only and has no use for a gradient in its position
-    leaf (the force-loss step of the energy models).  With a ``strain`` the second derivative raises
-    ``NotImplementedError``.
+    leaf (the force-loss step of the energy models).  With a ``strain`` the gradients w.r.t. ``pos`` and ``strain`` are
+    differentiable in the same way, once, in all five of (gY, gd, gA, pos, strain): the tangent along the cotangents (v, Xi) of
+    (g_pos, g_strain) is ``e3_edge_geometry_jvp_strained`` and the derivative in ``pos`` and ``strain`` is
+    ``e3_edge_geometry_hvp_strained`` -- together the second derivative of an energy in the joint coordinates (pos, strain):
+    force constants, the force-strain coupling and the Born elastic term.  ``pos_hessian=False`` then hands in constants for
+    both ``pos`` and ``strain`` (the parameter gradient of a loss on the stress needs the tangent only).
 
     ``strain`` [S,3,3] (or [3,3]: one structure), fp32 on the device, and ``structure`` [N] integer structure id of every
     row (graph order; None = every row is structure 0): every edge vector r of structure s (the structure of its dst row)
