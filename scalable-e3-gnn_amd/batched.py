@@ -7,7 +7,7 @@ with the same kernels as the single-cloud path.  The neighbour search runs on th
 returned carries the ORIGINAL coordinates, so edge vectors / spherical harmonics see no shift rounding.  The energy
 head is the per-molecule sum of a scalar (`1x0e`) node readout.  The force head is -dE/dpos by reverse-mode autograd
 through the whole message pass: every stage has a HIP backward (tensor products: `e3_l1tp_backward` / `e3_tp_backward`;
-edge geometry, gather/concat, gates, segment-sum: `e3_*_backward`, csrc/e3_edge_bwd.hip).  With ``create_graph=True`` the
+edge geometry, gather/concat, gates, segment-sum: `e3_*_backward`, csrc/e3_edge_geometry_bwd.hip and csrc/e3_edge_bwd.hip).  With ``create_graph=True`` the
 forces keep their graph: every stage's backward has a backward of its own (the multilinear stages by composition of the
 same entries; `e3_edge_geometry_jvp`, `e3_gate_blocks_backward2`, `e3_cutoff_envelope_backward2`), so a loss on energies
 AND forces has parameter gradients.  The derivative of the forces w.r.t. the positions needs one kernel

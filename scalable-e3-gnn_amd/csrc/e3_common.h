@@ -5,6 +5,7 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -208,6 +209,34 @@ inline bool make_cell(const float* cell, float r, PbcCell* out, float* heights =
     if (!(2.0f * r < h[a])) return false;
   for (int k = 0; k < 9; ++k) out->h[k] = cell[k];
   return true;
+}
+
+// host: grid of the one-wave-per-CSR-row stage kernels (256 threads = 4 rows per workgroup, grid-stride above 4096 groups)
+inline int wave_grid(int64_t N) { return (int)std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, 256 * 16)); }
+
+// block layout of the gate kernels (e3_gate_blocks and its two backwards), passed by value: block i = mul[i] channels of
+// degree l[i]; the unused tail has mul = 1 << 30, which ends the kernels' search for the block of a column
+struct GateBlocks {
+  int nblocks;
+  int l[8], mul[8];
+};
+// host: the descriptor of (ns, nblocks, ls, muls) with the gate count and the output width W = ns + sum mul (2 l + 1);
+// E3_ERR_INVALID_ARG for ns < 0, nblocks outside [0, 8], a missing array, l outside [0, 2] or a negative mul
+inline int make_gate_blocks(int ns, int nblocks, const int32_t* ls, const int32_t* muls, GateBlocks* gb, int* ngates,
+                            int* W) {
+  if (ns < 0 || nblocks < 0 || nblocks > 8 || (nblocks > 0 && (!ls || !muls))) return E3_ERR_INVALID_ARG;
+  gb->nblocks = nblocks;
+  int gates = 0, wide = 0;
+  for (int i = 0; i < 8; ++i) { gb->l[i] = 0; gb->mul[i] = 1 << 30; }
+  for (int i = 0; i < nblocks; ++i) {
+    if (ls[i] < 0 || ls[i] > 2 || muls[i] < 0) return E3_ERR_INVALID_ARG;
+    gb->l[i] = ls[i]; gb->mul[i] = muls[i];
+    gates += muls[i];
+    wide += muls[i] * (2 * ls[i] + 1);
+  }
+  *ngates = gates;
+  *W = ns + wide;
+  return E3_OK;
 }
 
 }  // namespace e3

@@ -1,9 +1,8 @@
 // Edge / node stages around the tensor product (builder-defined; spec in include/e3gnn.h).
 // All of them are HBM-bound streaming kernels: one wave per CSR row (dst node) where a row reduction
 // or a per-row broadcast is involved, 256-B coalesced row segments everywhere.
-#include "e3_common.h"
+#include "e3_edge_geometry.h"
 
-#include <algorithm>
 #include <cmath>
 
 namespace e3 {
@@ -186,11 +185,6 @@ __global__ __launch_bounds__(256) void edge_geometry_l2_kernel(const float4* __r
   }
 }
 
-struct GateBlocks {
-  int nblocks;
-  int l[8], mul[8];
-};
-
 __global__ __launch_bounds__(256) void gate_blocks_kernel(const float* __restrict__ in, int64_t ld_in,
                                                           float* __restrict__ out, int64_t ld_out, int64_t B, int ns,
                                                           int ngates, int W, GateBlocks gb) {
@@ -235,8 +229,6 @@ __global__ __launch_bounds__(256) void segment_sum_bf16_kernel(const bf16* __res
   }
 }
 
-static inline int wave_grid(int64_t N) { return (int)std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, 256 * 16)); }
-
 }  // namespace e3
 
 using namespace e3;
@@ -267,9 +259,9 @@ static int edge_geometry(int lmax, const float* pos4, const int32_t* rowptr, con
 // open (box NULL) or orthorhombic box
 static int edge_geometry(int lmax, const float* pos4, const int32_t* rowptr, const int32_t* src, int64_t N, float* edge_y,
                          float* edge_d, float* node_a, const float* box, const StrainArg* st, void* stream) {
-  const PbcBox b = make_box(box);
-  return box ? edge_geometry<kBox>(lmax, pos4, rowptr, src, N, edge_y, edge_d, node_a, b, st, stream)
-             : edge_geometry<kOpen>(lmax, pos4, rowptr, src, N, edge_y, edge_d, node_a, b, st, stream);
+  return dispatch_box(box, [&](auto mode, const PbcBox& b) {
+    return edge_geometry<decltype(mode)::value>(lmax, pos4, rowptr, src, N, edge_y, edge_d, node_a, b, st, stream);
+  });
 }
 
 // fp64 from the fp32 entries; contraction off: tests/triclinic_reference.py restates these expressions bit for bit
@@ -405,18 +397,9 @@ int e3_edge_geometry_strained(const float* pos4, const int32_t* rowptr, const in
 
 int e3_gate_blocks(const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t B, int ns, int nblocks,
                    const int32_t* ls, const int32_t* muls, void* stream) {
-  if (B < 0 || ns < 0 || nblocks < 0 || nblocks > 8 || (nblocks > 0 && (!ls || !muls))) return E3_ERR_INVALID_ARG;
   GateBlocks gb;
-  gb.nblocks = nblocks;
-  int ngates = 0, wide = 0;
-  for (int i = 0; i < 8; ++i) { gb.l[i] = 0; gb.mul[i] = 1 << 30; }
-  for (int i = 0; i < nblocks; ++i) {
-    if (ls[i] < 0 || ls[i] > 2 || muls[i] < 0) return E3_ERR_INVALID_ARG;
-    gb.l[i] = ls[i]; gb.mul[i] = muls[i];
-    ngates += muls[i];
-    wide += muls[i] * (2 * ls[i] + 1);
-  }
-  const int W = ns + wide;
+  int ngates, W;
+  if (B < 0 || make_gate_blocks(ns, nblocks, ls, muls, &gb, &ngates, &W) != E3_OK) return E3_ERR_INVALID_ARG;
   if (ld_in < W + ngates || ld_out < W) return E3_ERR_INVALID_ARG;
   if (B == 0 || W == 0) return E3_OK;
   if (!in || !out) return E3_ERR_INVALID_ARG;

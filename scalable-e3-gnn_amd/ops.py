@@ -31,6 +31,26 @@ def _wants_grad(*ts) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
+def _ptr(t):
+    """the address of a tensor, None (NULL) for None"""
+    return t.data_ptr() if t is not None else None
+
+
+def _f32c(t):
+    """a tensor as contiguous fp32, None for None"""
+    return t.to(torch.float32).contiguous() if t is not None else None
+
+
+def _geometry_head(pos4, g, N, *lmax):
+    """the leading arguments of every edge geometry entry: (pos4, rowptr, src, N), and lmax where the entry takes it"""
+    return (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, *lmax)
+
+
+def _strain_tail(strain, structure):
+    """the strain arguments of every ``*_strained`` entry, which follow its box or cell: (strain, structure | NULL, S)"""
+    return strain.data_ptr(), _ptr(structure), strain.shape[0]
+
+
 def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True, strain=None, structure=None):
     N, E, dev = g.rowptr.numel() - 1, g.num_edges, pos4.device
     ny = (lmax + 1) ** 2
@@ -41,18 +61,15 @@ def _edge_geometry_raw(pos4, g, want_dist, want_node_attr, lmax, want_edge=True,
         if A is not None:
             A.zero_()[:, 0] = 1.0
         return Y, d, A
-    head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N)
-    outs = (Y.data_ptr() if Y is not None else None, d.data_ptr() if d is not None else None,
-            A.data_ptr() if A is not None else None, _stream(pos4))
+    outs = (_ptr(Y), _ptr(d), _ptr(A), _stream(pos4))
     with torch.cuda.device(dev):
         if strain is not None:  # [S,3,3] contiguous fp32, structure [N] int32 | None (checked by _strain_args): the
             # minimum image of the box or cell first, then the strain
             name, pbc = g.entry("e3_edge_geometry_strained", strained=True)
-            _lib.call(name, *head, lmax, *pbc, strain.data_ptr(), structure.data_ptr() if structure is not None else None,
-                      strain.shape[0], *outs)
+            _lib.call(name, *_geometry_head(pos4, g, N, lmax), *pbc, *_strain_tail(strain, structure), *outs)
         else:  # periodic box / general cell: minimum-image edge vectors
             name, pbc = g.entry({1: "e3_edge_geometry", 2: "e3_edge_geometry_l2"}[lmax])
-            _lib.call(name, *head, *pbc, *outs)
+            _lib.call(name, *_geometry_head(pos4, g, N), *pbc, *outs)
     return Y, d, A
 
 
@@ -112,23 +129,21 @@ def _edge_geometry_backward_raw(pos4, strain, g, lmax, structure, gY, gd, gA):
     """-> (g_pos [N,3], g_strain | None): e3_edge_geometry_backward, or its strained form with a strain"""
     N = pos4.shape[0]
     gpos = torch.empty((N, 3), dtype=torch.float32, device=pos4.device)
-    c = lambda t: t.contiguous() if t is not None else None
-    gY, gd, gA = c(gY), c(gd), c(gA)
-    p = lambda t: t.data_ptr() if t is not None else None
+    gY, gd, gA = (t.contiguous() if t is not None else None for t in (gY, gd, gA))  # no cast: autograd hands in fp32
     gstrain = None
     if g.num_edges == 0:  # no edge: the outputs do not depend on pos or strain
         return gpos.zero_(), (torch.zeros_like(strain) if strain is not None else None)
     with torch.cuda.device(pos4.device):
-        head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax)
+        head = _geometry_head(pos4, g, N, lmax)
         if strain is not None:
             gstrain = torch.empty_like(strain)
             ws = _strain_workspace(N, pos4.device)
             name, pbc = g.entry("e3_edge_geometry_backward_strained", strained=True)
-            _lib.call(name, *head, *pbc, strain.data_ptr(), p(structure), strain.shape[0], p(gY), p(gd), p(gA),
-                      gpos.data_ptr(), gstrain.data_ptr(), ws.data_ptr(), ws.numel(), _stream(pos4))
+            _lib.call(name, *head, *pbc, *_strain_tail(strain, structure), _ptr(gY), _ptr(gd), _ptr(gA), gpos.data_ptr(),
+                      gstrain.data_ptr(), ws.data_ptr(), ws.numel(), _stream(pos4))
         else:
             name, pbc = g.entry("e3_edge_geometry_backward")
-            _lib.call(name, *head, *pbc, p(gY), p(gd), p(gA), gpos.data_ptr(), _stream(pos4))
+            _lib.call(name, *head, *pbc, _ptr(gY), _ptr(gd), _ptr(gA), gpos.data_ptr(), _stream(pos4))
     return gpos, gstrain
 
 
@@ -151,18 +166,16 @@ def _edge_geometry_jvp_raw(pos4, g, lmax, v, want_y=True, want_d=True, want_a=Tr
     dY = torch.empty((E, ny), dtype=torch.float32, device=dev) if want_y else None
     dd = torch.empty(E, dtype=torch.float32, device=dev) if want_d else None
     dA = torch.empty((N, ny), dtype=torch.float32, device=dev) if want_a else None
-    c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
-    v, xi = c(v), c(xi)
-    p = lambda t: t.data_ptr() if t is not None else None
+    v, xi = _f32c(v), _f32c(xi)
     with torch.cuda.device(dev):
-        head = (pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax)
+        head = _geometry_head(pos4, g, N, lmax)
         if strain is not None:
             name, pbc = g.entry("e3_edge_geometry_jvp_strained", strained=True)
-            _lib.call(name, *head, *pbc, strain.data_ptr(), p(structure), strain.shape[0], p(v), p(xi), p(dY), p(dd), p(dA),
+            _lib.call(name, *head, *pbc, *_strain_tail(strain, structure), _ptr(v), _ptr(xi), _ptr(dY), _ptr(dd), _ptr(dA),
                       _stream(pos4))
         else:
             name, pbc = g.entry("e3_edge_geometry_jvp")
-            _lib.call(name, *head, *pbc, v.data_ptr(), p(dY), p(dd), p(dA), _stream(pos4))
+            _lib.call(name, *head, *pbc, v.data_ptr(), _ptr(dY), _ptr(dd), _ptr(dA), _stream(pos4))
     return dY, dd, dA
 
 
@@ -173,13 +186,12 @@ def _edge_geometry_hvp_raw(pos4, g, lmax, gY, gd, gA, v):
     if g.num_edges == 0:  # no edge: g_pos does not depend on the positions
         return torch.zeros((N, 3), dtype=torch.float32, device=pos4.device)
     hpos = torch.empty((N, 3), dtype=torch.float32, device=pos4.device)
-    c = lambda t: t.contiguous() if t is not None else None
-    gY, gd, gA, v = c(gY), c(gd), c(gA), v.to(torch.float32).contiguous()
-    p = lambda t: t.data_ptr() if t is not None else None
+    gY, gd, gA = (t.contiguous() if t is not None else None for t in (gY, gd, gA))  # no cast, as in the backward
+    v = _f32c(v)
     with torch.cuda.device(pos4.device):
         name, pbc = g.entry("e3_edge_geometry_hvp")
-        _lib.call(name, pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, *pbc, p(gY), p(gd), p(gA),
-                  v.data_ptr(), hpos.data_ptr(), _stream(pos4))
+        _lib.call(name, *_geometry_head(pos4, g, N, lmax), *pbc, _ptr(gY), _ptr(gd), _ptr(gA), v.data_ptr(),
+                  hpos.data_ptr(), _stream(pos4))
     return hpos
 
 
@@ -192,15 +204,12 @@ def _edge_geometry_hvp_strained_raw(pos4, strain, g, lmax, structure, gY, gd, gA
     hstrain = torch.empty_like(strain) if want_strain else None
     if g.num_edges == 0:  # no edge: neither gradient depends on pos or strain
         return (hpos.zero_() if want_pos else None), (hstrain.zero_() if want_strain else None)
-    c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
-    gY, gd, gA, v, xi = c(gY), c(gd), c(gA), c(v), c(xi)
-    p = lambda t: t.data_ptr() if t is not None else None
+    gY, gd, gA, v, xi = (_f32c(t) for t in (gY, gd, gA, v, xi))
     with torch.cuda.device(dev):
         ws = _strain_workspace(N, dev)
         name, pbc = g.entry("e3_edge_geometry_hvp_strained", strained=True)
-        _lib.call(name, pos4.data_ptr(), g.rowptr.data_ptr(), g.src.data_ptr(), N, lmax, *pbc, strain.data_ptr(), p(structure),
-                  strain.shape[0], p(gY), p(gd), p(gA), p(v), p(xi), p(hpos), p(hstrain), ws.data_ptr(), ws.numel(),
-                  _stream(pos4))
+        _lib.call(name, *_geometry_head(pos4, g, N, lmax), *pbc, *_strain_tail(strain, structure), _ptr(gY), _ptr(gd),
+                  _ptr(gA), _ptr(v), _ptr(xi), _ptr(hpos), _ptr(hstrain), ws.data_ptr(), ws.numel(), _stream(pos4))
     return hpos, hstrain
 
 

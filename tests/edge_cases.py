@@ -1,5 +1,5 @@
 """Helpers of tests/test_edge_table_gpu.py and tests/test_edge_cases_host.py: the graphs, the fp64 references and the per-block
-error norm of the edge / node stage kernels (csrc/e3_edge_ops.hip, csrc/e3_edge_bwd.hip).  TEST INFRASTRUCTURE ONLY; nothing
+error norm of the edge / node stage kernels (csrc/e3_edge_ops.hip, csrc/e3_edge_bwd.hip, csrc/e3_edge_geometry_bwd.hip).  TEST INFRASTRUCTURE ONLY; nothing
 here touches the GPU at import time.
 
 Graphs: A and B, positions(), BOX and CELL are those of tests/msg_cases.py (a row of 70 edges, degrees 1 .. 5 and 16, isolated

@@ -1,4 +1,4 @@
-"""The edge / node stage kernels (csrc/e3_edge_ops.hip, csrc/e3_edge_bwd.hip) against fp64 references at the shapes their code
+"""The edge / node stage kernels (csrc/e3_edge_ops.hip, csrc/e3_edge_bwd.hip, csrc/e3_edge_geometry_bwd.hip) against fp64 references at the shapes their code
 branches on, PER BLOCK: max |got - want| / max |want| over the columns of one degree l (Y, A), of the scalars / the gates of a
 block / a gated block (gate), of one structure (g_strain).  Graphs, references and bounds are in tests/edge_cases.py (checked on
 the host by tests/test_edge_cases_host.py); DESIGN.md §4.5c has the table of which case stands for which branch.
@@ -538,3 +538,56 @@ def test_refusals():
     for t in (out, gpos, gstrain):
         assert bool((t == SENT).all())
     assert bool((ws == 7).all())
+
+
+def test_gate_blocks_entries_share_their_refusals():
+    """e3_gate_blocks, e3_gate_blocks_backward and e3_gate_blocks_backward2 validate one block descriptor the same way: each
+    invalid descriptor, and each leading dimension one below its minimum, is E3_ERR_INVALID_ARG from all three with nothing
+    written; B = 0 and a valid call are E3_OK.  Blocks [(l=1, mul=2), (l=2, mul=1)], ns = 3: 3 gates, output width W = 14,
+    input width W + 3 = 17."""
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    B, ns, W, WI = 2, 3, 14, 17
+    SENT = -7.25
+    x, go, ct = torch.randn(B, WI, device=DEV), torch.randn(B, W, device=DEV), torch.randn(B, WI, device=DEV)
+    out, gin = torch.full((B, W), SENT, device=DEV), torch.full((B, WI), SENT, device=DEV)
+    cgo, cin = torch.full((B, W), SENT, device=DEV), torch.full((B, WI), SENT, device=DEV)
+    arr = lambda v: (ctypes.c_int32 * len(v))(*v)
+    good = (ns, 2, arr([1, 2]), arr([2, 1]))
+
+    def forward(desc, b=B, ld_in=WI, ld_out=W):
+        return lib.e3_gate_blocks(x.data_ptr(), ld_in, out.data_ptr(), ld_out, b, *desc, stream)
+
+    def backward(desc, b=B, ld_in=WI, ld_gout=W, ld_gin=WI):
+        return lib.e3_gate_blocks_backward(x.data_ptr(), ld_in, go.data_ptr(), ld_gout, gin.data_ptr(), ld_gin, b, *desc, stream)
+
+    def backward2(desc, b=B, ld_in=WI, ld_gout=W, ld_c=WI, ld_cgout=W, ld_cin=WI):
+        return lib.e3_gate_blocks_backward2(x.data_ptr(), ld_in, go.data_ptr(), ld_gout, ct.data_ptr(), ld_c, cgo.data_ptr(),
+                                            ld_cgout, cin.data_ptr(), ld_cin, b, *desc, stream)
+
+    bad = {"nblocks 9": (ns, 9, arr([1] * 9), arr([1] * 9)), "l 3": (ns, 1, arr([3]), arr([2])),
+           "mul -1": (ns, 1, arr([1]), arr([-1])), "ns -1": (-1, 2, arr([1, 2]), arr([2, 1])),
+           "ls NULL": (ns, 1, None, arr([2]))}
+    refused = {}
+    for what, desc in bad.items():
+        for entry in (forward, backward, backward2):
+            refused[f"{entry.__name__} {what}"] = entry(desc)
+    for entry, lds in ((forward, {"ld_in": WI, "ld_out": W}), (backward, {"ld_in": WI, "ld_gout": W, "ld_gin": WI}),
+                       (backward2, {"ld_in": WI, "ld_gout": W, "ld_c": WI, "ld_cgout": W, "ld_cin": WI})):
+        for name, least in lds.items():
+            refused[f"{entry.__name__} {name} {least - 1}"] = entry(good, **{name: least - 1})
+    torch.cuda.synchronize()
+    for what, status in refused.items():
+        assert status == INVALID, (what, status)
+    for t in (out, gin, cgo, cin):
+        assert bool((t == SENT).all())
+    for entry in (forward, backward, backward2):
+        assert entry(good, b=0) == 0, entry.__name__
+    torch.cuda.synchronize()
+    for t in (out, gin, cgo, cin):
+        assert bool((t == SENT).all())
+    for entry in (forward, backward, backward2):
+        assert entry(good) == 0, entry.__name__
+    torch.cuda.synchronize()
+    for t in (out, gin, cgo, cin):
+        assert bool(torch.isfinite(t).all()) and not bool((t == SENT).any())
