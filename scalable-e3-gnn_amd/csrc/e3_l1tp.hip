@@ -1,92 +1,83 @@
-// L1 tensor product: plan, weight packing, generic forward kernel and the C ABI.
+// L1 tensor product: plan, weight packing, generic forward kernel and the operator's C ABI.
 //
-// Reference semantics: /root/reference/models/segnn/l1_tensor_prod.py (cited as L1TP.py:<line>).
+// Reference semantics (L1TP.py = the reference's models/segnn/l1_tensor_prod.py):
 //   out0e = ([s0e*Y0 | c3 <v1o,Y1>] @ W0e) * norm0e                                  L1TP.py:242-256
 //   out0o = ([s0o*Y0 | c3 <v1e,Y1>] @ W0o) * norm0o                                  L1TP.py:258-269
 //   out1e = ([c3 s0o (x) Y1 | c3 v1e Y0 | c6 v1o x Y1] ._k W1e) * norm1e             L1TP.py:271-284
 //   out1o = ([c3 s0e (x) Y1 | c3 v1o Y0 | c6 v1e x Y1] ._k W1o) * norm1o             L1TP.py:286-297
-// The kernels use bilinearity to contract the channel index with W first and apply Y afterwards:
+// (which input class stands in which block: kL1Src, e3_l1tp_plan.h).  The kernels use bilinearity to contract the channel
+// index with W first and apply Y afterwards:
 //   out1o[w,c] = norm * ( c3 (Y1[c] T0[w] + Y0 T1[w,c]) + c6 (T2[w] x Y1)[c] ),  T* = W-mixes of in1.
 //
 // This file holds the *generic* kernel: any irreps, fp32 / fp64 / bf16 storage (fp32 or fp64
 // accumulate), plain FMA.  The fp32 MFMA kernel lives in e3_l1tp_mfma.hip.
-#include "e3_common.h"
-
-#include <cmath>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <utility>
+#include "e3_l1tp_mix.h"
 
 namespace e3 {
 
-static thread_local std::string g_hip_err;
-void set_hip_error(hipError_t e, const char* what) {
-  g_hip_err = std::string(hipGetErrorName(e)) + ": " + hipGetErrorString(e) + " in " + what;
-}
-
-int ensure_dyn_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return E3_OK;
-  static std::mutex mu;
-  static std::map<std::pair<const void*, int>, size_t> have;
-  int dev = 0;
-  E3_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  size_t& cur = have[std::make_pair(fn, dev)];
-  if (bytes > cur) {
-    E3_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    cur = bytes;
+// -------------------------------------------------------------------------------------------------
+// plan
+// -------------------------------------------------------------------------------------------------
+static int parse_blocks(const int32_t* b, int n, std::vector<Block>& out, int* dim) {
+  int col = 0, lmax = -1;
+  for (int i = 0; i < n; ++i) {
+    int l = b[3 * i], p = b[3 * i + 1], mul = b[3 * i + 2];
+    if (l < 0 || l > 1 || (p != 1 && p != -1) || mul < 0) return E3_ERR_BAD_IRREPS;
+    out.push_back({l, p, mul, col});
+    col += (2 * l + 1) * mul;
+    if (l > lmax) lmax = l;
   }
+  if (lmax != 1) return E3_ERR_BAD_IRREPS;  // L1TP.py:13-14
+  *dim = col;
   return E3_OK;
 }
 
+static inline int cls_of(int l, int p) { return l * 2 + (p == 1 ? 0 : 1); }
 
-// Packed buffer, section 1 (all dtypes): [W0e | W0o | W1e | W1o | normcol[Dout]] in the accumulate
-// type; section 2 (MFMA tiles) follows at a 256-byte aligned offset.
-struct PackOffsets {
-  int64_t w[4];
-  int64_t normcol;
-  int64_t end;  // elements
-};
-static PackOffsets pack_offsets(const e3_l1tp_plan* p) {
-  PackOffsets o;
-  int64_t pos = 0;
-  for (int c = 0; c < 4; ++c) {
-    o.w[c] = pos;
-    pos += (int64_t)p->wrows[c] * p->wcols[c];
+// Device tables are uploaded on first use (so a plan can be created, and its shapes queried, on a
+// host without a GPU).  One plan belongs to the device that is current at that first use.
+int ensure_device(const e3_l1tp_plan* cplan) {
+  auto* P = const_cast<e3_l1tp_plan*>(cplan);
+  std::lock_guard<std::mutex> lock(P->mu);
+  int ndev = 0, cur = -1;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&cur) != hipSuccess) return E3_ERR_NO_DEVICE;
+  if (P->d_tables) return cur == P->device ? E3_OK : E3_ERR_INVALID_ARG;  // one plan = one device (create one per device)
+  int32_t* d = nullptr;
+  E3_HIP_CHECK(hipMalloc((void**)&d, P->h_tables.size() * sizeof(int32_t)));
+  hipError_t e = hipMemcpy(d, P->h_tables.data(), P->h_tables.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_hip_error(e, "plan table upload");
+    (void)hipFree(d);
+    return E3_ERR_HIP;
   }
-  o.normcol = pos;
-  pos += p->dev.Dout;
-  o.end = (pos + 63) / 64 * 64;
-  return o;
+  P->dev.cpos = d;
+  P->dev.opos = d + P->dev.D1;
+  P->dev.icol = P->dev.opos + P->dev.Dout;
+  P->dev.ocol = P->dev.icol + (P->dev.n[0] + P->dev.n[1] + P->dev.n[2] + P->dev.n[3]);
+  int st = mfma_plan_upload(P);
+  if (st != E3_OK) {
+    (void)hipFree(d);
+    return st;
+  }
+  P->device = cur;
+  P->d_tables = d;
+  return E3_OK;
 }
 
 // -------------------------------------------------------------------------------------------------
 // pack: convert weights to the accumulate type and expand the 4 norm buffers to one per-column vector
 // -------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ void pack_generic_kernel(const T* w0, const T* w1, const T* w2, const T* w3,
-                                    const T* n0, const T* n1, const T* n2, const T* n3,
-                                    typename AccOf<T>::type* packed, PackOffsets off, PlanDev p,
-                                    int64_t nw0, int64_t nw1, int64_t nw2, int64_t nw3) {
+__global__ void pack_generic_kernel(L1Ptr4<const T> w, L1Ptr4<const T> nrm, typename AccOf<T>::type* packed,
+                                    PackOffsets off, PlanDev p) {
   using A = typename AccOf<T>::type;
-  const T* w[4] = {w0, w1, w2, w3};
-  const T* nr[4] = {n0, n1, n2, n3};
-  const int64_t nw[4] = {nw0, nw1, nw2, nw3};
   int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int c = 0; c < 4; ++c)
-    for (int64_t i = tid; i < nw[c]; i += stride) packed[off.w[c] + i] = w[c] ? to_acc(w[c][i]) : A(0);
-  // normcol: class c, channel m -> out columns ocol[m] (+comp for vectors); norm index runs along the
-  // class's columns in order of appearance (L1TP.py:174,178,183,187)
   for (int c = 0; c < 4; ++c) {
-    int width = (c >= 2) ? 3 : 1;
-    for (int64_t i = tid; i < (int64_t)p.M[c] * width; i += stride) {
-      int m = (int)(i / width), comp = (int)(i - (int64_t)m * width);
-      int col = p.ocol[p.ocol_off[c] + m] + comp;
-      packed[off.normcol + col] = nr[c] ? to_acc(nr[c][i]) : A(1);
-    }
+    const int64_t nw = (c < 3 ? off.w[c + 1] : off.normcol) - off.w[c];
+    for (int64_t i = tid; i < nw; i += stride) packed[off.w[c] + i] = w.p[c] ? to_acc(w.p[c][i]) : A(0);
   }
+  l1_normcol_fill(p, nrm, packed + off.normcol, tid, stride);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -95,11 +86,6 @@ __global__ void pack_generic_kernel(const T* w0, const T* w1, const T* w2, const
 // One workgroup (256 threads) per tile of R rows.  The tile of in1 is staged into LDS in canonical
 // order [s0e | s0o | v1e xyz.. | v1o xyz..] (accumulate type); one thread then produces one
 // (row, class, channel) output: 1 value for scalar classes, 3 for vector classes.
-template <typename A>
-struct VecAcc {
-  A t0, t1x, t1y, t1z, t2x, t2y, t2z;
-};
-
 template <typename T, int R>
 __global__ __launch_bounds__(256) void l1tp_fwd_generic_kernel(
     const T* __restrict__ in1, int64_t ld1, const T* __restrict__ in2, int64_t ld2,
@@ -136,62 +122,23 @@ __global__ __launch_bounds__(256) void l1tp_fwd_generic_kernel(
       if (row >= B) continue;
       int cls = 0;
       while (it >= p.M[cls]) { it -= p.M[cls]; ++cls; }
-      const A* x = xs + r * D1;
       const A y0 = ys[r * 4 + 0], y1x = ys[r * 4 + 1], y1y = ys[r * 4 + 2], y1z = ys[r * 4 + 3];
       const int M = p.M[cls];
-      const A* W = packed + off.w[cls] + it;  // column `it`, row stride M
       const int ocol = p.ocol[p.ocol_off[cls] + it];
       T* o = out + row * ldo + ocol;
+      // column `it` of the class's matrix, row stride M
+      const L1Mix<A> m = l1_mix<A>(p, cls, xs + r * D1, packed + off.w[cls] + it, M);
       if (cls < 2) {
-        // scalar output: sources = same-parity scalars (x Y0) and opposite-parity vectors (. Y1)
-        const int sc = cls;                 // 0e <- s0e ; 0o <- s0o
-        const int vc = (cls == 0) ? 3 : 2;  // 0e <- v1o ; 0o <- v1e
-        const A* s = x + p.cbase[sc];
-        const A* v = x + p.cbase[vc];
-        const int ns = p.n[sc], nv = p.n[vc];
-        A as = 0, ax = 0, ay = 0, az = 0;
-        for (int k = 0; k < ns; ++k) as += s[k] * W[(int64_t)k * M];
-        const A* Wv = W + (int64_t)ns * M;
-        for (int k = 0; k < nv; ++k) {
-          A wk = Wv[(int64_t)k * M];
-          ax += v[3 * k + 0] * wk;
-          ay += v[3 * k + 1] * wk;
-          az += v[3 * k + 2] * wk;
-        }
-        A res = (y0 * as + c3 * (y1x * ax + y1y * ay + y1z * az)) * normcol[ocol];
+        A res = (y0 * m.t0 + c3 * (y1x * m.a.x + y1y * m.a.y + y1z * m.a.z)) * normcol[ocol];
         o[0] = from_acc<T, A>(res);
       } else {
-        // vector output: rows = [scalars of parity -p | vectors of parity p | vectors of parity -p]
-        const int sc = (cls == 3) ? 0 : 1;  // 1o <- s0e ; 1e <- s0o
-        const int v1 = cls;                 // same-parity vectors (x Y0)
-        const int v2 = (cls == 3) ? 2 : 3;  // opposite-parity vectors (cross Y1)
-        const A* s = x + p.cbase[sc];
-        const A* va = x + p.cbase[v1];
-        const A* vb = x + p.cbase[v2];
-        const int ns = p.n[sc], na = p.n[v1], nb = p.n[v2];
-        A t0 = 0, ax = 0, ay = 0, az = 0, bx = 0, by = 0, bz = 0;
-        for (int k = 0; k < ns; ++k) t0 += s[k] * W[(int64_t)k * M];
-        const A* Wa = W + (int64_t)ns * M;
-        for (int k = 0; k < na; ++k) {
-          A wk = Wa[(int64_t)k * M];
-          ax += va[3 * k + 0] * wk;
-          ay += va[3 * k + 1] * wk;
-          az += va[3 * k + 2] * wk;
-        }
-        const A* Wb = Wa + (int64_t)na * M;
-        for (int k = 0; k < nb; ++k) {
-          A wk = Wb[(int64_t)k * M];
-          bx += vb[3 * k + 0] * wk;
-          by += vb[3 * k + 1] * wk;
-          bz += vb[3 * k + 2] * wk;
-        }
         // (b x Y1)
-        A cx = by * y1z - bz * y1y;
-        A cy = bz * y1x - bx * y1z;
-        A cz = bx * y1y - by * y1x;
-        o[0] = from_acc<T, A>((c3 * (y1x * t0 + y0 * ax) + c6 * cx) * normcol[ocol + 0]);
-        o[1] = from_acc<T, A>((c3 * (y1y * t0 + y0 * ay) + c6 * cy) * normcol[ocol + 1]);
-        o[2] = from_acc<T, A>((c3 * (y1z * t0 + y0 * az) + c6 * cz) * normcol[ocol + 2]);
+        A cx = m.b.y * y1z - m.b.z * y1y;
+        A cy = m.b.z * y1x - m.b.x * y1z;
+        A cz = m.b.x * y1y - m.b.y * y1x;
+        o[0] = from_acc<T, A>((c3 * (y1x * m.t0 + y0 * m.a.x) + c6 * cx) * normcol[ocol + 0]);
+        o[1] = from_acc<T, A>((c3 * (y1y * m.t0 + y0 * m.a.y) + c6 * cy) * normcol[ocol + 1]);
+        o[2] = from_acc<T, A>((c3 * (y1z * m.t0 + y0 * m.a.z) + c6 * cz) * normcol[ocol + 2]);
       }
     }
     __syncthreads();
@@ -204,7 +151,7 @@ static int launch_generic(const e3_l1tp_plan* plan, const void* in1, int64_t ld1
   using A = typename AccOf<T>::type;
   constexpr int R = 16;
   size_t smem = (size_t)R * (plan->dev.D1 + 4) * sizeof(A);
-  if (smem > 160 * 1024) return E3_ERR_UNSUPPORTED;
+  if (smem > (size_t)kL1LdsBudget) return E3_ERR_UNSUPPORTED;
   auto kern = l1tp_fwd_generic_kernel<T, R>;
   if (int st = ensure_dyn_lds((const void*)kern, smem); st != E3_OK) return st;
   int64_t ntiles = (B + R - 1) / R;
@@ -219,19 +166,11 @@ template <typename T>
 static int launch_pack(const e3_l1tp_plan* plan, const void* const w[4], const void* const n[4], void* packed,
                        hipStream_t stream) {
   using A = typename AccOf<T>::type;
-  const void* nn[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (n)
-    for (int c = 0; c < 4; ++c) nn[c] = n[c];
-  int64_t nw[4];
-  for (int c = 0; c < 4; ++c) nw[c] = (int64_t)plan->wrows[c] * plan->wcols[c];
-  hipLaunchKernelGGL(pack_generic_kernel<T>, dim3(64), dim3(256), 0, stream, (const T*)w[0], (const T*)w[1],
-                     (const T*)w[2], (const T*)w[3], (const T*)nn[0], (const T*)nn[1], (const T*)nn[2],
-                     (const T*)nn[3], (A*)packed, pack_offsets(plan), plan->dev, nw[0], nw[1], nw[2], nw[3]);
+  hipLaunchKernelGGL(pack_generic_kernel<T>, dim3(64), dim3(256), 0, stream, l1_ptr4<const T>(w), l1_ptr4<const T>(n),
+                     (A*)packed, pack_offsets(plan), plan->dev);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }
-
-int64_t generic_packed_elems(const e3_l1tp_plan* plan) { return pack_offsets(plan).end; }
 
 }  // namespace e3
 
@@ -241,39 +180,6 @@ int64_t generic_packed_elems(const e3_l1tp_plan* plan) { return pack_offsets(pla
 using namespace e3;
 
 extern "C" {
-
-int e3_abi_version(void) { return E3GNN_ABI_VERSION; }
-
-const char* e3_status_string(int s) {
-  switch (s) {
-    case E3_OK: return "ok";
-    case E3_ERR_INVALID_ARG: return "invalid argument";
-    case E3_ERR_BAD_IRREPS: return "bad irreps (need l in {0,1}, lmax == 1, p in {+1,-1}, mul >= 0)";
-    case E3_ERR_MISSING_WEIGHT: return "an output class has columns but no weight matrix";
-    case E3_ERR_UNSUPPORTED: return "unsupported shape/dtype for the requested kernel";
-    case E3_ERR_HIP: return "HIP runtime error";
-    case E3_ERR_NO_DEVICE: return "no HIP device";
-    default: return "unknown status";
-  }
-}
-
-const char* e3_last_hip_error(void) { return g_hip_err.c_str(); }
-
-static int parse_blocks(const int32_t* b, int n, std::vector<Block>& out, int* dim) {
-  int col = 0, lmax = -1;
-  for (int i = 0; i < n; ++i) {
-    int l = b[3 * i], p = b[3 * i + 1], mul = b[3 * i + 2];
-    if (l < 0 || l > 1 || (p != 1 && p != -1) || mul < 0) return E3_ERR_BAD_IRREPS;
-    out.push_back({l, p, mul, col});
-    col += (2 * l + 1) * mul;
-    if (l > lmax) lmax = l;
-  }
-  if (lmax != 1) return E3_ERR_BAD_IRREPS;  // L1TP.py:13-14
-  *dim = col;
-  return E3_OK;
-}
-
-static inline int cls_of(int l, int p) { return l * 2 + (p == 1 ? 0 : 1); }
 
 int e3_l1tp_plan_create(const int32_t* in1_blocks, int n_in1, const int32_t* out_blocks, int n_out,
                         e3_l1tp_plan** plan_out) {
@@ -297,11 +203,10 @@ int e3_l1tp_plan_create(const int32_t* in1_blocks, int n_in1, const int32_t* out
     P->dev.M[c] += b.mul;
   }
   const int* n = P->dev.n;
-  // weight rows in forward-concat order (L1TP.py:81-88)
-  int rows[4] = {n[0] + n[3], n[1] + n[2], n[1] + n[2] + n[3], n[0] + n[3] + n[2]};
   for (int c = 0; c < 4; ++c) {
-    bool present = rows[c] > 0 && P->dev.M[c] > 0;
-    P->wrows[c] = present ? rows[c] : 0;
+    const int rows = l1_wrow(n, c, 3);  // weight rows in forward-concat order (L1TP.py:81-88)
+    bool present = rows > 0 && P->dev.M[c] > 0;
+    P->wrows[c] = present ? rows : 0;
     P->wcols[c] = present ? P->dev.M[c] : 0;
     P->normlen[c] = P->dev.M[c] * (c >= 2 ? 3 : 1);
   }
@@ -355,40 +260,6 @@ int e3_l1tp_plan_create(const int32_t* in1_blocks, int n_in1, const int32_t* out
   return E3_OK;
 }
 
-// Device tables are uploaded on first use (so a plan can be created, and its shapes queried, on a
-// host without a GPU).  One plan belongs to the device that is current at that first use.
-}  // extern "C"
-namespace e3 {
-int ensure_device(const e3_l1tp_plan* cplan) {
-  auto* P = const_cast<e3_l1tp_plan*>(cplan);
-  std::lock_guard<std::mutex> lock(P->mu);
-  int ndev = 0, cur = -1;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || hipGetDevice(&cur) != hipSuccess) return E3_ERR_NO_DEVICE;
-  if (P->d_tables) return cur == P->device ? E3_OK : E3_ERR_INVALID_ARG;  // one plan = one device (create one per device)
-  int32_t* d = nullptr;
-  E3_HIP_CHECK(hipMalloc((void**)&d, P->h_tables.size() * sizeof(int32_t)));
-  hipError_t e = hipMemcpy(d, P->h_tables.data(), P->h_tables.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    set_hip_error(e, "plan table upload");
-    (void)hipFree(d);
-    return E3_ERR_HIP;
-  }
-  P->dev.cpos = d;
-  P->dev.opos = d + P->dev.D1;
-  P->dev.icol = P->dev.opos + P->dev.Dout;
-  P->dev.ocol = P->dev.icol + (P->dev.n[0] + P->dev.n[1] + P->dev.n[2] + P->dev.n[3]);
-  int st = mfma_plan_upload(P);
-  if (st != E3_OK) {
-    (void)hipFree(d);
-    return st;
-  }
-  P->device = cur;
-  P->d_tables = d;
-  return E3_OK;
-}
-}  // namespace e3
-extern "C" {
-
 int e3_l1tp_plan_destroy(e3_l1tp_plan* plan) {
   if (!plan) return E3_OK;
   mfma_plan_free(plan);
@@ -407,14 +278,9 @@ int e3_l1tp_weight_shape(const e3_l1tp_plan* p, int cls, int* rows, int* cols) {
 }
 int e3_l1tp_norm_len(const e3_l1tp_plan* p, int cls) { return (p && cls >= 0 && cls < 4) ? p->normlen[cls] : -1; }
 
-static inline size_t acc_size(int dtype) { return dtype == E3_F64 ? 8 : 4; }
-
 int64_t e3_l1tp_packed_bytes(const e3_l1tp_plan* plan, int dtype) {
   if (!plan || dtype < 0 || dtype > 2) return -1;
-  int64_t bytes = generic_packed_elems(plan) * (int64_t)acc_size(dtype);
-  bytes = (bytes + 255) / 256 * 256;
-  if (dtype != E3_F64) bytes += mfma_packed_bytes(plan);
-  return bytes;
+  return l1_mfma_section_offset(plan, dtype) + (dtype != E3_F64 ? mfma_packed_bytes(plan) : 0);
 }
 
 int e3_l1tp_pack_weights(const e3_l1tp_plan* plan, const void* const weights[4], const void* const norms[4],
@@ -426,16 +292,12 @@ int e3_l1tp_pack_weights(const e3_l1tp_plan* plan, const void* const weights[4],
   hipStream_t s = (hipStream_t)stream;
   int st = ensure_device(plan);
   if (st != E3_OK) return st;
-  switch (dtype) {
-    case E3_F32: st = launch_pack<float>(plan, weights, norms, packed, s); break;
-    case E3_F64: st = launch_pack<double>(plan, weights, norms, packed, s); break;
-    default: st = launch_pack<bf16>(plan, weights, norms, packed, s); break;
-  }
+  st = l1_by_dtype(dtype, [&](auto tag) {
+    return launch_pack<typename decltype(tag)::type>(plan, weights, norms, packed, s);
+  });
   if (st != E3_OK) return st;
-  if (dtype != E3_F64 && mfma_packed_bytes(plan) > 0) {
-    int64_t off = (generic_packed_elems(plan) * 4 + 255) / 256 * 256;
-    st = mfma_pack(plan, weights, norms, dtype, (char*)packed + off, s);
-  }
+  if (dtype != E3_F64 && mfma_packed_bytes(plan) > 0)
+    st = mfma_pack(plan, weights, norms, dtype, (char*)packed + l1_mfma_section_offset(plan, dtype), s);
   return st;
 }
 
@@ -450,15 +312,12 @@ int e3_l1tp_forward(const e3_l1tp_plan* plan, const void* in1, int64_t ld_in1, c
   if (st != E3_OK) return st;
   bool can_mfma = mfma_supported(plan, dtype);
   if (kernel == 2 && !can_mfma) return E3_ERR_UNSUPPORTED;
-  if (kernel != 1 && can_mfma) {
-    int64_t off = (generic_packed_elems(plan) * 4 + 255) / 256 * 256;
-    return mfma_forward(plan, in1, ld_in1, in2, ld_in2, (const char*)packed + off, out, ld_out, B, dtype, s);
-  }
-  switch (dtype) {
-    case E3_F32: return launch_generic<float>(plan, in1, ld_in1, in2, ld_in2, packed, out, ld_out, B, s);
-    case E3_F64: return launch_generic<double>(plan, in1, ld_in1, in2, ld_in2, packed, out, ld_out, B, s);
-    default: return launch_generic<bf16>(plan, in1, ld_in1, in2, ld_in2, packed, out, ld_out, B, s);
-  }
+  if (kernel != 1 && can_mfma)
+    return mfma_forward(plan, in1, ld_in1, in2, ld_in2, (const char*)packed + l1_mfma_section_offset(plan, dtype), out,
+                        ld_out, B, dtype, s);
+  return l1_by_dtype(dtype, [&](auto tag) {
+    return launch_generic<typename decltype(tag)::type>(plan, in1, ld_in1, in2, ld_in2, packed, out, ld_out, B, s);
+  });
 }
 
 }  // extern "C"

@@ -4,14 +4,15 @@
 // With gn = grad_out * norm (per output column) and, per row,
 //   out0e[m]   = Y0 S0e.A0e[:,m] + c3 Y1.(V1o.B0e[:,m])
 //   out1o[w,c] = c3 Y1[c] S0e.A1o[:,w] + c3 Y0 (V1o.B1o[:,w])[c] + c6 ((V1e.C1o[:,w]) x Y1)[c]
-// (0o / 1e: swap parities), A/B/C being the row blocks of the weight matrices (L1TP.py:81-88):
+// (0o / 1e: swap parities), A/B/C being the row blocks of the weight matrices (L1TP.py:81-88; which class stands in which
+// block, and which matrices a class has rows in: kL1Src / kL1Dst, e3_l1tp_plan.h):
 //   d s0e[k]   = Y0 A0e[k,:].gn0e + c3 Y1.(A1o[k,:].gn1o)
 //   d v1o[k]   = c3 Y1 (B0e[k,:].gn0e) + c3 Y0 (B1o[k,:].gn1o) + c6 Y1 x (C1e[k,:].gn1e)
 //   d Y0       = sum_m gn0e[m] (S0e.A0e[:,m]) + c3 sum_w gn1o[w].(V1o.B1o[:,w])           (+ 0o/1e terms)
 //   d Y1       = c3 sum_m gn0e[m] (V1o.B0e[:,m]) + c3 sum_w gn1o[w] (S0e.A1o[:,w])
 //                + c6 sum_w gn1o[w] x (V1e.C1o[:,w])                                       (+ 0o/1e terms)
 //   d W        = sum over rows of feature (x) gn  (two-stage, deterministic reduction)
-#include "e3_common.h"
+#include "e3_l1tp_mix.h"
 
 namespace e3 {
 
@@ -23,8 +24,7 @@ template <typename T>
 struct BwdArgs {
   const T* in1; int64_t ld1;
   const T* in2; int64_t ld2;
-  const T* w[4];
-  const T* nrm[4];
+  L1Ptr4<const T> w, nrm;
   const T* gout; int64_t ldg;
   int64_t B;
 };
@@ -43,7 +43,7 @@ __device__ __forceinline__ void stage_tile(const BwdArgs<T>& a, const PlanDev& p
     int64_t row = row0 + r;
     int pos = p.opos[d];
     int c = pos >= p.obase[3] ? 3 : pos >= p.obase[2] ? 2 : pos >= p.obase[1] ? 1 : 0;
-    A nv = a.nrm[c] ? to_acc(a.nrm[c][pos - p.obase[c]]) : A(1);
+    A nv = a.nrm.p[c] ? to_acc(a.nrm.p[c][pos - p.obase[c]]) : A(1);
     gs[r * p.Dout + pos] = row < a.B ? to_acc(a.gout[row * a.ldg + d]) * nv : A(0);
   }
   for (int i = tid; i < kR * 4; i += 256) {
@@ -85,66 +85,22 @@ __global__ __launch_bounds__(256) void l1tp_bwd_rows_kernel(BwdArgs<T> a, T* __r
         const A* g = gs + r * p.Dout;
         const A y0 = ys[r * 4], y1x = ys[r * 4 + 1], y1y = ys[r * 4 + 2], y1z = ys[r * 4 + 3];
         T* o = gin1 + row * ldgi + p.icol[p.icol_off[cls] + it];
+        // channel `it` of input class cls is row wrow + it of the block it feeds in each consumer's matrix (kL1Dst)
+        const int os = kL1Dst[cls][0], ov = kL1Dst[cls][1];
+        const A t = l1_wdot1(a.w.p[os], l1_wrow(p.n, os, l1_dst_slot(cls, 0)) + it, p.M[os], g + p.obase[os]);
+        const L1Vec3<A> s = l1_wdot3(a.w.p[ov], l1_wrow(p.n, ov, l1_dst_slot(cls, 1)) + it, p.M[ov], g + p.obase[ov]);
         if (cls < 2) {
-          // scalar channel k of parity class `cls`: rows k of W0(cls) and of W1(opposite parity out)
-          const int so = cls;                  // scalar out class fed through Y0
-          const int vo = (cls == 0) ? 3 : 2;   // vector out class fed through Y1
-          A acc = 0, vx = 0, vy = 0, vz = 0;
-          if (a.w[so]) {
-            const T* W = a.w[so] + (int64_t)it * p.M[so];
-            const A* gg = g + p.obase[so];
-            for (int m = 0; m < p.M[so]; ++m) acc += to_acc(W[m]) * gg[m];
-          }
-          if (a.w[vo]) {
-            const T* W = a.w[vo] + (int64_t)it * p.M[vo];
-            const A* gg = g + p.obase[vo];
-            for (int w = 0; w < p.M[vo]; ++w) {
-              A wk = to_acc(W[w]);
-              vx += wk * gg[3 * w];
-              vy += wk * gg[3 * w + 1];
-              vz += wk * gg[3 * w + 2];
-            }
-          }
-          o[0] = from_acc<T, A>(y0 * acc + c3 * (y1x * vx + y1y * vy + y1z * vz));
+          // scalar channel: fed the scalar output through Y0 and the vector output through Y1
+          o[0] = from_acc<T, A>(y0 * t + c3 * (y1x * s.x + y1y * s.y + y1z * s.z));
         } else {
-          // vector channel k of class `cls` (3 = 1o, 2 = 1e)
-          const int so = (cls == 3) ? 0 : 1;   // scalar out fed by <v,Y1>:   0e <- v1o, 0o <- v1e
-          const int vs = cls;                  // same-parity vector out (x Y0)
-          const int vx_ = (cls == 3) ? 2 : 3;  // opposite-parity vector out (cross)
-          const int ns_so = p.n[so];                                   // scalar rows before us in W0(so)
-          const int ns_vs = p.n[(cls == 3) ? 0 : 1];                   // scalar rows before us in W1(vs)
-          const int rows_before_cross = p.n[(vx_ == 3) ? 0 : 1] + p.n[vx_];  // [scalars | same vectors] of W1(vx_)
-          A t = 0, sx = 0, sy = 0, sz = 0, cx = 0, cy = 0, cz = 0;
-          if (a.w[so]) {
-            const T* W = a.w[so] + (int64_t)(ns_so + it) * p.M[so];
-            const A* gg = g + p.obase[so];
-            for (int m = 0; m < p.M[so]; ++m) t += to_acc(W[m]) * gg[m];
-          }
-          if (a.w[vs]) {
-            const T* W = a.w[vs] + (int64_t)(ns_vs + it) * p.M[vs];
-            const A* gg = g + p.obase[vs];
-            for (int w = 0; w < p.M[vs]; ++w) {
-              A wk = to_acc(W[w]);
-              sx += wk * gg[3 * w];
-              sy += wk * gg[3 * w + 1];
-              sz += wk * gg[3 * w + 2];
-            }
-          }
-          if (a.w[vx_]) {
-            const T* W = a.w[vx_] + (int64_t)(rows_before_cross + it) * p.M[vx_];
-            const A* gg = g + p.obase[vx_];
-            for (int w = 0; w < p.M[vx_]; ++w) {
-              A wk = to_acc(W[w]);
-              cx += wk * gg[3 * w];
-              cy += wk * gg[3 * w + 1];
-              cz += wk * gg[3 * w + 2];
-            }
-          }
+          // vector channel: dotted with Y1 (scalar output), taken with Y0 (same-parity vectors), crossed with Y1
+          const int ox = kL1Dst[cls][2];
+          const L1Vec3<A> c = l1_wdot3(a.w.p[ox], l1_wrow(p.n, ox, l1_dst_slot(cls, 2)) + it, p.M[ox], g + p.obase[ox]);
           // Y1 x c
-          A kx = y1y * cz - y1z * cy, ky = y1z * cx - y1x * cz, kz = y1x * cy - y1y * cx;
-          o[0] = from_acc<T, A>(c3 * (y1x * t + y0 * sx) + c6 * kx);
-          o[1] = from_acc<T, A>(c3 * (y1y * t + y0 * sy) + c6 * ky);
-          o[2] = from_acc<T, A>(c3 * (y1z * t + y0 * sz) + c6 * kz);
+          A kx = y1y * c.z - y1z * c.y, ky = y1z * c.x - y1x * c.z, kz = y1x * c.y - y1y * c.x;
+          o[0] = from_acc<T, A>(c3 * (y1x * t + y0 * s.x) + c6 * kx);
+          o[1] = from_acc<T, A>(c3 * (y1y * t + y0 * s.y) + c6 * ky);
+          o[2] = from_acc<T, A>(c3 * (y1z * t + y0 * s.z) + c6 * kz);
         }
       }
     }
@@ -161,54 +117,21 @@ __global__ __launch_bounds__(256) void l1tp_bwd_rows_kernel(BwdArgs<T> a, T* __r
         for (int i = lane; i < Mtot; i += 64) {
           int it = i, cls = 0;
           while (it >= p.M[cls]) { it -= p.M[cls]; ++cls; }
-          const int M = p.M[cls];
-          const T* W = a.w[cls] + it;
+          const L1Mix<A> m = l1_mix<A>(p, cls, x, a.w.p[cls] + it, p.M[cls]);
           if (cls < 2) {
-            const int sc = cls, vc = (cls == 0) ? 3 : 2;
-            const A* s = x + p.cbase[sc];
-            const A* v = x + p.cbase[vc];
-            A as = 0, ax = 0, ay = 0, az = 0;
-            for (int k = 0; k < p.n[sc]; ++k) as += s[k] * to_acc(W[(int64_t)k * M]);
-            const T* Wv = W + (int64_t)p.n[sc] * M;
-            for (int k = 0; k < p.n[vc]; ++k) {
-              A wk = to_acc(Wv[(int64_t)k * M]);
-              ax += v[3 * k] * wk;
-              ay += v[3 * k + 1] * wk;
-              az += v[3 * k + 2] * wk;
-            }
             A gg = g[p.obase[cls] + it];
-            d0 += gg * as;
-            dx += c3 * gg * ax;
-            dy += c3 * gg * ay;
-            dz += c3 * gg * az;
+            d0 += gg * m.t0;
+            dx += c3 * gg * m.a.x;
+            dy += c3 * gg * m.a.y;
+            dz += c3 * gg * m.a.z;
           } else {
-            const int sc = (cls == 3) ? 0 : 1, v1 = cls, v2 = (cls == 3) ? 2 : 3;
-            const A* s = x + p.cbase[sc];
-            const A* va = x + p.cbase[v1];
-            const A* vb = x + p.cbase[v2];
-            A t0 = 0, ax = 0, ay = 0, az = 0, bx = 0, by = 0, bz = 0;
-            for (int k = 0; k < p.n[sc]; ++k) t0 += s[k] * to_acc(W[(int64_t)k * M]);
-            const T* Wa = W + (int64_t)p.n[sc] * M;
-            for (int k = 0; k < p.n[v1]; ++k) {
-              A wk = to_acc(Wa[(int64_t)k * M]);
-              ax += va[3 * k] * wk;
-              ay += va[3 * k + 1] * wk;
-              az += va[3 * k + 2] * wk;
-            }
-            const T* Wb = Wa + (int64_t)p.n[v1] * M;
-            for (int k = 0; k < p.n[v2]; ++k) {
-              A wk = to_acc(Wb[(int64_t)k * M]);
-              bx += vb[3 * k] * wk;
-              by += vb[3 * k + 1] * wk;
-              bz += vb[3 * k + 2] * wk;
-            }
             const A* gg = g + p.obase[cls] + 3 * it;
             A gx = gg[0], gy = gg[1], gz = gg[2];
-            d0 += c3 * (gx * ax + gy * ay + gz * az);
+            d0 += c3 * (gx * m.a.x + gy * m.a.y + gz * m.a.z);
             // d/dY1 of c3 Y1[c] t0 g[c] + c6 (b x Y1).g  =  c3 t0 g + c6 (g x b)
-            dx += c3 * t0 * gx + c6 * (gy * bz - gz * by);
-            dy += c3 * t0 * gy + c6 * (gz * bx - gx * bz);
-            dz += c3 * t0 * gz + c6 * (gx * by - gy * bx);
+            dx += c3 * m.t0 * gx + c6 * (gy * m.b.z - gz * m.b.y);
+            dy += c3 * m.t0 * gy + c6 * (gz * m.b.x - gx * m.b.z);
+            dz += c3 * m.t0 * gz + c6 * (gx * m.b.y - gy * m.b.x);
           }
         }
         for (int o = 32; o > 0; o >>= 1) {
@@ -310,7 +233,7 @@ __global__ __launch_bounds__(256) void l1tp_bwd_w_kernel(BwdArgs<T> a, typename 
       const int k = e_k[j], m = e_m[j];
       A sum = 0;
       if (cls < 2) {
-        const int sc = cls, vc = (cls == 0) ? 3 : 2;
+        const int sc = kL1Src[cls][0], vc = kL1Src[cls][1];
         const int ns = p.n[sc];
         for (int r = 0; r < nrows; ++r) {
           const A* x = xs + r * p.D1;
@@ -325,7 +248,7 @@ __global__ __launch_bounds__(256) void l1tp_bwd_w_kernel(BwdArgs<T> a, typename 
           sum += f * g;
         }
       } else {
-        const int sc = (cls == 3) ? 0 : 1, v1 = cls, v2 = (cls == 3) ? 2 : 3;
+        const int sc = kL1Src[cls][0], v1 = kL1Src[cls][1], v2 = kL1Src[cls][2];
         const int ns = p.n[sc], na = p.n[v1];
         for (int r = 0; r < nrows; ++r) {
           const A* x = xs + r * p.D1;
@@ -358,14 +281,13 @@ __global__ __launch_bounds__(256) void l1tp_bwd_w_kernel(BwdArgs<T> a, typename 
 
 template <typename T>
 __global__ void l1tp_bwd_w_reduce_kernel(const typename AccOf<T>::type* __restrict__ partial, int nchunks, WOffsets wo,
-                                         T* g0, T* g1, T* g2, T* g3) {
+                                         L1Ptr4<T> gw) {
   using A = typename AccOf<T>::type;
-  T* gw[4] = {g0, g1, g2, g3};
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < wo.total; e += (int64_t)gridDim.x * blockDim.x) {
     A acc = 0;
     for (int c = 0; c < nchunks; ++c) acc += partial[(int64_t)c * wo.total + e];
     int cls = w_class_of(wo, e);
-    if (gw[cls]) gw[cls][e - wo.w[cls]] = from_acc<T, A>(acc);
+    if (gw.p[cls]) gw.p[cls][e - wo.w[cls]] = from_acc<T, A>(acc);
   }
 }
 
@@ -410,14 +332,16 @@ static int launch_backward(const e3_l1tp_plan* plan, const void* in1, int64_t ld
   using A = typename AccOf<T>::type;
   BwdArgs<T> a;
   a.in1 = (const T*)in1; a.ld1 = ld1; a.in2 = (const T*)in2; a.ld2 = ld2;
+  a.w = l1_ptr4<const T>(w);
+  a.nrm = l1_ptr4<const T>(n);
   for (int c = 0; c < 4; ++c) {
-    a.w[c] = plan->wrows[c] > 0 ? (const T*)w[c] : nullptr;
-    a.nrm[c] = (n && plan->normlen[c] > 0) ? (const T*)n[c] : nullptr;
+    if (plan->wrows[c] <= 0) a.w.p[c] = nullptr;
+    if (plan->normlen[c] <= 0) a.nrm.p[c] = nullptr;
   }
   a.gout = (const T*)gout; a.ldg = ldg; a.B = B;
   const PlanDev& p = plan->dev;
   size_t smem = (size_t)kR * (p.D1 + p.Dout + 4) * sizeof(A);
-  if (smem > 160 * 1024) return E3_ERR_UNSUPPORTED;
+  if (smem > (size_t)kL1LdsBudget) return E3_ERR_UNSUPPORTED;
   BwdGeom g = bwd_geom(plan, B, sizeof(A));
   char* ws = (char*)workspace;
   const bool bcast = (ld2 == 0);
@@ -451,7 +375,7 @@ static int launch_backward(const e3_l1tp_plan* plan, const void* in1, int64_t ld
     E3_HIP_CHECK(hipGetLastError());
     int rb = (int)std::min<int64_t>((wo.total + 255) / 256, 1024);
     hipLaunchKernelGGL(l1tp_bwd_w_reduce_kernel<T>, dim3(rb), dim3(256), 0, stream, partial, g.nchunks, wo,
-                       (T*)gw[0], (T*)gw[1], (T*)gw[2], (T*)gw[3]);
+                       l1_ptr4<T>(gw));
     E3_HIP_CHECK(hipGetLastError());
   }
   return E3_OK;
@@ -465,7 +389,7 @@ extern "C" {
 
 int64_t e3_l1tp_backward_workspace_bytes(const e3_l1tp_plan* plan, int64_t B, int dtype) {
   if (!plan || B < 0 || dtype < 0 || dtype > 2) return -1;
-  return bwd_geom(plan, B, dtype == E3_F64 ? 8 : 4).total;
+  return bwd_geom(plan, B, l1_acc_size(dtype)).total;
 }
 
 int e3_l1tp_backward(const e3_l1tp_plan* plan, const void* in1, int64_t ld_in1, const void* in2, int64_t ld_in2,
@@ -481,17 +405,10 @@ int e3_l1tp_backward(const e3_l1tp_plan* plan, const void* in1, int64_t ld_in1, 
   int st = ensure_device(plan);
   if (st != E3_OK) return st;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case E3_F32:
-      return launch_backward<float>(plan, in1, ld_in1, in2, ld_in2, weights, norms, grad_out, ld_gout, grad_in1,
-                                    ld_gin1, grad_in2, grad_weights, workspace, B, s);
-    case E3_F64:
-      return launch_backward<double>(plan, in1, ld_in1, in2, ld_in2, weights, norms, grad_out, ld_gout, grad_in1,
-                                     ld_gin1, grad_in2, grad_weights, workspace, B, s);
-    default:
-      return launch_backward<bf16>(plan, in1, ld_in1, in2, ld_in2, weights, norms, grad_out, ld_gout, grad_in1,
-                                   ld_gin1, grad_in2, grad_weights, workspace, B, s);
-  }
+  return l1_by_dtype(dtype, [&](auto tag) {
+    return launch_backward<typename decltype(tag)::type>(plan, in1, ld_in1, in2, ld_in2, weights, norms, grad_out, ld_gout,
+                                                         grad_in1, ld_gin1, grad_in2, grad_weights, workspace, B, s);
+  });
 }
 
 }  // extern "C"

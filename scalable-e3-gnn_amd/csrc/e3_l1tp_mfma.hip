@@ -11,10 +11,8 @@
 // original column order (row stride odd => the lane=row reads are bank-conflict free); results go
 // through an LDS out-tile so that the global stores are coalesced 256-B row segments, with the
 // per-column norm applied on the way out (L1TP.py:256,269,284,297).
-#include "e3_common.h"
-
-#include <algorithm>
-#include <cstdlib>
+// The run lists of a class follow kL1Src (e3_l1tp_plan.h); the kernel, run_gemm and the stage lambda are the round-1 text.
+#include "e3_l1tp_mix.h"
 
 namespace e3 {
 
@@ -57,7 +55,6 @@ struct Mfma {
   size_t lds_bytes = 0;
 };
 
-constexpr int kLdsBudget = 160 * 1024;
 int mfma_set_lds_attr();
 
 int mfma_plan_init(e3_l1tp_plan* P) {
@@ -75,12 +72,7 @@ int mfma_plan_init(e3_l1tp_plan* P) {
     d.NT[c] = (p.M[c] + 31) / 32;
     d.Mpad[c] = d.NT[c] * 32;
     d.ocol_off[c] = p.ocol_off[c];
-    // source classes: scalars / same-parity (or dot) vectors / cross vectors
-    int src[3];
-    if (c == 0) { src[0] = 0; src[1] = 3; src[2] = -1; }       // 0e <- s0e, <v1o,Y1>
-    else if (c == 1) { src[0] = 1; src[1] = 2; src[2] = -1; }  // 0o <- s0o, <v1e,Y1>
-    else if (c == 2) { src[0] = 1; src[1] = 2; src[2] = 3; }   // 1e <- s0o (x) Y1, v1e Y0, v1o x Y1
-    else { src[0] = 0; src[1] = 3; src[2] = 2; }               // 1o <- s0e (x) Y1, v1o Y0, v1e x Y1
+    const int* src = kL1Src[c];  // source classes: scalars / same-parity (or dot) vectors / cross vectors
     int wrow = 0, orig = 0;
     for (int s = 0; s < 3; ++s) {
       d.roff[c][s] = (int)m->h_runs.size();
@@ -106,8 +98,8 @@ int mfma_plan_init(e3_l1tp_plan* P) {
   size_t wbytes = (size_t)d.wtotal * 4;
   auto waves_for = [&](size_t fixed, int nbuf) -> int {
     size_t per_wave = in_tile * nbuf + out_tile;
-    if (fixed + per_wave > (size_t)kLdsBudget) return 0;
-    return (int)std::min<size_t>(((size_t)kLdsBudget - fixed) / per_wave, 8);
+    if (fixed + per_wave > (size_t)kL1LdsBudget) return 0;
+    return (int)std::min<size_t>(((size_t)kL1LdsBudget - fixed) / per_wave, 8);
   };
   // preference: weights in LDS, then double buffering with >= 3 waves, else single buffer with more waves
   d.w_in_lds = waves_for(tables + wbytes, 1) >= 2 ? 1 : 0;
@@ -157,29 +149,18 @@ int64_t mfma_packed_bytes(const e3_l1tp_plan* P) {
 
 // packed = [W' (wtotal floats) | normcol (Dout floats)]
 template <typename T>
-__global__ void mfma_pack_kernel(const T* w0, const T* w1, const T* w2, const T* w3, const T* n0, const T* n1,
-                                 const T* n2, const T* n3, float* packed, MfmaDev d, PlanDev p, const PackRun* pr,
-                                 int npr) {
-  const T* w[4] = {w0, w1, w2, w3};
-  const T* nr[4] = {n0, n1, n2, n3};
+__global__ void mfma_pack_kernel(L1Ptr4<const T> w, L1Ptr4<const T> nrm, float* packed, MfmaDev d, PlanDev p,
+                                 const PackRun* pr, int npr) {
   for (int r = blockIdx.x; r < npr; r += gridDim.x) {
     PackRun q = pr[r];
     const int M = d.M[q.cls], Mpad = d.Mpad[q.cls];
     const float cg = (q.cls < 2) ? (q.kind == 0 ? 1.0f : (float)kC3) : (q.kind == 2 ? (float)kC6 : (float)kC3);
     for (int i = threadIdx.x; i < q.count * M; i += blockDim.x) {
       int k = i / M, mm = i - k * M;
-      packed[d.woff[q.cls] + (q.wrow + k) * Mpad + mm] = to_acc(w[q.cls][(int64_t)(q.orig_row + k) * M + mm]) * cg;
+      packed[d.woff[q.cls] + (q.wrow + k) * Mpad + mm] = to_acc(w.p[q.cls][(int64_t)(q.orig_row + k) * M + mm]) * cg;
     }
   }
-  if (blockIdx.x == 0) {
-    for (int c = 0; c < 4; ++c) {
-      int width = (c >= 2) ? 3 : 1;
-      for (int i = threadIdx.x; i < p.M[c] * width; i += blockDim.x) {
-        int mm = i / width, comp = i - mm * width;
-        packed[d.wtotal + p.ocol[p.ocol_off[c] + mm] + comp] = nr[c] ? to_acc(nr[c][i]) : 1.0f;
-      }
-    }
-  }
+  if (blockIdx.x == 0) l1_normcol_fill(p, nrm, packed + d.wtotal, threadIdx.x, blockDim.x);
 }
 
 int mfma_pack(const e3_l1tp_plan* P, const void* const w[4], const void* const n[4], int dtype, void* packed,
@@ -187,20 +168,18 @@ int mfma_pack(const e3_l1tp_plan* P, const void* const w[4], const void* const n
   Mfma* m = P->mfma;
   if (!m || !m->usable) return E3_OK;
   E3_HIP_CHECK(hipMemsetAsync(packed, 0, (size_t)m->dev.wtotal * 4, stream));
-  const void* nn[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (n)
-    for (int c = 0; c < 4; ++c) nn[c] = P->normlen[c] > 0 ? n[c] : nullptr;
   int npr = (int)m->h_pack.size();
   int grid = std::max(1, std::min(npr, 256));
-  if (dtype == E3_F32)
-    hipLaunchKernelGGL(mfma_pack_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)w[0],
-                       (const float*)w[1], (const float*)w[2], (const float*)w[3], (const float*)nn[0],
-                       (const float*)nn[1], (const float*)nn[2], (const float*)nn[3], (float*)packed, m->dev, P->dev,
-                       m->d_pack, npr);
-  else
-    hipLaunchKernelGGL(mfma_pack_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)w[0],
-                       (const bf16*)w[1], (const bf16*)w[2], (const bf16*)w[3], (const bf16*)nn[0], (const bf16*)nn[1],
-                       (const bf16*)nn[2], (const bf16*)nn[3], (float*)packed, m->dev, P->dev, m->d_pack, npr);
+  auto launch = [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    L1Ptr4<const T> nn = l1_ptr4<const T>(n);
+    for (int c = 0; c < 4; ++c)
+      if (P->normlen[c] <= 0) nn.p[c] = nullptr;
+    hipLaunchKernelGGL(mfma_pack_kernel<T>, dim3(grid), dim3(256), 0, stream, l1_ptr4<const T>(w), nn, (float*)packed,
+                       m->dev, P->dev, m->d_pack, npr);
+  };
+  if (dtype == E3_F32) launch(L1Tag<float>{});
+  else launch(L1Tag<bf16>{});
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }
@@ -484,8 +463,8 @@ __global__ __launch_bounds__(512) void l1tp_fwd_mfma_kernel(const float* __restr
 
 int mfma_set_lds_attr() {
   // the budget every plan's lds_bytes stays within, once per device (at the upload of the first plan)
-  const int st = ensure_dyn_lds((const void*)l1tp_fwd_mfma_kernel<true>, kLdsBudget);
-  return st != E3_OK ? st : ensure_dyn_lds((const void*)l1tp_fwd_mfma_kernel<false>, kLdsBudget);
+  const int st = ensure_dyn_lds((const void*)l1tp_fwd_mfma_kernel<true>, kL1LdsBudget);
+  return st != E3_OK ? st : ensure_dyn_lds((const void*)l1tp_fwd_mfma_kernel<false>, kL1LdsBudget);
 }
 
 int mfma_forward(const e3_l1tp_plan* P, const void* in1, int64_t ld1, const void* in2, int64_t ld2,
@@ -495,14 +474,9 @@ int mfma_forward(const e3_l1tp_plan* P, const void* in1, int64_t ld1, const void
   const MfmaDev& d = m->dev;
   int64_t ntiles = (B + 31) / 32;
   int grid = (int)std::min<int64_t>((ntiles + d.nwaves - 1) / d.nwaves, 256);
-  if (d.w_in_lds)
-    hipLaunchKernelGGL(l1tp_fwd_mfma_kernel<true>, dim3(grid), dim3(64 * d.nwaves), m->lds_bytes, stream,
-                       (const float*)in1, ld1, (const float*)in2, ld2, (const float*)packed, (float*)out, ldo, B,
-                       m->d_dev, m->d_runs, P->dev.ocol);
-  else
-    hipLaunchKernelGGL(l1tp_fwd_mfma_kernel<false>, dim3(grid), dim3(64 * d.nwaves), m->lds_bytes, stream,
-                       (const float*)in1, ld1, (const float*)in2, ld2, (const float*)packed, (float*)out, ldo, B,
-                       m->d_dev, m->d_runs, P->dev.ocol);
+  const auto kern = d.w_in_lds ? l1tp_fwd_mfma_kernel<true> : l1tp_fwd_mfma_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * d.nwaves), m->lds_bytes, stream, (const float*)in1, ld1,
+                     (const float*)in2, ld2, (const float*)packed, (float*)out, ldo, B, m->d_dev, m->d_runs, P->dev.ocol);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }

@@ -24,6 +24,9 @@ from . import _lib, profiling
 from .irreps import Instruction, Irreps, as_blocks
 
 _CLS = ("l0e", "l0o", "l1e", "l1o")
+# kL1Src of csrc/e3_l1tp_plan.h, restated: per output class the input classes of its weight-row blocks, in row order
+# (`L1TP.py:81-88`), each with the sign its block takes in the dual operator (the cross-product block is antisymmetric)
+_SRC = (((0, 1.0), (3, 1.0)), ((1, 1.0), (2, 1.0)), ((1, 1.0), (2, 1.0), (3, -1.0)), ((0, 1.0), (3, 1.0), (2, -1.0)))
 
 
 def _cls_name(l: int, p: int) -> str:
@@ -42,6 +45,15 @@ def _class_masks(irreps) -> dict:
             masks[_cls_name(l, p)][col:col + width] = True
         col += width
     return masks
+
+
+def _row_operands(in1: Tensor, in2: Tensor):
+    """-> (in1, in2, ld2) as the library takes them: last dimension contiguous, ld2 = 0 for one broadcast row of in2"""
+    if in1.stride(-1) != 1:
+        in1 = in1.contiguous()
+    if in2.stride(-1) != 1:
+        in2 = in2.contiguous()
+    return in1, in2, (0 if (in2.shape[0] == 1 and in1.shape[0] != 1) else in2.stride(0))
 
 
 def _Plan(in1_blocks, out_blocks) -> "_lib.DevicePlans":
@@ -261,11 +273,7 @@ class L1TensorProduct(Module):
         out = torch.empty((B, len(self.iro_l0e)), device=in1.device, dtype=in1.dtype)   # L1TP.py:240
         if B == 0:
             return out
-        if in1.stride(-1) != 1:
-            in1 = in1.contiguous()
-        if in2.stride(-1) != 1:
-            in2 = in2.contiguous()
-        ld2 = 0 if (in2.shape[0] == 1 and B != 1) else in2.stride(0)
+        in1, in2, ld2 = _row_operands(in1, in2)
         with torch.cuda.device(in1.device):
             packed = self._packed_weights(in1.dtype, in1.device)
             stream = torch.cuda.current_stream(in1.device).cuda_stream
@@ -296,11 +304,7 @@ class L1TensorProduct(Module):
                 if t is not None:
                     t.zero_()
             return g_in1, g_in2, g_w
-        if in1.stride(-1) != 1:
-            in1 = in1.contiguous()
-        if in2.stride(-1) != 1:
-            in2 = in2.contiguous()
-        ld2 = 0 if (in2.shape[0] == 1 and B != 1) else in2.stride(0)
+        in1, in2, ld2 = _row_operands(in1, in2)
         code = _lib.dtype_code(dtype)
         from . import tensor_product as _tp
         if (B >= _tp._BWD_GEMM_MIN_ROWS and dtype == torch.float32 and need_in1 and not need_in2 and ld2 != 0 and
@@ -358,26 +362,22 @@ class L1TensorProduct(Module):
                 getattr(dual, "norm_" + c).fill_(1.0)
             dual.requires_grad_(False)
             object.__setattr__(self, "_dual", dual)   # not a submodule: no parameters of its own, rebuilt from self's
-        if dual._weights()[0] is None and dual._weights()[1] is None and dual._weights()[2] is None and dual._weights()[3] is None:
+        dual_ws = [w for w in dual._weights() if w is not None]
+        if not dual_ws:
             return torch.zeros_like(in1, memory_format=torch.contiguous_format)
-        if next((w for w in dual._weights() if w is not None)).device != dev or \
-                next((w for w in dual._weights() if w is not None)).dtype != in1.dtype:
+        if dual_ws[0].device != dev or dual_ws[0].dtype != in1.dtype:
             dual.to(device=dev, dtype=in1.dtype)
-        n0e, n0o, n1e, n1o = self.num_i1_l0e, self.num_i1_l0o, self.num_i1_l1e, self.num_i1_l1o
-        W = dict(zip(_CLS, ws))
+        n = (self.num_i1_l0e, self.num_i1_l0o, self.num_i1_l1e, self.num_i1_l1o)       # in1 channels per class
+        nd = (dual.num_i1_l0e, dual.num_i1_l0o, dual.num_i1_l1e, dual.num_i1_l1o)      # the dual's = out channels per class
 
-        def blk(c, r0, n):   # rows r0 .. r0 + n of the forward matrix of class c, transposed; zeros when the class is absent
-            w = W[c]
-            return None if (w is None or n == 0) else w.detach()[r0:r0 + n].t()
+        def blk(o, c):   # the rows that in class c has in the forward matrix of out class o, transposed; None when absent
+            srcs = [i for i, _ in _SRC[o]]
+            r0 = sum(n[i] for i in srcs[:srcs.index(c)])
+            return None if (ws[o] is None or n[c] == 0) else ws[o].detach()[r0:r0 + n[c]].t()
 
-        rows = {   # dual class -> [(block or None, rows of the block = multiplicity of the dual's in class), ...]
-            "l0e": [(blk("l0e", 0, n0e), dual.num_i1_l0e, 1.0), (blk("l1o", 0, n0e), dual.num_i1_l1o, 1.0)],
-            "l0o": [(blk("l0o", 0, n0o), dual.num_i1_l0o, 1.0), (blk("l1e", 0, n0o), dual.num_i1_l1e, 1.0)],
-            "l1e": [(blk("l0o", n0o, n1e), dual.num_i1_l0o, 1.0), (blk("l1e", n0o, n1e), dual.num_i1_l1e, 1.0),
-                    (blk("l1o", n0e + n1o, n1e), dual.num_i1_l1o, -1.0)],
-            "l1o": [(blk("l0e", n0e, n1o), dual.num_i1_l0e, 1.0), (blk("l1o", n0e, n1o), dual.num_i1_l1o, 1.0),
-                    (blk("l1e", n0o + n1e, n1o), dual.num_i1_l1e, -1.0)],
-        }
+        # dual class c -> [(block or None, rows of the block = multiplicity of the dual's in class o, sign), ...]: the dual's
+        # block (c <- o) is the forward's block (o <- c), and the two tables are the same (e3_l1tp_plan.h, kL1Dst)
+        rows = {_CLS[c]: [(blk(o, c), nd[o], sign) for o, sign in _SRC[c]] for c in range(4)}
         with torch.no_grad():
             for c in _CLS:
                 wd = getattr(dual, "weights_" + c, None)
