@@ -214,6 +214,43 @@ int e3_rg_fill_cell(int64_t N, const e3_rg_params* prm, const float cell[9], con
                     const float* sorted_pos4, const int32_t* rowptr, int32_t* src,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Capped rows: per node the k nearest neighbours inside r, k in [1, 64] (radius_graph(..., max_neighbors=k)).  Everything up
+ * to the edge test is the uncapped builder of the mode: wrapping, grid, Morton order, perm, sorted_pos4 and the edge test with
+ * its explicitly rounded d2 (and image shift).  Call the sources that pass the test for row i its full neighbourhood, of
+ * size deg_i (what the count pass counts).
+ *   deg_i <= k : the row is the uncapped row: the same ids in the same order.
+ *   deg_i >  k : the row keeps the k sources with the smallest key (d2, j): d2 is the fp32 value the edge test computed for
+ *                the pair (the same bits, image shift included), j the source's new (Morton) id; d2 is compared first, ties
+ *                on d2 go to the lower j.  The kept ids are written in ascending j, as in every other row.
+ *   rowptr     : the exclusive scan of min(deg_i, k).
+ * All integer outputs stay bit-exact functions of the inputs.  The capped graph is DIRECTED: j -> i can exist without
+ * i -> j (j among the k nearest of i does not make i one of the k nearest of j).
+ *
+ * Call sequence: e3_rg_sort_count* (unchanged: rowptr_full, and the full degrees stay in the workspace)
+ *   -> e3_rg_cap_rowptr (rowptr_capped, stats) -> read E = rowptr_capped[N] and stats -> e3_rg_fill_nearest* (fills src)
+ * on the same stream, with the same prm / periodic / cell and the same workspace in the first and the last call.
+ *
+ * e3_rg_cap_rowptr: deg_i is the WRAPPING int32 difference rowptr_full[i + 1] - rowptr_full[i] (each degree is below 2^31
+ * even when the running sum has wrapped, i.e. when the uncapped graph does not fit int32).  rowptr_capped [N+1] may be the
+ * buffer of rowptr_full (every degree is read before the first entry is written).  stats (device, 2 x int64): the number of
+ * rows with deg_i > k, and the full edge count sum deg_i in 64 bits.  workspace: e3_rg_cap_workspace_bytes(N) bytes of its
+ * own (the capped degrees and the scan's temporary storage; NOT the builder's workspace, whose contents the fill still needs).
+ * e3_rg_fill_nearest*: src [E] int32.  One wave per non-empty cell, as the plain fill; a row above k keeps a sorted best-k
+ * across the wave and merges batches of 64 candidates into it; a neighbourhood of more than 1024 candidates arrives in
+ * several chunks, between which such a row parks its best ids in its own k slots of src.  No scratch beyond the builder's
+ * workspace.  k outside [1, 64] or a NULL pointer: E3_ERR_INVALID_ARG before any launch. */
+int64_t e3_rg_cap_workspace_bytes(int64_t N);
+int e3_rg_cap_rowptr(const int32_t* rowptr_full, int64_t N, int k, int32_t* rowptr_capped, int64_t* stats,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+int e3_rg_fill_nearest(int64_t N, const e3_rg_params* prm, const float* sorted_pos4, const int32_t* rowptr_capped, int k,
+                       int32_t* src, void* workspace, int64_t workspace_bytes, void* stream);
+int e3_rg_fill_nearest_pbc(int64_t N, const e3_rg_params* prm, int32_t periodic, const float* sorted_pos4,
+                           const int32_t* rowptr_capped, int k, int32_t* src,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int e3_rg_fill_nearest_cell(int64_t N, const e3_rg_params* prm, const float cell[9], const float origin[3],
+                            const float* sorted_pos4, const int32_t* rowptr_capped, int k, int32_t* src,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =================================================================================================
  * Edge / node stages of the SEGNN forward around the tensor product (builder-defined, SURVEY.md
  * §8a-N2, N3; fp32).  Graph = CSR by dst from e3_rg_* (rowptr [N+1], src [E], positions pos4 [N,4]).

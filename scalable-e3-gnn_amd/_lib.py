@@ -136,6 +136,15 @@ SIGNATURES = {
                                       c_int64, c_void_p]),
     "e3_rg_fill_cell": (c_int, [c_int64, c_void_p, Float9, Float3, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                 c_void_p]),
+    # capped rows, the k nearest inside r (rowptr_full, N, k, rowptr_capped, stats[2] int64, workspace, bytes, stream), and
+    # the fills of the three modes (..., sorted_pos4, rowptr_capped, k, src, workspace, bytes, stream)
+    "e3_rg_cap_workspace_bytes": (c_int64, [c_int64]),
+    "e3_rg_cap_rowptr": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_rg_fill_nearest": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_rg_fill_nearest_pbc": (c_int, [c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                       c_void_p]),
+    "e3_rg_fill_nearest_cell": (c_int, [c_int64, c_void_p, Float9, Float3, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_int64, c_void_p]),
     "e3_edge_geometry_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, Float9, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
     "e3_edge_geometry_l2_cell": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, Float9, c_void_p, c_void_p, c_void_p,

@@ -26,20 +26,25 @@ import math
 import torch
 from torch import nn
 
-from .radius_graph import RadiusGraph, radius_graph
+from .radius_graph import RadiusGraph, check_max_neighbors, radius_graph
 from .segnn import SEGNN
 
 
-def batched_radius_graph(pos: torch.Tensor, batch: torch.Tensor, r: float):
+def batched_radius_graph(pos: torch.Tensor, batch: torch.Tensor, r: float, max_neighbors=None):
     """pos [N,3] fp32 on a ROCm device, batch [N] integer molecule id of every atom (any order, ids 0..n_mol-1).
-    -> (RadiusGraph over all atoms with intra-molecular edges only, mol_of_node [N] int64 in the graph's node order)"""
+    -> (RadiusGraph over all atoms with intra-molecular edges only, mol_of_node [N] int64 in the graph's node order)
+
+    ``max_neighbors`` (None or an int in [1, 64]): the cap of ``radius_graph(max_neighbors=)`` -- every atom keeps its k
+    nearest neighbours inside ``r``; the distances are those of the lattice copy the search runs on, and the graph is
+    then directed."""
+    check_max_neighbors(max_neighbors)
     if not pos.is_cuda:
         raise RuntimeError("batched_radius_graph runs on ROCm tensors only; there is no CPU path")
     batch = batch.long()
     N = pos.shape[0]
     n_mol = int(batch.max().item()) + 1 if N else 0
     if N == 0:
-        g = radius_graph(pos, r, [0.0] * 3, [1.0] * 3)
+        g = radius_graph(pos, r, [0.0] * 3, [1.0] * 3, max_neighbors=max_neighbors)
         return g, batch
     idx = batch[:, None].expand(-1, 3)
     pmin = torch.full((n_mol, 3), float("inf"), device=pos.device).scatter_reduce(0, idx, pos, "amin")
@@ -53,7 +58,7 @@ def batched_radius_graph(pos: torch.Tensor, batch: torch.Tensor, r: float):
     hi = [side * cell + float(r), side * cell + float(r), nz * cell + float(r)]
     if max(hi) / float(r) > 1000:
         raise RuntimeError("batch too large for one lattice pass (cell grid > 1000 cells per axis): split the batch")
-    g = radius_graph(shifted.contiguous(), r, [0.0, 0.0, 0.0], hi)
+    g = radius_graph(shifted.contiguous(), r, [0.0, 0.0, 0.0], hi, max_neighbors=max_neighbors)
     perm = g.perm.long()
     pos4 = torch.zeros((N, 4), dtype=torch.float32, device=pos.device)
     pos4[:, :3] = pos[perm]

@@ -11,6 +11,10 @@ downstream (geometry, message kernels, forces) uses the minimum-image edge vecto
 General (triclinic) cells (``cell=``, rows = lattice vectors, periodic on all three): coordinates are wrapped into the cell
 and the grid runs over the fractional coordinates scaled by the perpendicular heights (``e3_rg_sort_count_cell``); the
 graph then carries ``cell`` / ``origin`` / ``volume`` instead of ``box`` and every edge stage selects its ``*_cell`` entry.
+
+Capped rows (``max_neighbors=k``, any of the three periodicities): the count pass is followed by ``e3_rg_cap_rowptr`` and
+``e3_rg_fill_nearest*`` instead of ``e3_rg_fill*``; every node keeps its k nearest neighbours inside ``r`` and the graph is
+directed (include/e3gnn.h, "Capped rows").
 """
 from __future__ import annotations
 
@@ -39,6 +43,13 @@ class RadiusGraph:
     cell: tuple | None = None    # 9 fp32-exact floats, row-major, rows = lattice vectors; None = no general cell
     origin: tuple | None = None  # 3 fp32-exact floats: the corner of the cell (None without a cell)
     volume: float | None = None  # |det cell| (fp32-exact; None without a cell)
+    max_neighbors: int | None = None  # the cap k of a capped graph (rows = the k nearest inside r); None = every pair
+    truncated: int = 0                # rows cut by the cap (0 uncapped)
+    full_edges: int | None = None     # the uncapped edge count (None = num_edges: the graph is uncapped)
+
+    def __post_init__(self):
+        if self.full_edges is None:
+            self.full_edges = self.num_edges
 
     @property
     def cell_arg(self):
@@ -191,8 +202,40 @@ def _edge_count(rowptr, N) -> int:
     return int(E)
 
 
-def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, cell=None, origin=None) -> RadiusGraph:
+MAX_NEIGHBORS_LIMIT = 64  # one candidate per lane of the wave that selects a capped row (e3_rg_fill_nearest)
+
+
+def check_max_neighbors(max_neighbors):
+    """``None`` or an int in [1, 64] (``bool`` is not an int here); ``ValueError`` otherwise."""
+    if max_neighbors is None:
+        return None
+    if isinstance(max_neighbors, bool) or not isinstance(max_neighbors, int) or \
+            not 1 <= max_neighbors <= MAX_NEIGHBORS_LIMIT:
+        raise ValueError(f"max_neighbors must be None or an int in [1, {MAX_NEIGHBORS_LIMIT}], got {max_neighbors!r}")
+    return max_neighbors
+
+
+def _capped_counts(rowptr, stats, N):
+    """One host read of a capped build -> (E, rows cut, full edge count).  The int32 guard of ``_edge_count`` applies to the
+    capped count: a capped degree is in [0, k], so a wrapped running sum shows as a negative E or a decreasing rowptr."""
+    mindeg = (rowptr[1:] - rowptr[:-1]).min() if N > 0 else rowptr[-1] * 0
+    E, mindeg, cut, full = torch.cat([torch.stack([rowptr[-1], mindeg]).long(), stats]).tolist()
+    if E < 0 or mindeg < 0:
+        raise RuntimeError("radius_graph: the capped edge count does not fit int32 (>= 2^31 edges); shard the cloud "
+                           "(sharding.SlabHalo) or lower max_neighbors")
+    return int(E), int(cut), int(full)
+
+
+def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, cell=None, origin=None,
+                 max_neighbors=None) -> RadiusGraph:
     """pos [N,3] fp32 on a ROCm device.  ``lo``/``hi``: bounding box (computed from pos when omitted).
+
+    ``max_neighbors`` (None or an int k in [1, 64]): cap every node at its k nearest neighbours inside ``r``.  A row with at
+    most k neighbours is unchanged; a longer row keeps the k sources with the smallest ``(d2, id)`` -- the fp32 ``d2`` of the
+    edge test, ties to the lower new id -- still in ascending id (include/e3gnn.h, "Capped rows").  The capped graph is
+    DIRECTED: ``j -> i`` can exist without ``i -> j``.  The graph records ``max_neighbors``, ``truncated`` (rows cut) and
+    ``full_edges`` (the uncapped count, which may exceed int32: only the capped count has to fit).  ``ValueError`` for
+    anything else; None is the uncapped call, launch for launch.
 
     ``periodic``: bool or 3 bools; periodic axes wrap at ``[lo, hi)`` (then ``lo`` / ``hi`` are required and
     ``2 r < hi - lo``).  Positions may lie outside the box on those axes; ``pos4`` holds them wrapped.
@@ -201,6 +244,7 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, 
     (0,0,0)): a general cell, periodic on all three directions; needs ``2 r <`` every perpendicular height and excludes
     ``lo`` / ``hi`` / ``periodic`` (``ValueError``).  The graph carries ``cell`` / ``origin`` / ``volume``; ``box`` stays
     None."""
+    k = check_max_neighbors(max_neighbors)
     if cell is not None:
         if lo is not None or hi is not None or not (periodic is False or periodic is None):
             raise ValueError("cell= describes the whole periodic cell: it cannot be combined with lo / hi / periodic")
@@ -237,8 +281,21 @@ def radius_graph(pos: torch.Tensor, r: float, lo=None, hi=None, periodic=False, 
         rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
         _lib.call("e3_rg_sort_count" + suffix, pos.data_ptr(), N, ctypes.byref(p), *extra, perm.data_ptr(), pos4.data_ptr(),
                   rowptr.data_ptr(), ws.data_ptr(), wbytes, stream)
-        E = _edge_count(rowptr, N)
-        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        _lib.call("e3_rg_fill" + suffix, N, ctypes.byref(p), *extra, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
-                  ws.data_ptr(), wbytes, stream)
+        if k is None:
+            E = _edge_count(rowptr, N)
+            src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+            _lib.call("e3_rg_fill" + suffix, N, ctypes.byref(p), *extra, pos4.data_ptr(), rowptr.data_ptr(), src.data_ptr(),
+                      ws.data_ptr(), wbytes, stream)
+        else:
+            # the capped row pointer replaces the full one in place: the full degrees stay in the workspace for the fill
+            cbytes = lib.e3_rg_cap_workspace_bytes(N)
+            cws = torch.empty(max(int(cbytes), 16), dtype=torch.uint8, device=dev)
+            stats = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.call("e3_rg_cap_rowptr", rowptr.data_ptr(), N, k, rowptr.data_ptr(), stats.data_ptr(), cws.data_ptr(),
+                      cbytes, stream)
+            E, cut, full = _capped_counts(rowptr, stats, N)
+            src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+            _lib.call("e3_rg_fill_nearest" + suffix, N, ctypes.byref(p), *extra, pos4.data_ptr(), rowptr.data_ptr(), k,
+                      src.data_ptr(), ws.data_ptr(), wbytes, stream)
+            fields.update(max_neighbors=k, truncated=cut, full_edges=full)
     return RadiusGraph(perm, pos4, rowptr, src[:E], E, (tuple(p.n), p.bits), **fields)
