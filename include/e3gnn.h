@@ -105,7 +105,9 @@ int e3_l1tp_forward(const e3_l1tp_plan* plan,
  * grad_weights[cls] (same shapes as weights) are overwritten.  When in2 was broadcast
  * (ld_in2 == 0) grad_in2 is a single row [1,4].  `workspace` must hold
  * e3_l1tp_backward_workspace_bytes() bytes.  Any of grad_in1 / grad_in2 / grad_weights may be
- * NULL to skip that gradient.
+ * NULL to skip that gradient.  grad_out has row stride ld_gout >= out_dim, grad_in1 row stride
+ * ld_gin1 >= in1_dim; grad_in2 is contiguous.  As in e3_l1tp_forward, a leading dimension below
+ * the row width, or ld_in2 in {1, 2, 3}, is E3_ERR_INVALID_ARG before any launch.
  */
 int64_t e3_l1tp_backward_workspace_bytes(const e3_l1tp_plan* plan, int64_t B, int dtype);
 int e3_l1tp_backward(const e3_l1tp_plan* plan,

@@ -400,6 +400,7 @@ int e3_l1tp_backward(const e3_l1tp_plan* plan, const void* in1, int64_t ld_in1, 
   if (B == 0) return E3_OK;  // caller zero-fills
   if (!in1 || !in2 || !grad_out || !workspace) return E3_ERR_INVALID_ARG;
   if (ld_in1 < plan->dev.D1 || ld_gout < plan->dev.Dout || (grad_in1 && ld_gin1 < plan->dev.D1)) return E3_ERR_INVALID_ARG;
+  if (ld_in2 != 0 && ld_in2 < 4) return E3_ERR_INVALID_ARG;  // as e3_l1tp_forward: rows of in2 do not overlap
   for (int c = 0; c < 4; ++c)
     if (plan->dev.M[c] > 0 && !(plan->wrows[c] > 0 && weights[c])) return E3_ERR_MISSING_WEIGHT;
   int st = ensure_device(plan);
