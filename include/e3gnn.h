@@ -968,6 +968,66 @@ int e3_halo_reduce(const void* g, int64_t ld_g, const void* back, int64_t ld_bac
                    const int32_t* red_ptr, const int32_t* red_k, int64_t n, int D, int dtype, void* out, int64_t ld_out,
                    void* stream);
 
+/* =================================================================================================
+ * Image rows: periodic cells below twice the cutoff (cell_images.CellImages).  The cloud is extended by explicit lattice
+ * images and the graph over [owned (wrapped) | images] is built OPEN (e3_rg_sort_count), so every open edge-stage kernel
+ * serves a cell of any size; an image row is refreshed from its owner before every layer and its gradient returns to it.
+ * cell / origin / frac / shift / wrap: "General (triclinic) periodic cell" above.  No contraction in any fp32 operation.
+ *
+ * Selection.  rho = r + 2^-18 (r + sum_k |cell[k]| + sum_a |origin[a]|), evaluated in fp64 in that order and rounded UP to
+ *   fp32; shells m_a = max(1, ceil(rho / h_a)) (fp64 quotient of the fp32 values; rho, not r: a wrapped fraction that rounding
+ *   left at 1 then cannot need shell m_a + 1).  e3_cell_images_plan (host only) returns both, the shells as they are (capped
+ *   at 2^20) so that a caller can name the limit; more than E3_CELL_IMAGE_MAX_SHELLS on an axis is E3_ERR_INVALID_ARG in
+ *   count / fill.
+ *   For a particle with wrapped position w and s = frac(fl(w - origin)), the shift n != 0, n_a in [-m_a, m_a], is kept iff on
+ *   every axis   fl(fl(s_a + n_a) h_a) >= -rho   and   fl(fl(fl(s_a + n_a) - 1) h_a) <= rho:
+ *   the image's cell lies within rho of the home cell along the normal of each face pair.  This is a superset of the images
+ *   an edge can use (an edge needs |d| <= r, hence at most r along every normal); the edge test stays the graph builder's.
+ *   Margin, in ulp (2^-24) of a length: s_a h_a carries 7 roundings (the subtraction, three products, two sums, the rounding
+ *   of G) of terms bounded by |w - origin| <= sum |cell[k]|; the test's sum, difference and two products are 3 roundings of
+ *   values up to |s_a + n_a| h_a <= 8 h_a, i.e. 24 of h_a <= sum |cell[k]|; the image position fl(w + n cell) carries 4 of a
+ *   coordinate of at most |origin| + 8 sum |cell[k]|, i.e. 32 of sum |cell[k]| and 4 of |origin|; the builder's d2 2 of r.
+ *   Together 63 of sum |cell[k]|, 4 of sum |origin[a]| and 2 of r: below 64 ulp = 2^-18 of their sum, which grows with the
+ *   cell.
+ *   e3_cell_images_count : pos [N,3] (may be unwrapped) -> pos_wrapped [N,3] and offsets [N + 1] int32, the exclusive scan
+ *             of the per-particle image counts; offsets[N] = G is the ONE value the host reads.  workspace >=
+ *             e3_cell_images_workspace_bytes(N) (-1 for N outside [0, 2^31 - 1)).
+ *   e3_cell_images_fill  : owner [G] int32, shift [G,3] int32 and image_pos [G,3] = shift(w_owner, -n) = fl(w + n cell),
+ *             ordered by (owner ascending, shift lexicographic with n_0 most significant): deterministic, no atomics.
+ *             Same cell / origin / r as the count; a particle writes inside [offsets[i], min(offsets[i+1], G)) only.
+ *   E3_ERR_INVALID_ARG before any launch for a cell that does not derive, a non-finite origin, r not finite or <= 0,
+ *   N (2 m_0 + 1)(2 m_1 + 1)(2 m_2 + 1) >= 2^31 - 1 (so N + G fits int32), N + G >= 2^31 - 1, a short workspace or a NULL
+ *   pointer that is needed.  N = 0 is valid: offsets[0] = 0, nothing else is touched.
+ *
+ * Rows [M, D] with a leading dimension (elements), in any numbering; source [M] int32: source[i] = i on an owned row, the
+ * owner's row on an image row (an image row is never a source).
+ *   e3_image_rows_expand : out[i] = in[source[i]]; dtype E3_F32, E3_BF16 or E3_F64 (a byte copy).  A source outside [0, M)
+ *             writes a zero row.  out == in (same leading dimension) is the in-place form: only the rows with
+ *             source[i] != i are written.  shift [M,3] int32 with cell (both or neither; D = 3 and E3_F32 only):
+ *             out[i] = shift(in[source[i]], -shift[i]) = fl(in[source[i]] + n_i cell), the positions of the extended cloud.
+ *   e3_image_rows_reduce : the transpose.  out[i] = source[i] == i ? g[i] + sum_{q = ptr[i]}^{ptr[i+1] - 1} g[rows[q]] : 0;
+ *             ptr [M + 1] / rows [n_rows] int32: the image rows grouped by owner (CSR), ascending inside a row.  The sum
+ *             starts from the row's own value and adds the list in its order, in the rows' dtype (E3_F32 or E3_F64): no
+ *             atomics, bit-equal from run to run.  List bounds are clamped to [0, n_rows]; a row id outside [0, M) adds
+ *             nothing.  out must not be g.
+ *   One wave per row; 16-byte accesses when every pointer is 16-byte aligned and every leading dimension is a multiple of 16
+ *   bytes, the remaining columns (or all) element by element: same values either way.  E3_ERR_INVALID_ARG before any launch
+ *   for M outside [0, 2^31 - 1), D < 1, a leading dimension below D, another dtype, a shift without a cell (or the reverse,
+ *   or with D != 3 / another dtype), an in-place call with two leading dimensions, and, when M > 0, a NULL pointer that is
+ *   needed.  M = 0 returns E3_OK and launches nothing.
+ * ================================================================================================= */
+#define E3_CELL_IMAGE_MAX_SHELLS 7
+int e3_cell_images_plan(const float cell[9], const float origin[3], float r, int32_t shells[3], float* rho);  /* host only */
+int64_t e3_cell_images_workspace_bytes(int64_t N);
+int e3_cell_images_count(const float* pos, int64_t N, const float cell[9], const float origin[3], float r, float* pos_wrapped,
+                         int32_t* offsets, void* workspace, int64_t workspace_bytes, void* stream);
+int e3_cell_images_fill(const float* pos_wrapped, int64_t N, const float cell[9], const float origin[3], float r,
+                        const int32_t* offsets, int64_t G, int32_t* owner, int32_t* shift, float* image_pos, void* stream);
+int e3_image_rows_expand(const void* in, int64_t ld_in, const int32_t* source, const int32_t* shift, const float cell[9],
+                         int64_t M, int D, int dtype, void* out, int64_t ld_out, void* stream);
+int e3_image_rows_reduce(const void* g, int64_t ld_g, const int32_t* source, const int32_t* ptr, const int32_t* rows,
+                         int64_t n_rows, int64_t M, int D, int dtype, void* out, int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

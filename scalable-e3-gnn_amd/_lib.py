@@ -252,6 +252,18 @@ SIGNATURES = {
                                 c_int64, c_void_p]),
     "e3_halo_reduce": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                c_int, c_void_p, c_int64, c_void_p]),
+    # image rows of a small periodic cell: (cell, origin, r, shells int32[3], rho), the count / fill pair of the selection
+    # (pos, N, cell, origin, r, ...) and the row pair (rows, ld, source, [shift, cell | ptr, rows, n_rows], M, D, dtype, out, ld)
+    "e3_cell_images_plan": (c_int, [Float9, Float3, ctypes.c_float, Int3, POINTER(ctypes.c_float)]),
+    "e3_cell_images_workspace_bytes": (c_int64, [c_int64]),
+    "e3_cell_images_count": (c_int, [c_void_p, c_int64, Float9, Float3, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p]),
+    "e3_cell_images_fill": (c_int, [c_void_p, c_int64, Float9, Float3, ctypes.c_float, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    "e3_image_rows_expand": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, POINTER(ctypes.c_float), c_int64, c_int, c_int,
+                                     c_void_p, c_int64, c_void_p]),
+    "e3_image_rows_reduce": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p,
+                                     c_int64, c_void_p]),
 }
 
 

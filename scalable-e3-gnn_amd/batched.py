@@ -126,7 +126,8 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
 
     ``halo`` / ``split`` (sharded path; ``g`` = ``split.graph``): the readout is summed over THIS rank's owned rows, the
     ghost rows are refreshed by ``halo.refresh`` in every layer, and ``halo.anchor`` is among the differentiated inputs, so
-    the backward of every refresh runs on every rank; dE/dpos_g then covers the local cloud, ghost rows included."""
+    the backward of every refresh runs on every rank; dE/dpos_g then covers the local cloud, ghost rows included.  A
+    ``cell_images.CellImages`` serves as ``halo`` in one process (image rows of a small cell; its ``anchor`` is None)."""
     from . import ops
     with torch.enable_grad():
         p = pos_g.detach().float().requires_grad_(forces)
@@ -141,7 +142,9 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
             energy = e_node[:, 0].sum()
         else:
             energy = torch.zeros(n_seg, dtype=e_node.dtype, device=e_node.device).index_add(0, seg, e_node[:, 0])
-        leaves = ([p] if forces else []) + ([eps] if eps is not None else []) + ([] if halo is None else [halo.anchor])
+        # halo.anchor: the leaf that keeps every rank's refresh in the backward (None for the image rows of one process)
+        anchor = None if halo is None else halo.anchor
+        leaves = ([p] if forces else []) + ([eps] if eps is not None else []) + ([] if anchor is None else [anchor])
         if create_graph:
             grads = list(torch.autograd.grad(energy.sum(), leaves, create_graph=True))
         else:
@@ -154,14 +157,18 @@ def _energy_and_gradients(net, x_g, g, pos_g, seg, n_seg, forces, n_strain, stru
 HESSIAN_MAX_ATOMS = 256   # hessian(): 3 N second backwards and a dense [N,3,N,3] result -- molecules and small cells
 
 
-def _hessian_vector_products(net, x_g, g, pos_g, v_g, cutoff_kw, xi=None, strained=False):
+def _hessian_vector_products(net, x_g, g, pos_g, v_g, cutoff_kw, xi=None, strained=False, halo=None, split=None):
     """H v for every v of ``v_g`` [K,N,3] (graph order) -> [K,N,3], H = d2(sum of the scalar node readout)/dpos_g^2 on the
     edge set of ``g``.  One forward, one first backward with ``create_graph=True`` -- the geometry with its position edge
     (``ops.edge_geometry(pos_hessian=True)``) -- and one second backward per vector on the retained graph.  Only the
     position leaf is differentiated: the parameters may be frozen and none of them gets a ``.grad``.
 
     ``strained`` (or an ``xi`` [K,3,3]): the same in the joint coordinates (pos_g, eps) at a zero strain eps of the whole graph
-    -> (h_pos [K,N,3], h_strain [K,3,3]) = the Hessian applied to (v, xi), either of which may be None (zero), not both."""
+    -> (h_pos [K,N,3], h_strain [K,3,3]) = the Hessian applied to (v, xi), either of which may be None (zero), not both.
+
+    ``halo`` / ``split`` (a ``cell_images.CellImages`` and its split graph, ``g`` = ``split.graph``): N counts the rows of the
+    extended cloud, the readout is summed over the owned rows and every layer refreshes the image rows differentiably; the
+    caller extends ``v`` to the image rows and reduces the product (H = E^T H_ext E)."""
     from . import ops
     if x_g.dtype == torch.bfloat16:
         raise NotImplementedError("hessian_vector_product with bf16 storage: bf16 runs the fused inference kernels only and "
@@ -181,7 +188,9 @@ def _hessian_vector_products(net, x_g, g, pos_g, v_g, cutoff_kw, xi=None, strain
             eps = torch.zeros((1, 3, 3), dtype=torch.float32, device=p.device, requires_grad=True) if strained else None
             leaves = [p] + ([eps] if strained else [])
             geometry = ops.edge_geometry(g, lmax=net.lmax, pos=p, strain=eps)
-            e_node = net(x_g, g, geometry=geometry, **(cutoff_kw or {}))
+            e_node = net(x_g, g, geometry=geometry, halo=halo, split=split, **(cutoff_kw or {}))
+            if halo is not None:
+                e_node = e_node[halo.owned_new]
             first = torch.autograd.grad(e_node[:, 0].sum(), leaves, create_graph=True)
         out = []
         for k in range(K):
@@ -336,6 +345,35 @@ class BatchedEnergyModel(nn.Module):
         return _dense_hessian(lambda vs: self.hessian_vector_product(x, pos, batch, r, vs, skin=skin, neighbors=neighbors), pos)
 
 
+def _graph_volume(g) -> float:
+    """V of a fully periodic graph: |det cell|, or L_x L_y L_z of a box"""
+    return float(g.volume) if g.cell is not None else float(g.box[0]) * float(g.box[1]) * float(g.box[2])
+
+
+_IMAGES_NEED_CELL = ("images= extends a general cell by its lattice images: it needs cell= (the lo / hi / periodic box form is not "
+                     "covered; pass the box as a diagonal cell)")
+_IMAGES_NO_LIST = ("images= with neighbors=: a Verlet list over image rows is not implemented (the list would have to follow the "
+                   "image selection); call without neighbors=")
+
+
+def _image_vectors(images, v):
+    """v [K,N,3] on the owned particles (caller order) -> [K,M,3] on the extended cloud, image rows copies of their owners'
+    (no translation: a direction has no lattice shift)"""
+    K, N = v.shape[0], v.shape[1]
+    M = images.n_owned + images.n_ghost
+    if K == 0:
+        return v.new_zeros((0, M, 3))
+    return images.extend(v.permute(1, 0, 2).reshape(N, 3 * K)).view(M, K, 3).permute(1, 0, 2).contiguous()
+
+
+def _reduce_vectors(images, h):
+    """the transpose of ``_image_vectors``: h [K,M,3] -> [K,N,3] in the caller's order"""
+    K, M = h.shape[0], h.shape[1]
+    if K == 0:
+        return h.new_zeros((0, images.n_owned, 3))
+    return images.reduce(h.permute(1, 0, 2).reshape(M, 3 * K)).view(images.n_owned, K, 3).permute(1, 0, 2).contiguous()
+
+
 class PeriodicEnergyModel(nn.Module):
     """SEGNN with a scalar node readout summed over a periodic (or partly periodic) orthorhombic box, or over a general
     (triclinic) cell: the energy, and on request forces, the virial and the stress of the box (conventions:
@@ -351,7 +389,7 @@ class PeriodicEnergyModel(nn.Module):
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, forces: bool = False,
                 virial: bool = False, stress: bool = False, cell=None, origin=None, skin: float = 0.0, neighbors=None,
-                create_graph: bool = False):
+                create_graph: bool = False, images=False):
         """x [N, in_dim], pos [N,3] (caller order; coordinates on periodic axes may be unwrapped).  -> the 0-d energy,
         then whichever of forces [N,3] (= -dE/dpos, caller order), virial W [3,3] (= -dE/deps at eps = 0, not
         symmetrised) and stress [3,3] (= (1/V) dE/deps = -W/V, V = L_x L_y L_z) were requested, in that order; the
@@ -374,9 +412,20 @@ class PeriodicEnergyModel(nn.Module):
         ``skin=`` and ``neighbors=``.  The graph leads to the parameters only: the derivative of the forces w.r.t. the
         positions is ``hessian_vector_product``.  ``NotImplementedError`` with ``virial=True`` / ``stress=True`` (the tangent kernel of
         the strained geometry exists, ``ops.edge_geometry(strain=)``, but a loss on the stress is not wired at model level) and
-        for bf16 storage.  False (the default) is the first-order call, unchanged."""
+        for bf16 storage.  False (the default) is the first-order call, unchanged.
+
+        ``images`` (with ``cell=``): False (the default) is the call above -- a cell with ``2 r >=`` a perpendicular height
+        is a ``ValueError``.  True extends the cloud by the lattice images within ``r`` of the cell
+        (``cell_images.CellImages``) and runs the OPEN graph over [particles | images], so a cell of any size works -- a
+        primitive cell, a one-atom cell -- up to 7 image shells per axis (``ValueError`` beyond); forces come out on the N
+        particles, an image's share added to its owner's in a fixed order; energy only under ``no_grad`` runs the fused
+        inference kernels.  "auto" takes that path only when the cell needs it (``2 (r + skin) >=`` a height) and is the
+        default call otherwise.  Everything above holds on the image path (``forces``, ``virial``, ``stress``, ``skin``,
+        ``create_graph``) except ``neighbors=`` (``NotImplementedError``); without ``cell=`` it is a ``ValueError``."""
         if create_graph:
             _check_create_graph(self.net, x, forces, virial or stress)
+        if self._use_images(images, r, lo, hi, periodic, cell, origin, skin, neighbors):
+            return self._forward_images(x, pos, r, cell, origin, skin, forces, virial, stress, create_graph)
         g, cut = self._graph(pos, r, lo, hi, periodic, cell, origin, skin, neighbors, stress)
         perm = g.perm.long()
         if not (forces or virial or stress):
@@ -391,8 +440,46 @@ class PeriodicEnergyModel(nn.Module):
         if virial:
             out.append(-geps[0])
         if stress:
-            V = float(g.volume) if g.cell is not None else float(g.box[0]) * float(g.box[1]) * float(g.box[2])
-            out.append((geps[0].double() / V).float())
+            out.append((geps[0].double() / _graph_volume(g)).float())
+        return tuple(out)
+
+    def _use_images(self, images, r, lo, hi, periodic, cell, origin, skin, neighbors) -> bool:
+        """Whether a call takes the image path; the refusals of ``images=`` (before anything is built)"""
+        if images is False:
+            return False
+        if images is not True and images != "auto":
+            raise ValueError(f'images must be False, True or "auto", got {images!r}')
+        if cell is None or lo is not None or hi is not None or periodic is not True:
+            raise ValueError(_IMAGES_NEED_CELL)
+        if neighbors is not None:
+            raise NotImplementedError(_IMAGES_NO_LIST)
+        if images is True:
+            return True
+        from .cell_images import CellImages
+        return CellImages(cell, origin).needs_images(_skin_radius(self.net, r, skin))
+
+    def _image_cloud(self, x, pos, r, cell, origin, skin):
+        """-> (CellImages, SplitGraph, x and pos of the extended cloud in graph order, the cutoff= of the net's forward)"""
+        from .cell_images import cell_image_graph
+        cut = _cutoff_kw(self.net, r)
+        return (*cell_image_graph(pos, x, _skin_radius(self.net, r, skin), cell, origin), cut)
+
+    def _forward_images(self, x, pos, r, cell, origin, skin, forces, virial, stress, create_graph):
+        """``forward`` over the image rows: the open graph of the extended cloud, the readout summed over the particles,
+        dE/dpos of the extended cloud reduced to the particles (differentiable: ``create_graph`` keeps it in the graph)"""
+        im, split, x_g, pos_g, cut = self._image_cloud(x, pos, r, cell, origin, skin)
+        if not (forces or virial or stress):
+            return self.net(x_g, split.graph, halo=im, split=split, **cut)[im.owned_new, 0].sum()
+        energy, gpos, geps = _energy_and_gradients(self.net, x_g, split.graph, pos_g, None, 1, forces,
+                                                   1 if (virial or stress) else 0, None, cut, halo=im, split=split,
+                                                   create_graph=create_graph)
+        out = [energy]
+        if forces:
+            out.append(-im.reduce(gpos))
+        if virial:
+            out.append(-geps[0])
+        if stress:
+            out.append((geps[0].double() / float(im.volume)).float())
         return tuple(out)
 
     def _graph(self, pos, r, lo, hi, periodic, cell, origin, skin, neighbors, stress=False):
@@ -416,15 +503,23 @@ class PeriodicEnergyModel(nn.Module):
         return g, cut
 
     def hessian_vector_product(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, cell=None,
-                               origin=None, v: torch.Tensor | None = None, skin: float = 0.0, neighbors=None) -> torch.Tensor:
+                               origin=None, v: torch.Tensor | None = None, skin: float = 0.0, neighbors=None,
+                               images=False) -> torch.Tensor:
         """H v, H = d2E/dpos2 on the edge set of the current graph (the lattice shift of every edge held fixed); ``v`` [N,3]
         or [K,N,3] in the caller's order -> a detached tensor of the shape of ``v``.  ``lo`` / ``hi`` / ``periodic`` /
         ``cell`` / ``origin`` / ``skin`` / ``neighbors`` select the graph exactly as in ``forward``: open box, box, cell,
         envelope, skin, Verlet list.  One forward and one first backward with ``create_graph=True``, then one second backward
         per vector (``e3_edge_geometry_hvp`` closes the chain) -- what vibrational frequencies, phonons at
         Gamma, dimer / Lanczos saddle searches and Newton-type relaxations consume.  Works on a frozen model in ``eval()``;
-        no parameter gets a ``.grad``.  fp32: bf16 storage raises ``NotImplementedError``."""
+        no parameter gets a ``.grad``.  fp32: bf16 storage raises ``NotImplementedError``.  ``images``: as in ``forward``;
+        on the image path ``v`` is copied to the image rows (a direction has no lattice shift) and the product is reduced
+        back to the N particles, H = E^T H_ext E."""
         vs = _check_vectors(v, pos)
+        if self._use_images(images, r, lo, hi, periodic, cell, origin, skin, neighbors):
+            im, split, x_g, pos_g, cut = self._image_cloud(x, pos, r, cell, origin, skin)
+            hv = _hessian_vector_products(self.net, x_g, split.graph, pos_g, _image_vectors(im, vs.float()), cut, halo=im,
+                                          split=split)
+            return _reduce_vectors(im, hv).reshape(v.shape)
         g, cut = self._graph(pos, r, lo, hi, periodic, cell, origin, skin, neighbors)
         perm = g.perm.long()
         hv = _hessian_vector_products(self.net, x[perm], g, pos[perm], vs[:, perm], cut)
@@ -432,21 +527,28 @@ class PeriodicEnergyModel(nn.Module):
         out[:, perm] = hv
         return out.reshape(v.shape)
 
-    def _strain_hvp(self, x, pos, r, lo, hi, periodic, cell, origin, v, strain_v, skin, neighbors, stress):
-        """-> (h_pos [K,N,3] caller order, h_strain [K,3,3], whether the caller's vectors carry no K, the graph);
-        ``stress``: refuse an open axis as ``forward(stress=True)`` does"""
+    def _strain_hvp(self, x, pos, r, lo, hi, periodic, cell, origin, v, strain_v, skin, neighbors, stress, images=False):
+        """-> (h_pos [K,N,3] caller order, h_strain [K,3,3], whether the caller's vectors carry no K, the volume | None);
+        ``stress``: refuse an open axis as ``forward(stress=True)`` does (the volume is returned then)"""
         vs, xs, single = _check_strain_vectors(v, strain_v, pos)
+        if self._use_images(images, r, lo, hi, periodic, cell, origin, skin, neighbors):
+            im, split, x_g, pos_g, cut = self._image_cloud(x, pos, r, cell, origin, skin)
+            hp, hs = _hessian_vector_products(self.net, x_g, split.graph, pos_g,
+                                              _image_vectors(im, vs.float()) if vs is not None else None, cut, xi=xs,
+                                              strained=True, halo=im, split=split)
+            return _reduce_vectors(im, hp), hs, single, float(im.volume)
         g, cut = self._graph(pos, r, lo, hi, periodic, cell, origin, skin, neighbors, stress)
         perm = g.perm.long()
         hp, hs = _hessian_vector_products(self.net, x[perm], g, pos[perm], vs[:, perm] if vs is not None else None, cut,
                                           xi=xs, strained=True)
         out = torch.empty_like(hp)
         out[:, perm] = hp
-        return out, hs, single, g
+        return out, hs, single, (_graph_volume(g) if stress else None)
 
     def strain_hessian_vector_product(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True,
                                       cell=None, origin=None, v: torch.Tensor | None = None,
-                                      strain_v: torch.Tensor | None = None, skin: float = 0.0, neighbors=None):
+                                      strain_v: torch.Tensor | None = None, skin: float = 0.0, neighbors=None,
+                                      images=False):
         """The Hessian of E in the joint coordinates (pos, eps) at eps = 0 -- eps the 3x3 strain of ``forward``'s virial, every
         edge vector r of the current graph becoming r + eps r -- applied to (v, Xi):
             h_pos = H v + Lambda Xi,   h_strain = Lambda^T v + B Xi,
@@ -456,12 +558,15 @@ class PeriodicEnergyModel(nn.Module):
         [K,3,3]) when the vectors carry a K; detached.  The graph arguments are those of ``forward``.  One forward, one first
         backward with ``create_graph=True``, one second backward per pair (``e3_edge_geometry_jvp_strained`` /
         ``e3_edge_geometry_hvp_strained`` close the chain).  Works on a frozen model in ``eval()``; no
-        parameter gets a ``.grad``.  fp32: bf16 storage raises ``NotImplementedError``."""
-        hp, hs, single, _ = self._strain_hvp(x, pos, r, lo, hi, periodic, cell, origin, v, strain_v, skin, neighbors, False)
+        parameter gets a ``.grad``.  fp32: bf16 storage raises ``NotImplementedError``.  ``images``: as in ``forward`` and
+        ``hessian_vector_product``; the strain is the global one of the open graph over the extended cloud, whose image
+        positions carry their lattice shift, so every edge vector is the true one."""
+        hp, hs, single, _ = self._strain_hvp(x, pos, r, lo, hi, periodic, cell, origin, v, strain_v, skin, neighbors, False,
+                                             images)
         return (hp[0], hs[0]) if single else (hp, hs)
 
     def elastic_tensor(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, cell=None,
-                       origin=None, skin: float = 0.0, neighbors=None):
+                       origin=None, skin: float = 0.0, neighbors=None, images=False):
         """-> (born [3,3,3,3], coupling [N,3,3,3]) of the current graph (the graph arguments of ``forward``):
             born[a,b,c,d]     = (1/V) d2E/deps_ab deps_cd    the Born (clamped-ion) elastic tensor,
             coupling[i,k,a,b] = d2E/dpos_ik deps_ab          the force-strain coupling (internal-strain tensor), caller order,
@@ -470,20 +575,20 @@ class PeriodicEnergyModel(nn.Module):
         |det cell|).  What it is NOT: it is the plain second derivative in the full 3x3 eps (nine independent components), not
         symmetrised -- ``voigt(born)`` contracts it with the symmetric strain basis -- and at a stressed state it differs from
         the stress-strain coefficients by terms in the stress.  The relaxed-ion constants are born - Lambda^T H^+ Lambda / V
-        with ``hessian()``, left to the caller."""
+        with ``hessian()``, left to the caller.  ``images``: as in ``forward`` (a small cell: V = |det cell|)."""
         unit = torch.eye(9, dtype=torch.float32, device=pos.device).view(9, 3, 3)
-        hp, hs, _, g = self._strain_hvp(x, pos, r, lo, hi, periodic, cell, origin, None, unit, skin, neighbors, True)
-        V = float(g.volume) if g.cell is not None else float(g.box[0]) * float(g.box[1]) * float(g.box[2])
+        hp, hs, _, V = self._strain_hvp(x, pos, r, lo, hi, periodic, cell, origin, None, unit, skin, neighbors, True, images)
         born = (hs.double() / V).float().view(3, 3, 3, 3).permute(2, 3, 0, 1).contiguous()   # hs[(c, d), a, b]
         coupling = hp.view(3, 3, pos.shape[0], 3).permute(2, 3, 0, 1).contiguous()             # hp[(a, b), i, k]
         return born, coupling
 
     def hessian(self, x: torch.Tensor, pos: torch.Tensor, r: float, lo=None, hi=None, periodic=True, cell=None, origin=None,
-                skin: float = 0.0, neighbors=None) -> torch.Tensor:
+                skin: float = 0.0, neighbors=None, images=False) -> torch.Tensor:
         """The dense H [N,3,N,3] (``H[i,a,j,b]`` = d2E/dpos[i,a] dpos[j,b]): ``hessian_vector_product`` on the 3 N unit vectors
-        in chunks.  ``ValueError`` above ``HESSIAN_MAX_ATOMS`` = 256 atoms: it is meant for molecules and small cells."""
+        in chunks.  ``ValueError`` above ``HESSIAN_MAX_ATOMS`` = 256 atoms: it is meant for molecules and small cells.
+        ``images``: as in ``forward``; the limit counts the N particles, not their image rows."""
         return _dense_hessian(lambda vs: self.hessian_vector_product(x, pos, r, lo, hi, periodic, cell, origin, vs, skin=skin,
-                                                                     neighbors=neighbors), pos)
+                                                                     neighbors=neighbors, images=images), pos)
 
 
 class ShardedEnergyModel(nn.Module):

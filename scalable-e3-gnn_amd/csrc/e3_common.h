@@ -106,6 +106,36 @@ __device__ __forceinline__ void min_image(const PbcCell& c, float& dx, float& dy
               n2 = rintf(cell_frac(c, 2, dx, dy, dz));
   cell_shift(c, n0, n1, n2, dx, dy, dz);
 }
+// general cell (the *_cell entries; include/e3gnn.h): lattice vectors and their inverse, the origin, and the perpendicular
+// heights (the grid is the open grid of q_a = s_a h_a in [0, h_a): g.lo = 0, 1 / g.inv = h_a / n_a)
+struct RgCell {
+  PbcCell c;
+  float o[3], hgt[3];
+};
+// fractional coordinates of p relative to the origin
+__device__ __forceinline__ void cell_s(const RgCell& rc, const float3 p, float (&s)[3]) {
+  const float x = __fsub_rn(p.x, rc.o[0]), y = __fsub_rn(p.y, rc.o[1]), z = __fsub_rn(p.z, rc.o[2]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) s[a] = cell_frac(rc.c, a, x, y, z);
+}
+// p wrapped into the cell: w = p - floor(s(p)) h, then one correction step per lattice direction from s(w)
+__device__ __forceinline__ float3 wrap_cell(const RgCell& rc, float3 p) {
+  float s[3];
+  cell_s(rc, p, s);
+  cell_shift(rc.c, floorf(s[0]), floorf(s[1]), floorf(s[2]), p.x, p.y, p.z);
+  cell_s(rc, p, s);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float n = s[a] >= 1.0f ? 1.0f : (s[a] < 0.0f ? -1.0f : 0.0f);
+    if (n != 0.0f) {
+      p.x = __fsub_rn(p.x, __fmul_rn(n, rc.c.h[3 * a + 0]));
+      p.y = __fsub_rn(p.y, __fmul_rn(n, rc.c.h[3 * a + 1]));
+      p.z = __fsub_rn(p.z, __fmul_rn(n, rc.c.h[3 * a + 2]));
+    }
+  }
+  return p;
+}
+
 // edge vector x_src - x_dst of the geometry kernels; kBox / kCell: its minimum image (the rint form, so unwrapped
 // coordinates work too)
 template <int PBC>

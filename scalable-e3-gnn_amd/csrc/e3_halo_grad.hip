@@ -3,21 +3,12 @@
 // column groups (float4 / double2) when every pointer and every row pitch allows them, the D % (16 / sizeof(T)) columns left
 // over -- or the whole row otherwise -- one element per lane.  The row index is wave-uniform, so slot[i], red_ptr[i] and the
 // red_k of a row are scalar loads.  No atomics: a row's sum is taken by one wave in the list's order, bit-equal run to run.
-#include "e3_common.h"
+// The 16-byte groups and their sum are e3_rows.h, shared with e3_cell_images.hip.
+#include "e3_rows.h"
 
 #include <algorithm>
-#include <initializer_list>
 
 namespace e3 {
-
-template <typename T> struct Vec16;
-template <> struct Vec16<float> { using type = float4; };
-template <> struct Vec16<double> { using type = double2; };
-
-__device__ __forceinline__ void vclear(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void vclear(double2& a) { a = make_double2(0.0, 0.0); }
-__device__ __forceinline__ void vadd(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
-__device__ __forceinline__ void vadd(double2& a, const double2 b) { a.x += b.x; a.y += b.y; }
 
 // out[i] = slot[i] < 0 ? h[i] : recv[slot[i]]  (a slot >= n_recv reads nothing: the row is written as zero).
 // DV = the 16-byte groups of a row (0: every column goes through the element loop)
@@ -90,15 +81,6 @@ __global__ __launch_bounds__(256) void halo_reduce_kernel(const T* __restrict__ 
 }
 
 static inline int row_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, 256 * 16)); }
-
-// 16-byte groups of a row of D elements of `es` bytes, 0 unless every pointer and every pitch keeps them aligned
-static inline int groups16(int D, int64_t es, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds) {
-  for (const void* p : ptrs)
-    if ((uintptr_t)p & 15) return 0;
-  for (int64_t ld : lds)
-    if ((ld * es) & 15) return 0;
-  return (int)(D / (16 / es));
-}
 
 template <typename T>
 static int refresh_launch(const void* h, int64_t ld_h, const void* recv, int64_t ld_r, int64_t n_recv, const int32_t* slot,

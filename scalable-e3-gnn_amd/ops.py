@@ -6,7 +6,9 @@ own backward a whole SEGNN layer has parameter gradients and forces.  With grad 
 the linear stages by composition (gather <-> its backward, segment sum <-> its backward), the gate, the edge geometry and the
 envelope on ``e3_gate_blocks_backward2``, ``e3_edge_geometry_jvp`` / ``e3_edge_geometry_hvp`` (and their ``_strained`` forms)
 and ``e3_cutoff_envelope_backward2`` -- so a loss on the forces has parameter gradients and the energy has Hessian-vector
-products in the positions and in a strain; those Functions are once differentiable.  ROCm tensors only; no CPU path."""
+products in the positions and in a strain; those Functions are once differentiable.  ROCm tensors only; no CPU path.
+The exception is the pair ``image_rows_expand`` / ``image_rows_reduce`` (image rows of a small periodic cell, cell_images.py): two
+adjoint linear maps, each the other's backward, differentiable to any order, with a torch restatement for CPU tensors."""
 from __future__ import annotations
 
 import torch
@@ -805,3 +807,47 @@ def add_pow2_scale(h: torch.Tensor, u: torch.Tensor, target_log2: int = 10):
         _lib.check(_lib.load().e3_add_pow2_scale(h.data_ptr(), u.data_ptr(), out.data_ptr(), h.numel(), target_log2,
                                                  sc.data_ptr(), _stream(h)), "e3_add_pow2_scale")
     return out, sc
+
+
+class _ImageRowsExpandFn(torch.autograd.Function):
+    """rows -> rows[source] (+ a constant translation): linear in the rows, its backward is the row reduce."""
+
+    @staticmethod
+    def forward(ctx, x, rmap, translate):
+        from .cell_images import image_rows_expand_raw
+        ctx.rmap = rmap
+        return image_rows_expand_raw(x, rmap, translate)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _ImageRowsReduceFn.apply(g, ctx.rmap), None, None
+
+
+class _ImageRowsReduceFn(torch.autograd.Function):
+    """the transpose of the expand: linear, its backward is the expand (without the translation, a constant)."""
+
+    @staticmethod
+    def forward(ctx, g, rmap):
+        from .cell_images import image_rows_reduce_raw
+        ctx.rmap = rmap
+        return image_rows_reduce_raw(g, rmap)
+
+    @staticmethod
+    def backward(ctx, c):
+        return _ImageRowsExpandFn.apply(c, ctx.rmap, False), None
+
+
+def image_rows_expand(x: torch.Tensor, rmap, translate: bool = False) -> torch.Tensor:
+    """x [M, D] -> out[i] = x[rmap.source[i]]: every image row a copy of its owner's row, owned rows unchanged
+    (``e3_image_rows_expand``; fp32, bf16 or fp64 on a ROCm device, a torch restatement on the CPU).  ``rmap``: a
+    ``cell_images.ImageRowMap``.  ``translate=True`` (x [M,3] fp32 positions) adds the lattice shift ``rmap.shift[i] @ cell``.
+    Differentiable to any order: the backward is ``image_rows_reduce`` and that one's backward is this op, both applied as
+    Functions."""
+    return _ImageRowsExpandFn.apply(x, rmap, translate)
+
+
+def image_rows_reduce(g: torch.Tensor, rmap) -> torch.Tensor:
+    """g [M, D] -> out[i] = g[i] + the rows of the images of owned row i, zero on image rows: the transpose of
+    ``image_rows_expand`` (``e3_image_rows_reduce``: fp32 / fp64, summed in ascending row order without atomics, so bit-equal
+    from run to run; a torch restatement on the CPU).  Differentiable to any order."""
+    return _ImageRowsReduceFn.apply(g, rmap)

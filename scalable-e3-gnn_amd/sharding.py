@@ -350,6 +350,44 @@ class SplitGraph:
     dropped: int                  # edges into ghost rows that were removed
 
 
+def split_graph(is_ghost, g) -> SplitGraph:
+    """Drop the edges of ``g`` into the rows marked in ``is_ghost`` [N] bool (ghost or image rows) and split the rest by
+    the ownership of their src (``Halo.split_graph``, ``cell_images.CellImages.split_graph``)."""
+    from .radius_graph import RadiusGraph
+    src, dst = g.src, g.dst
+    N, E = g.rowptr.numel() - 1, int(src.numel())
+    if src.is_cuda:
+        # one classification + compaction on the device (csrc/e3_shard.hip); ONE host read for the three counts
+        from . import _lib
+        lib = _lib.load()
+        dev = src.device
+        ghost8 = is_ghost.to(torch.uint8)
+        rowptr2 = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        outs = [torch.empty(max(E, 1), dtype=torch.int32, device=dev) for _ in range(6)]
+        counts = torch.empty(4, dtype=torch.int32, device=dev)
+        work = torch.empty(int(lib.e3_split_edges_workspace_bytes(N)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.e3_split_edges(g.rowptr.data_ptr(), src.data_ptr(), ghost8.data_ptr(), N, E,
+                                          rowptr2.data_ptr(), *[o.data_ptr() for o in outs], counts.data_ptr(),
+                                          work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "e3_split_edges")
+        ek, ei, eb = (int(v) for v in counts[:3].tolist())
+        g2 = RadiusGraph(g.perm, g.pos4, rowptr2, outs[0][:ek], ek, g.grid)
+        object.__setattr__(g2, "_dst", outs[1][:ek])
+        return SplitGraph(g2, (outs[2][:ei], outs[3][:ei]), (outs[4][:eb], outs[5][:eb]), E - ek)
+    keep = ~is_ghost[dst.long()]
+    src_k, dst_k = src[keep], dst[keep]
+    deg = (g.rowptr[1:] - g.rowptr[:-1]).clone()
+    deg[is_ghost] = 0
+    rowptr = torch.zeros_like(g.rowptr)
+    rowptr[1:] = torch.cumsum(deg, 0)
+    g2 = RadiusGraph(g.perm, g.pos4, rowptr, src_k.contiguous(), int(src_k.numel()), g.grid)
+    object.__setattr__(g2, "_dst", dst_k.contiguous())
+    ghost_src = is_ghost[src_k.long()]
+    interior = (src_k[~ghost_src].contiguous(), dst_k[~ghost_src].contiguous())
+    boundary = (src_k[ghost_src].contiguous(), dst_k[ghost_src].contiguous())
+    return SplitGraph(g2, interior, boundary, int(src.numel() - src_k.numel()))
+
+
 def halo_refresh_torch(h, recv, recv_idx):
     """Torch restatement of ``e3_halo_refresh`` (any device): the ghost rows ``recv_idx`` of a copy of ``h`` <- ``recv``."""
     return h.clone().index_copy_(0, recv_idx, recv)
@@ -730,39 +768,7 @@ class Halo:
     def split_graph(self, g) -> SplitGraph:
         """Drop the edges into ghost rows and split the rest by the ownership of their src (see the module docstring).
         ``g``: the RadiusGraph of the local cloud (after ``renumber(g.perm)``)."""
-        from .radius_graph import RadiusGraph
-        src, dst = g.src, g.dst
-        N, E = g.rowptr.numel() - 1, int(src.numel())
-        if src.is_cuda:
-            # one classification + compaction on the device (csrc/e3_shard.hip); ONE host read for the three counts
-            from . import _lib
-            lib = _lib.load()
-            dev = src.device
-            ghost8 = self.is_ghost.to(torch.uint8)
-            rowptr2 = torch.empty(N + 1, dtype=torch.int32, device=dev)
-            outs = [torch.empty(max(E, 1), dtype=torch.int32, device=dev) for _ in range(6)]
-            counts = torch.empty(4, dtype=torch.int32, device=dev)
-            work = torch.empty(int(lib.e3_split_edges_workspace_bytes(N)), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.e3_split_edges(g.rowptr.data_ptr(), src.data_ptr(), ghost8.data_ptr(), N, E,
-                                              rowptr2.data_ptr(), *[o.data_ptr() for o in outs], counts.data_ptr(),
-                                              work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "e3_split_edges")
-            ek, ei, eb = (int(v) for v in counts[:3].tolist())
-            g2 = RadiusGraph(g.perm, g.pos4, rowptr2, outs[0][:ek], ek, g.grid)
-            object.__setattr__(g2, "_dst", outs[1][:ek])
-            return SplitGraph(g2, (outs[2][:ei], outs[3][:ei]), (outs[4][:eb], outs[5][:eb]), E - ek)
-        keep = ~self.is_ghost[dst.long()]
-        src_k, dst_k = src[keep], dst[keep]
-        deg = (g.rowptr[1:] - g.rowptr[:-1]).clone()
-        deg[self.is_ghost] = 0
-        rowptr = torch.zeros_like(g.rowptr)
-        rowptr[1:] = torch.cumsum(deg, 0)
-        g2 = RadiusGraph(g.perm, g.pos4, rowptr, src_k.contiguous(), int(src_k.numel()), g.grid)
-        object.__setattr__(g2, "_dst", dst_k.contiguous())
-        ghost_src = self.is_ghost[src_k.long()]
-        interior = (src_k[~ghost_src].contiguous(), dst_k[~ghost_src].contiguous())
-        boundary = (src_k[ghost_src].contiguous(), dst_k[ghost_src].contiguous())
-        return SplitGraph(g2, interior, boundary, int(src.numel() - src_k.numel()))
+        return split_graph(self.is_ghost, g)
 
     # -- once per layer -------------------------------------------------------------------------------
     def start(self, h: torch.Tensor):
