@@ -999,6 +999,25 @@ int e3_halo_reduce(const void* g, int64_t ld_g, const void* back, int64_t ld_bac
  *   N (2 m_0 + 1)(2 m_1 + 1)(2 m_2 + 1) >= 2^31 - 1 (so N + G fits int32), N + G >= 2^31 - 1, a short workspace or a NULL
  *   pointer that is needed.  N = 0 is valid: offsets[0] = 0, nothing else is touched.
  *
+ * Batches (cell_images.BatchedCellImages): B structures, each with its own cell and origin, one r; structure [N] int32 names
+ *   every particle's structure, in any order.  The rule, the rounding and the output order are those above with the cell
+ *   looked up per particle -- the particles of one structure get, bit for bit, what the single entries give that structure
+ *   alone -- so the images come out by (owner ascending in the caller's order, shift lexicographic), whatever the structures.
+ *   e3_cell_images_plan_batch (host only): cells [B,9], origins [B,3] -> shells [B,3] and rho [B] exactly as
+ *             e3_cell_images_plan per structure (shells as they are), and table: B records of
+ *             e3_cell_images_record_bytes() = E3_CELL_IMAGE_RECORD_BYTES bytes each, a multiple of 16 (cell, inverse, origin,
+ *             heights, shells, rho as the kernels hold them; opaque to the caller), in 16-byte aligned HOST memory.  The caller
+ *             copies the table to the device, 16-byte aligned, and passes both: the device copy is what the kernels read (one
+ *             thread per particle, the record in 16-byte loads), the host copy is what the entries check.
+ *   e3_cell_images_count_batch / _fill_batch: as the single pair.  counts [B] int64 (host): the particles of every structure;
+ *             a structure without particles is valid.  A particle whose id lies outside [0, B) gets no image and keeps its
+ *             position unwrapped (the host layer refuses such input).
+ *   E3_ERR_INVALID_ARG before any launch for B outside [0, 2^31 - 1), a structure the single plan refuses, more than
+ *   E3_CELL_IMAGE_MAX_SHELLS shells in any structure, a negative count, counts that do not sum to N,
+ *   sum_b counts[b] (2 m_0 + 1)(2 m_1 + 1)(2 m_2 + 1) >= 2^31 - 1 with each structure's own shells, N + G >= 2^31 - 1, a table
+ *   that is not 16-byte aligned, a short workspace (e3_cell_images_workspace_bytes(N), as above) or a NULL pointer that is
+ *   needed.  N = 0 is valid as above.
+ *
  * Rows [M, D] with a leading dimension (elements), in any numbering; source [M] int32: source[i] = i on an owned row, the
  * owner's row on an image row (an image row is never a source).
  *   e3_image_rows_expand : out[i] = in[source[i]]; dtype E3_F32, E3_BF16 or E3_F64 (a byte copy).  A source outside [0, M)
@@ -1023,6 +1042,16 @@ int e3_cell_images_count(const float* pos, int64_t N, const float cell[9], const
                          int32_t* offsets, void* workspace, int64_t workspace_bytes, void* stream);
 int e3_cell_images_fill(const float* pos_wrapped, int64_t N, const float cell[9], const float origin[3], float r,
                         const int32_t* offsets, int64_t G, int32_t* owner, int32_t* shift, float* image_pos, void* stream);
+#define E3_CELL_IMAGE_RECORD_BYTES 112
+int64_t e3_cell_images_record_bytes(void);
+int e3_cell_images_plan_batch(const float* cells, const float* origins, int64_t B, float r, int32_t* shells, float* rho,
+                              void* table);  /* host only */
+int e3_cell_images_count_batch(const float* pos, const int32_t* structure, int64_t N, const void* table,
+                               const void* table_host, const int64_t* counts, int64_t B, float* pos_wrapped, int32_t* offsets,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int e3_cell_images_fill_batch(const float* pos_wrapped, const int32_t* structure, int64_t N, const void* table,
+                              const void* table_host, const int64_t* counts, int64_t B, const int32_t* offsets, int64_t G,
+                              int32_t* owner, int32_t* shift, float* image_pos, void* stream);
 int e3_image_rows_expand(const void* in, int64_t ld_in, const int32_t* source, const int32_t* shift, const float cell[9],
                          int64_t M, int D, int dtype, void* out, int64_t ld_out, void* stream);
 int e3_image_rows_reduce(const void* g, int64_t ld_g, const int32_t* source, const int32_t* ptr, const int32_t* rows,

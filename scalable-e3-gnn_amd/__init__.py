@@ -17,15 +17,18 @@ Public surface:
     what a migration moves (``sharding.Halo.migrate``, ``sharding.migrate_rows``).
   * ``CellImages`` / ``cell_image_graph`` — periodic cells below twice the cutoff: the cloud extended by explicit lattice image
     rows under an open graph (``PeriodicEnergyModel(...)(..., cell=, images=True | "auto")`` uses it).
+  * ``BatchedPeriodicEnergyModel`` / ``BatchedCellImages`` / ``batched_cell_image_graph`` — a batch of periodic structures, each
+    with its own cell, in one call: per-structure energies, forces, virials and stresses over one selection of image rows.
 Everything computes through ``lib/libe3gnn_hip.so`` (C ABI: ``include/e3gnn.h``); there is no CPU path.
 """
 from .irreps import Instruction, Irrep, Irreps, as_blocks  # noqa: F401
 from .l1_tensor_prod import L1TensorProduct  # noqa: F401
 from .neighbor_list import NeighborList  # noqa: F401
-from .batched import ShardedEnergyModel  # noqa: F401
-from .cell_images import CellImages, cell_image_graph  # noqa: F401
+from .batched import BatchedPeriodicEnergyModel, ShardedEnergyModel  # noqa: F401
+from .cell_images import BatchedCellImages, CellImages, batched_cell_image_graph, cell_image_graph  # noqa: F401
 from .sharded_list import OwnershipChanged, ShardedNeighborList  # noqa: F401
 from .sharding import pack_rows, unpack_rows  # noqa: F401
 
 __all__ = ["L1TensorProduct", "Irreps", "Irrep", "Instruction", "as_blocks", "NeighborList", "ShardedEnergyModel",
-           "ShardedNeighborList", "OwnershipChanged", "pack_rows", "unpack_rows", "CellImages", "cell_image_graph"]
+           "ShardedNeighborList", "OwnershipChanged", "pack_rows", "unpack_rows", "CellImages", "cell_image_graph",
+           "BatchedCellImages", "batched_cell_image_graph", "BatchedPeriodicEnergyModel"]

@@ -260,6 +260,14 @@ SIGNATURES = {
                                      c_void_p]),
     "e3_cell_images_fill": (c_int, [c_void_p, c_int64, Float9, Float3, ctypes.c_float, c_void_p, c_int64, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
+    # ... and a batch of cells: (cells [B,9], origins [B,3], B, r, shells [B,3], rho [B], table) on the host, then
+    # (pos, structure, N, table, table_host, counts [B] int64, B, ...) as the single pair
+    "e3_cell_images_record_bytes": (c_int64, []),
+    "e3_cell_images_plan_batch": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "e3_cell_images_count_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                           c_void_p, c_void_p, c_int64, c_void_p]),
+    "e3_cell_images_fill_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "e3_image_rows_expand": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, POINTER(ctypes.c_float), c_int64, c_int, c_int,
                                      c_void_p, c_int64, c_void_p]),
     "e3_image_rows_reduce": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p,

@@ -16,7 +16,8 @@ force-loss step does not launch it; `hessian_vector_product` / `hessian` of the 
 both kernels (`e3_edge_geometry_jvp_strained` / `_hvp_strained`) give the second derivative in the joint coordinates
 (pos, strain): `PeriodicEnergyModel.strain_hessian_vector_product` / `elastic_tensor` (Born term and force-strain coupling).
 Virials and stress are the derivative w.r.t. a zero strain per structure, reduced inside the same geometry backward
-(`e3_edge_geometry_backward_strained`); `PeriodicEnergyModel` is the periodic-box counterpart of `BatchedEnergyModel`.
+(`e3_edge_geometry_backward_strained`); `PeriodicEnergyModel` is the periodic-box counterpart of `BatchedEnergyModel`, and
+`BatchedPeriodicEnergyModel` their combination: a batch of periodic structures, each with its own cell, over image rows.
 """
 from __future__ import annotations
 
@@ -589,6 +590,102 @@ class PeriodicEnergyModel(nn.Module):
         ``images``: as in ``forward``; the limit counts the N particles, not their image rows."""
         return _dense_hessian(lambda vs: self.hessian_vector_product(x, pos, r, lo, hi, periodic, cell, origin, vs, skin=skin,
                                                                      neighbors=neighbors, images=images), pos)
+
+
+class BatchedPeriodicEnergyModel(nn.Module):
+    """SEGNN with a scalar node readout summed per structure over a BATCH of periodic structures, each with its own general
+    cell: energies [B], and on request forces, per-structure virials and stresses, in one call (fitting a potential to a
+    crystal dataset).  Every structure takes the image path of ``PeriodicEnergyModel(..., images=True)`` whatever its size:
+    the cloud is extended by every structure's lattice images in one selection (``cell_images.BatchedCellImages``) and the
+    open batched graph runs over it, so a cell may be smaller than the cutoff, up to 7 image shells per axis.  ``.net`` is the
+    same ``SEGNN(..., "1x0e", ...)``: a state dict of the other energy models loads as it is.
+
+    Not covered: ``neighbors=`` (a Verlet list over image rows), ``max_neighbors=``, ``hessian()``,
+    ``strain_hessian_vector_product`` and ``elastic_tensor`` on a batch, a minimum-image fast path for the structures of a batch
+    that are large enough for one, the sharded path, and bf16 storage with gradients (bf16 runs the fused inference call
+    only)."""
+
+    def __init__(self, in_irreps="1x0e+1x1o", hidden: int = 32, num_layers: int = 4, lmax: int = 2,
+                 envelope: int | None = None):
+        super().__init__()
+        self.net = SEGNN(in_irreps, hidden, "1x0e", num_layers, lmax=lmax, envelope=envelope)
+
+    def _image_cloud(self, x, pos, batch, r, cells, origins, skin):
+        """-> (BatchedCellImages, SplitGraph, x, pos and structure of the extended cloud in graph order, the cutoff= of the
+        net's forward)"""
+        from .cell_images import batched_cell_image_graph
+        cut = _cutoff_kw(self.net, r)
+        return (*batched_cell_image_graph(pos, x, batch, _skin_radius(self.net, r, skin), cells, origins), cut)
+
+    def forward(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, cells, origins=None,
+                forces: bool = False, virial: bool = False, stress: bool = False, skin: float = 0.0,
+                create_graph: bool = False):
+        """x [N, in_dim], pos [N,3] (caller order, may be unwrapped), batch [N] the structure of every atom (any integer
+        dtype, any order), cells [B,3,3] (rows = lattice vectors; a nested sequence or a CPU tensor) with origins [B,3]
+        (None: zeros).  B comes from ``cells``: a structure without atoms is legal and has energy 0 and zero virial and
+        stress.  -> energies [B], then whichever of forces [N,3] (= -dE/dpos, caller order), virials [B,3,3] (= -dE/deps_b
+        at a zero strain per structure, not symmetrised) and stresses [B,3,3] (= (1/V_b) dE/deps_b, V_b = |det cell_b|) were
+        requested, in that order; the energies alone when none was.  Energies only under ``no_grad`` run the fused inference
+        kernels.
+
+        ``skin``, ``create_graph``: as ``PeriodicEnergyModel.forward`` on its image path -- ``create_graph=True`` needs
+        ``forces=True`` and a parameter that requires grad, and raises ``NotImplementedError`` with ``virial=True`` /
+        ``stress=True`` and for bf16 storage.
+
+        ``ValueError`` before any launch of the selection for a ``batch`` id outside [0, B), a structure above 7 image shells
+        (the message names it), non-finite input; ``RuntimeError`` for CPU tensors."""
+        if create_graph:
+            _check_create_graph(self.net, x, forces, virial or stress)
+        if pos.shape[0] == 0:
+            return self._empty(x, pos, r, cells, origins, skin, forces, virial, stress)
+        im, split, x_g, pos_g, structure_g, cut = self._image_cloud(x, pos, batch, r, cells, origins, skin)
+        B = im.n_structures
+        seg = batch.to(pos.device).long()
+        if not (forces or virial or stress):
+            e_node = self.net(x_g, split.graph, halo=im, split=split, **cut)[im.owned_new, 0]
+            return torch.zeros(B, dtype=e_node.dtype, device=e_node.device).index_add_(0, seg, e_node)
+        strained = virial or stress
+        energy, gpos, geps = _energy_and_gradients(self.net, x_g, split.graph, pos_g, seg, B, forces, B if strained else 0,
+                                                   structure_g if strained else None, cut, halo=im, split=split,
+                                                   create_graph=create_graph)
+        out = [energy]
+        if forces:
+            out.append(-im.reduce(gpos))
+        if virial:
+            out.append(-geps)
+        if stress:
+            V = torch.tensor(im.volumes, dtype=torch.float64, device=geps.device).view(B, 1, 1)
+            out.append((geps.double() / V).float())
+        return tuple(out)
+
+    def _empty(self, x, pos, r, cells, origins, skin, forces, virial, stress):
+        """``forward`` of a batch without atoms: the cells are checked as always, every output is zero, nothing is launched"""
+        from .cell_images import BatchedCellImages
+        if not pos.is_cuda:
+            raise RuntimeError("BatchedCellImages.setup runs on ROCm tensors only; there is no CPU path")
+        im = BatchedCellImages(cells, origins)
+        im.plan(_skin_radius(self.net, r, skin))
+        B = im.n_structures
+        energy = torch.zeros(B, dtype=x.dtype, device=pos.device)
+        if not (forces or virial or stress):
+            return energy
+        zeros = torch.zeros((B, 3, 3), dtype=torch.float32, device=pos.device)
+        return (energy,) + ((torch.zeros_like(pos),) if forces else ()) + (zeros,) * (int(virial) + int(stress))
+
+    def hessian_vector_product(self, x: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, r: float, cells, origins=None,
+                               v: torch.Tensor | None = None, skin: float = 0.0) -> torch.Tensor:
+        """H v, H = d2(sum of the energies)/dpos2 on the edge set of the current graph, block diagonal over the structures;
+        ``v`` [N,3] or [K,N,3] in the caller's order -> a detached tensor of the shape of ``v``.  As
+        ``PeriodicEnergyModel.hessian_vector_product`` on its image path: ``v`` is copied to the image rows (a direction has
+        no lattice shift) and the product is reduced back to the N atoms, H = E^T H_ext E.  fp32: bf16 storage raises
+        ``NotImplementedError``."""
+        if pos.shape[0] == 0 and v is not None and v.dim() in (2, 3) and tuple(v.shape[-2:]) == (0, 3):
+            return torch.zeros_like(v)                            # no atoms: nothing to reshape and nothing to launch
+        vs = _check_vectors(v, pos)
+        im, split, x_g, pos_g, _, cut = self._image_cloud(x, pos, batch, r, cells, origins, skin)
+        hv = _hessian_vector_products(self.net, x_g, split.graph, pos_g, _image_vectors(im, vs.float()), cut, halo=im,
+                                      split=split)
+        return _reduce_vectors(im, hv).reshape(v.shape)
 
 
 class ShardedEnergyModel(nn.Module):

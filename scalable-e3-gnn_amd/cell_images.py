@@ -11,8 +11,9 @@ every layer.  Every open-graph kernel then serves the small cell as it is; the c
 ``CellImages`` offers the part of the ``sharding.Halo`` interface that ``SEGNN`` and the energy models use (``refresh``,
 ``exchange``, ``start`` / ``finish``, ``ghost_rows``, ``owned_new``, ``overflow``, ``anchor``, ``split_graph``), without a
 process group: a refresh is one row copy on the device (``e3_image_rows_expand``), its transpose one ordered row sum
-(``e3_image_rows_reduce``).  Not covered: a Verlet list over image rows, batches of cells, the ``lo`` / ``hi`` box form, a cell
-with an open direction, the sharded path, more than ``MAX_SHELLS`` image shells on an axis."""
+(``e3_image_rows_reduce``).  ``BatchedCellImages`` is the same for a batch of structures, each with its own cell, in one
+selection.  Not covered: a Verlet list over image rows, the ``lo`` / ``hi`` box form, a cell with an open direction, the
+sharded path, more than ``MAX_SHELLS`` image shells on an axis."""
 from __future__ import annotations
 
 import ctypes
@@ -135,60 +136,27 @@ def image_shells(cell9, origin3, r):
     return tuple(m), rho.value
 
 
-class CellImages:
-    """The image rows of one periodic cell (``cell`` 3x3, rows = lattice vectors, with ``origin``; held as ``cell_params``
-    derives them).  ``setup`` selects the images, ``renumber`` follows the graph builder's order, ``split_graph`` drops the
-    edges into image rows; after that it serves ``SEGNN(..., halo=images, split=split)`` as a ``sharding.Halo`` does."""
+class ImageRows:
+    """What ``CellImages`` and ``BatchedCellImages`` share: the index state of an extended cloud ``[owned | images]`` after its
+    ``setup`` and the part of the ``sharding.Halo`` interface that ``SEGNN`` and the energy models use.  Nothing here knows a
+    cell: a subclass' ``setup`` selects the images and calls ``_selected``."""
 
     anchor = None    # ``Halo.anchor`` keeps a refresh in every rank's backward; one process has no peer to keep waiting
+    _map_cell = None  # the cell of ``ImageRowMap`` (translate=True), where one cell serves every row
 
-    def __init__(self, cell, origin=None):
-        self.cell, self.origin, self.heights, self.volume = cell_params(cell, origin)
+    def __init__(self):
         self.n_owned = self.n_ghost = 0
         self.overflow = None
         self.map = None
 
-    def needs_images(self, r: float) -> bool:
-        """Whether ``radius_graph(cell=)`` refuses ``r``: ``2 r >=`` a perpendicular height in fp32."""
-        r32 = ctypes.c_float(r).value
-        return not all(ctypes.c_float(2.0 * r32).value < h for h in self.heights)
-
-    def setup(self, pos: torch.Tensor, feats: torch.Tensor, r: float):
-        """pos [N,3] fp32 (may be unwrapped), feats [N, C] -> (pos_ext [N + G, 3], feats_ext [N + G, C]): the wrapped
-        particles in caller order, then their G images ordered by (owner, shift); ``owner`` [G] / ``shift`` [G,3] int32 are
-        kept.  Count pass, one scan, ONE host read (G), fill pass (``e3_cell_images_count`` / ``_fill``)."""
-        self.shells, self.rho = image_shells(self.cell, self.origin, r)
-        if not pos.is_cuda:
-            raise RuntimeError("CellImages.setup runs on ROCm tensors only; there is no CPU path")
-        if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
-            raise RuntimeError(f"pos must be [N,3] float32, got {tuple(pos.shape)} {pos.dtype}")
-        pos = pos.detach().contiguous()
-        N, dev = pos.shape[0], pos.device
-        lib = _lib.load()
-        c9, o3 = _lib.Float9(*self.cell), _lib.Float3(*self.origin)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            wbytes = lib.e3_cell_images_workspace_bytes(N)
-            if wbytes < 0:
-                raise RuntimeError("e3_cell_images_workspace_bytes: invalid arguments")
-            ws = torch.empty(max(int(wbytes), 16), dtype=torch.uint8, device=dev)
-            pos_w = torch.empty((N, 3), dtype=torch.float32, device=dev)
-            off = torch.empty(N + 1, dtype=torch.int32, device=dev)
-            _lib.call("e3_cell_images_count", pos.data_ptr(), N, c9, o3, float(r), pos_w.data_ptr(), off.data_ptr(),
-                      ws.data_ptr(), wbytes, stream)
-            G = int(off[-1].item())
-            owner = torch.empty(G, dtype=torch.int32, device=dev)
-            shift = torch.empty((G, 3), dtype=torch.int32, device=dev)
-            pos_ext = torch.empty((N + G, 3), dtype=torch.float32, device=dev)
-            pos_ext[:N] = pos_w
-            _lib.call("e3_cell_images_fill", pos_w.data_ptr(), N, c9, o3, float(r), off.data_ptr(), G, owner.data_ptr(),
-                      shift.data_ptr(), pos_ext[N:].data_ptr() if G else None, stream)
-        self.n_owned, self.n_ghost, self.owner, self.shift = N, G, owner, shift
+    def _selected(self, N, owner, shift):
+        """The state after a selection: ``owner`` [G] / ``shift`` [G,3] int32 of the images of N owned particles"""
+        dev = owner.device
+        self.n_owned, self.n_ghost, self.owner, self.shift = N, owner.numel(), owner, shift
         # the setup order [owned | images]: every ``renumber`` starts from it, so it can be repeated (as ``Halo.renumber``)
         self._source0 = torch.cat([torch.arange(N, device=dev), owner.long()])
         self._shift0 = torch.cat([torch.zeros((N, 3), dtype=torch.int32, device=dev), shift])
-        self.renumber(torch.arange(N + G, device=dev))
-        return pos_ext, image_rows_expand_raw(_pad_rows(feats, N + G), self.map)
+        self.renumber(torch.arange(N + owner.numel(), device=dev))
 
     def renumber(self, perm: torch.Tensor):
         """The graph builder renumbers the extended cloud (``perm[new] = old``, old = the order ``setup`` returned): the index
@@ -197,7 +165,7 @@ class CellImages:
         inv = torch.empty_like(p)
         inv[p] = torch.arange(p.numel(), device=p.device)
         n = self.n_owned
-        self.map = ImageRowMap.build(inv[self._source0[p]], self._shift0[p], self.cell)
+        self.map = ImageRowMap.build(inv[self._source0[p]], self._shift0[p], self._map_cell)
         self.owned_new = inv[:n]              # ids of the owned particles, in the caller's order
         self._img_idx = inv[n:]               # ids of the image rows, (owner, shift) order
         self.is_ghost = torch.zeros(p.numel(), dtype=torch.bool, device=p.device)
@@ -252,6 +220,166 @@ class CellImages:
         return ops.image_rows_reduce(t, self.map)[self.owned_new]
 
 
+class CellImages(ImageRows):
+    """The image rows of one periodic cell (``cell`` 3x3, rows = lattice vectors, with ``origin``; held as ``cell_params``
+    derives them).  ``setup`` selects the images, ``renumber`` follows the graph builder's order, ``split_graph`` drops the
+    edges into image rows; after that it serves ``SEGNN(..., halo=images, split=split)`` as a ``sharding.Halo`` does."""
+
+    def __init__(self, cell, origin=None):
+        super().__init__()
+        self.cell, self.origin, self.heights, self.volume = cell_params(cell, origin)
+        self._map_cell = self.cell
+
+    def needs_images(self, r: float) -> bool:
+        """Whether ``radius_graph(cell=)`` refuses ``r``: ``2 r >=`` a perpendicular height in fp32."""
+        r32 = ctypes.c_float(r).value
+        return not all(ctypes.c_float(2.0 * r32).value < h for h in self.heights)
+
+    def setup(self, pos: torch.Tensor, feats: torch.Tensor, r: float):
+        """pos [N,3] fp32 (may be unwrapped), feats [N, C] -> (pos_ext [N + G, 3], feats_ext [N + G, C]): the wrapped
+        particles in caller order, then their G images ordered by (owner, shift); ``owner`` [G] / ``shift`` [G,3] int32 are
+        kept.  Count pass, one scan, ONE host read (G), fill pass (``e3_cell_images_count`` / ``_fill``)."""
+        self.shells, self.rho = image_shells(self.cell, self.origin, r)
+        if not pos.is_cuda:
+            raise RuntimeError("CellImages.setup runs on ROCm tensors only; there is no CPU path")
+        if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
+            raise RuntimeError(f"pos must be [N,3] float32, got {tuple(pos.shape)} {pos.dtype}")
+        pos = pos.detach().contiguous()
+        N, dev = pos.shape[0], pos.device
+        lib = _lib.load()
+        c9, o3 = _lib.Float9(*self.cell), _lib.Float3(*self.origin)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            wbytes = lib.e3_cell_images_workspace_bytes(N)
+            if wbytes < 0:
+                raise RuntimeError("e3_cell_images_workspace_bytes: invalid arguments")
+            ws = torch.empty(max(int(wbytes), 16), dtype=torch.uint8, device=dev)
+            pos_w = torch.empty((N, 3), dtype=torch.float32, device=dev)
+            off = torch.empty(N + 1, dtype=torch.int32, device=dev)
+            _lib.call("e3_cell_images_count", pos.data_ptr(), N, c9, o3, float(r), pos_w.data_ptr(), off.data_ptr(),
+                      ws.data_ptr(), wbytes, stream)
+            G = int(off[-1].item())
+            owner = torch.empty(G, dtype=torch.int32, device=dev)
+            shift = torch.empty((G, 3), dtype=torch.int32, device=dev)
+            pos_ext = torch.empty((N + G, 3), dtype=torch.float32, device=dev)
+            pos_ext[:N] = pos_w
+            _lib.call("e3_cell_images_fill", pos_w.data_ptr(), N, c9, o3, float(r), off.data_ptr(), G, owner.data_ptr(),
+                      shift.data_ptr(), pos_ext[N:].data_ptr() if G else None, stream)
+        self._selected(N, owner, shift)
+        return pos_ext, image_rows_expand_raw(_pad_rows(feats, N + G), self.map)
+
+
+def _aligned_host(n_bytes):
+    """a zeroed host buffer whose address is a multiple of 16 -> (the ctypes array that owns it, the address)"""
+    raw = (ctypes.c_uint8 * (n_bytes + 16))()
+    addr = ctypes.addressof(raw)
+    return raw, addr + (-addr) % 16
+
+
+class BatchedCellImages(ImageRows):
+    """The image rows of a batch of periodic structures, each with its own cell: ``cells`` [B,3,3] (a nested sequence or a
+    CPU tensor; rows = lattice vectors) and ``origins`` [B,3] (None: zeros), every structure derived by ``cell_params``;
+    ``volumes`` holds the B volumes.  One selection serves the whole batch (``e3_cell_images_count_batch`` / ``_fill_batch``:
+    the cell is looked up per particle in a table of B records), and the rest is ``CellImages``' -- except that no single cell
+    translates every row, so ``extend(translate=True)`` is a ``ValueError``."""
+
+    def __init__(self, cells, origins=None):
+        super().__init__()
+        if isinstance(cells, torch.Tensor):
+            if cells.is_cuda:
+                raise ValueError("cells must be a nested sequence or a CPU tensor (they are host arguments of the kernels)")
+            cells = cells.detach().tolist()
+        if isinstance(origins, torch.Tensor):
+            origins = origins.detach().cpu().tolist()
+        cells = list(cells)
+        origins = [None] * len(cells) if origins is None else list(origins)
+        if len(origins) != len(cells):
+            raise ValueError(f"origins must hold one origin per cell: {len(cells)} cells, {len(origins)} origins")
+        params = [cell_params(c, o) for c, o in zip(cells, origins)]
+        self.n_structures = len(params)
+        self.cells = [p[0] for p in params]
+        self.origins = [p[1] for p in params]
+        self.heights = [p[2] for p in params]
+        self.volumes = [p[3] for p in params]
+
+    def plan(self, r: float):
+        """-> (shells [B] of 3-tuples, rho [B] floats) of ``e3_cell_images_plan_batch``, which are those of
+        ``e3_cell_images_plan`` per structure; the host table of the device records is kept for ``setup``.  ``ValueError``
+        for an r that is not finite and positive and for a structure above ``MAX_SHELLS`` shells on an axis."""
+        B, lib = self.n_structures, _lib.load()
+        rec = int(lib.e3_cell_images_record_bytes())
+        cells = (ctypes.c_float * (9 * max(B, 1)))(*[v for c in self.cells for v in c])
+        origins = (ctypes.c_float * (3 * max(B, 1)))(*[v for o in self.origins for v in o])
+        shells, rho = (ctypes.c_int32 * (3 * max(B, 1)))(), (ctypes.c_float * max(B, 1))()
+        self._table_owner, self._table_host = _aligned_host(rec * max(B, 1))
+        self._table_bytes = rec * B
+        st = lib.e3_cell_images_plan_batch(ctypes.addressof(cells), ctypes.addressof(origins), B, float(r),
+                                           ctypes.addressof(shells), ctypes.addressof(rho), self._table_host)
+        if st != _lib.E3_OK:
+            raise ValueError(f"cell images: need a finite r > 0 and finite cells and origins, got r = {r}")
+        self.shells = [tuple(shells[3 * b:3 * b + 3]) for b in range(B)]
+        self.rho = [rho[b] for b in range(B)]
+        for b, m in enumerate(self.shells):
+            if max(m) > MAX_SHELLS:
+                raise ValueError(f"cell images: structure {b}: r = {r} needs {m} image shells, more than {MAX_SHELLS} image "
+                                 "shells on an axis (the limit); the cell is too small for this cutoff -- build a supercell")
+        return self.shells, self.rho
+
+    def setup(self, pos: torch.Tensor, feats: torch.Tensor, batch: torch.Tensor, r: float):
+        """pos [N,3] fp32 (may be unwrapped), feats [N, C], batch [N] (any integer dtype, any order; ids in [0, B), a structure
+        may have no atoms) -> (pos_ext [N + G, 3], feats_ext [N + G, C], batch_ext [N + G] int64): every particle wrapped
+        into its own cell, in caller order, then the G images ordered by (owner, shift).  One read of the per-structure
+        counts (which is also where an id outside [0, B) and a non-finite position are refused, before any launch of the
+        selection), count pass, one scan, ONE read of G, fill pass."""
+        B = self.n_structures
+        self.plan(r)
+        if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 3:
+            raise RuntimeError(f"pos must be [N,3] float32, got {tuple(pos.shape)} {pos.dtype}")
+        if batch.dim() != 1 or batch.shape[0] != pos.shape[0] or batch.dtype.is_floating_point or batch.dtype == torch.bool:
+            raise ValueError(f"batch must be [N] of an integer dtype with N = {pos.shape[0]}, got {tuple(batch.shape)} "
+                             f"{batch.dtype}")
+        pos = pos.detach().contiguous()
+        N, dev = pos.shape[0], pos.device
+        ids = batch.to(dev).long()
+        outside = (ids < 0) | (ids >= B)
+        tally = torch.cat([torch.bincount(torch.where(outside, B, ids), minlength=B + 1),
+                           (~torch.isfinite(pos)).sum().view(1)]).tolist()
+        if tally[B]:
+            raise ValueError(f"batch holds {tally[B]} structure ids outside [0, {B}): cells= describes {B} structures")
+        if tally[B + 1]:
+            raise ValueError("pos holds non-finite coordinates")
+        if not pos.is_cuda:
+            raise RuntimeError("BatchedCellImages.setup runs on ROCm tensors only; there is no CPU path")
+        structure = ids.to(torch.int32)
+        counts = (ctypes.c_int64 * max(B, 1))(*tally[:B])
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            wbytes = lib.e3_cell_images_workspace_bytes(N)
+            if wbytes < 0:
+                raise RuntimeError("e3_cell_images_workspace_bytes: invalid arguments")
+            ws = torch.empty(max(int(wbytes), 16), dtype=torch.uint8, device=dev)
+            host = torch.frombuffer(self._table_owner, dtype=torch.uint8, count=max(self._table_bytes, 16),
+                                    offset=self._table_host - ctypes.addressof(self._table_owner))
+            table = host.to(dev)                                  # a fresh allocation: 256-byte aligned
+            pos_w = torch.empty((N, 3), dtype=torch.float32, device=dev)
+            off = torch.empty(N + 1, dtype=torch.int32, device=dev)
+            _lib.call("e3_cell_images_count_batch", pos.data_ptr(), structure.data_ptr(), N, table.data_ptr(),
+                      self._table_host, ctypes.addressof(counts), B, pos_w.data_ptr(), off.data_ptr(), ws.data_ptr(), wbytes,
+                      stream)
+            G = int(off[-1].item())
+            owner = torch.empty(G, dtype=torch.int32, device=dev)
+            shift = torch.empty((G, 3), dtype=torch.int32, device=dev)
+            pos_ext = torch.empty((N + G, 3), dtype=torch.float32, device=dev)
+            pos_ext[:N] = pos_w
+            _lib.call("e3_cell_images_fill_batch", pos_w.data_ptr(), structure.data_ptr(), N, table.data_ptr(),
+                      self._table_host, ctypes.addressof(counts), B, off.data_ptr(), G, owner.data_ptr(), shift.data_ptr(),
+                      pos_ext[N:].data_ptr() if G else None, stream)
+        self._selected(N, owner, shift)
+        self.counts = tally[:B]
+        return pos_ext, image_rows_expand_raw(_pad_rows(feats, N + G), self.map), torch.cat([ids, ids[owner.long()]])
+
+
 def _pad_rows(t, M):
     """[N, C] -> [M, C], zero rows past N (the expand overwrites them)"""
     out = torch.zeros((M,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
@@ -271,3 +399,20 @@ def cell_image_graph(pos: torch.Tensor, x: torch.Tensor, r: float, cell, origin=
     split = images.split_graph(g)
     perm = g.perm.long()
     return images, split, x_ext[perm], pos_ext[perm]
+
+
+def batched_cell_image_graph(pos: torch.Tensor, x: torch.Tensor, batch: torch.Tensor, r: float, cells, origins=None):
+    """The extended cloud of a batch of periodic structures (``cells`` [B,3,3], ``batch`` [N] the structure of every particle)
+    and its open graph -> ``(images, split, x_g, pos_g, structure_g)``: a ``BatchedCellImages``, the ``SplitGraph`` without the
+    edges into image rows, features / positions of the extended cloud in the graph's order and ``structure_g`` [M] int64, the
+    structure of every extended row in that order.  The graph is ``batched.batched_radius_graph`` over the extended cloud:
+    intra-structure edges only, found on a lattice copy and returned with the extended positions themselves, so the edge
+    vectors see no offset.  Use as ``cell_image_graph``'s result."""
+    from .batched import batched_radius_graph
+    images = BatchedCellImages(cells, origins)
+    pos_ext, x_ext, batch_ext = images.setup(pos, x, batch, r)
+    g, structure_g = batched_radius_graph(pos_ext, batch_ext, r)
+    images.renumber(g.perm)
+    split = images.split_graph(g)
+    perm = g.perm.long()
+    return images, split, x_ext[perm], pos_ext[perm], structure_g

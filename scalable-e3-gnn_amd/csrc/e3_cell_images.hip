@@ -4,8 +4,9 @@
 //               per-axis sets (a 15-bit mask each, shifts -7 .. 7); the count is the product of the three popcounts minus the
 //               zero shift, ONE exclusive scan (e3_scan.hip) over the N + 1 counts gives every particle its output offset
 //               and the total, and the fill pass recomputes the masks and walks them in lexicographic order -- the output
-//               is ordered by (owner, shift) by construction, no atomics.
-//   expand    : out[i] = in[source[i]], one wave per row, 16-byte column groups where every pointer and pitch allows them
+//               is ordered by (owner, shift) by construction, no atomics.  The batched form (many cells per call) is the same
+//               pair with the cell read per particle from a table of records; the single-cell kernels are untouched.
+//   expand   : out[i] = in[source[i]], one wave per row, 16-byte column groups where every pointer and pitch allows them
 //               (the layout of e3_halo_grad.hip); a row copy moves bytes, so one kernel per element SIZE serves fp32, bf16
 //               and fp64.  The translated form (positions, D = 3, fp32) is one thread per row.
 //   reduce    : the transpose, a row sum over a CSR in the list's order by one wave per row: bit-equal from run to run.
@@ -86,6 +87,85 @@ __global__ __launch_bounds__(kImgThreads) void images_fill_kernel(const float* _
   }
 }
 
+// ---- batches of cells: the same selection with the cell looked up per particle -----------------------------------------
+// One record per structure in a device table the caller uploads (e3_cell_images_plan_batch fills the host copy): the ImgDev of
+// the single-cell kernels, 112 bytes = seven 16-byte groups.  Still one thread per particle: the work of a particle is its own
+// wrap and three axis masks, nothing is shared between the particles of a structure but the record, and neighbouring
+// particles usually share a structure, so a wave's seven loads hit the same one or two lines.
+struct alignas(16) ImgRec {
+  ImgDev d;
+};
+static_assert(sizeof(ImgDev) == 112 && sizeof(ImgRec) == E3_CELL_IMAGE_RECORD_BYTES && sizeof(ImgRec) % 16 == 0,
+              "the table record is the single-cell kernel argument, in whole 16-byte groups");
+
+// the record of structure s (s inside [0, B): the caller checks), seven 16-byte loads; false for a record the masks cannot
+// hold (more than kImgBias shells: the host entries refuse it, a table changed behind them selects nothing)
+__device__ __forceinline__ bool load_record(const ImgRec* __restrict__ table, const int s, ImgDev& d) {
+  constexpr int kGroups = sizeof(ImgRec) / 16;
+  uint4 q[kGroups];
+  const uint4* p = reinterpret_cast<const uint4*>(table + s);
+#pragma unroll
+  for (int k = 0; k < kGroups; ++k) q[k] = p[k];
+  __builtin_memcpy(&d, q, sizeof(ImgDev));
+  return d.m[0] >= 1 && d.m[1] >= 1 && d.m[2] >= 1 && d.m[0] <= kImgBias && d.m[1] <= kImgBias && d.m[2] <= kImgBias;
+}
+
+// a structure id outside [0, B): count 0, the position kept as it is
+__global__ __launch_bounds__(kImgThreads) void images_count_batch_kernel(const float* __restrict__ pos,
+                                                                         const int32_t* __restrict__ structure, int64_t n,
+                                                                         const ImgRec* __restrict__ table, int B,
+                                                                         float* __restrict__ pos_w, int32_t* __restrict__ cnt) {
+  const int64_t i = blockIdx.x * (int64_t)kImgThreads + threadIdx.x;
+  if (i >= n) return;
+  float3 w = make_float3(pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2]);
+  const int s = structure[i];
+  ImgDev d;
+  int c = 0;
+  if (s >= 0 && s < B && load_record(table, s, d)) {
+    w = wrap_cell(d.rc, w);
+    uint32_t k[3];
+    image_masks(d, w, k);
+    const int zero = (k[0] >> kImgBias) & (k[1] >> kImgBias) & (k[2] >> kImgBias) & 1;
+    c = __popc(k[0]) * __popc(k[1]) * __popc(k[2]) - zero;
+  }
+  pos_w[3 * i + 0] = w.x; pos_w[3 * i + 1] = w.y; pos_w[3 * i + 2] = w.z;
+  cnt[i] = c;
+}
+
+__global__ __launch_bounds__(kImgThreads) void images_fill_batch_kernel(const float* __restrict__ pos_w,
+                                                                        const int32_t* __restrict__ structure, int64_t n,
+                                                                        const ImgRec* __restrict__ table, int B,
+                                                                        const int32_t* __restrict__ off, int64_t total,
+                                                                        int32_t* __restrict__ owner, int32_t* __restrict__ shift,
+                                                                        float* __restrict__ image_pos) {
+  const int64_t i = blockIdx.x * (int64_t)kImgThreads + threadIdx.x;
+  if (i >= n) return;
+  const int s = structure[i];
+  ImgDev d;
+  if (s < 0 || s >= B || !load_record(table, s, d)) return;
+  const float3 w = make_float3(pos_w[3 * i + 0], pos_w[3 * i + 1], pos_w[3 * i + 2]);
+  uint32_t k[3];
+  image_masks(d, w, k);
+  int64_t o = off[i];
+  const int64_t end = off[i + 1] < total ? off[i + 1] : total;   // as the single-cell fill: nothing past the particle's own
+  for (int n0 = -d.m[0]; n0 <= d.m[0]; ++n0) {                  // rows and nothing past the arrays
+    if (!((k[0] >> (n0 + kImgBias)) & 1)) continue;
+    for (int n1 = -d.m[1]; n1 <= d.m[1]; ++n1) {
+      if (!((k[1] >> (n1 + kImgBias)) & 1)) continue;
+      for (int n2 = -d.m[2]; n2 <= d.m[2]; ++n2) {
+        if (!((k[2] >> (n2 + kImgBias)) & 1) || (n0 == 0 && n1 == 0 && n2 == 0)) continue;
+        if (o < 0 || o >= end) return;
+        float x = w.x, y = w.y, z = w.z;
+        cell_shift(d.rc.c, (float)-n0, (float)-n1, (float)-n2, x, y, z);
+        owner[o] = (int32_t)i;
+        shift[3 * o + 0] = n0; shift[3 * o + 1] = n1; shift[3 * o + 2] = n2;
+        image_pos[3 * o + 0] = x; image_pos[3 * o + 1] = y; image_pos[3 * o + 2] = z;
+        ++o;
+      }
+    }
+  }
+}
+
 // host: shells and margin (include/e3gnn.h).  E3_ERR_INVALID_ARG for a cell that does not derive, a non-finite origin or an
 // r that is not finite and positive.  The shells are reported as they are (capped at 2^20): shells_ok is the limit
 static int image_plan(const float* cell, const float* origin, float r, ImgDev* d) {
@@ -122,6 +202,23 @@ static bool image_sizes_ok(int64_t n, const ImgDev& d) {
   const int64_t per = (int64_t)(2 * d.m[0] + 1) * (2 * d.m[1] + 1) * (2 * d.m[2] + 1);
   return n >= 0 && n * per < 0x7fffffffLL;
 }
+
+// a batch: the host copy of the table and the particles per structure.  Every structure inside the shell limit, the counts
+// non-negative with sum N, and sum_b counts[b] (2 m_0 + 1)(2 m_1 + 1)(2 m_2 + 1) < 2^31 - 1 with each structure's own shells
+static bool batch_sizes_ok(const ImgRec* host, const int64_t* counts, int64_t B, int64_t n) {
+  if (B < 0 || B >= 0x7fffffffLL || n < 0 || (B > 0 && (!host || !counts))) return false;
+  int64_t atoms = 0, rows = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const ImgDev& d = host[b].d;
+    if (!shells_ok(d) || d.m[0] < 1 || d.m[1] < 1 || d.m[2] < 1 || counts[b] < 0 || counts[b] >= 0x7fffffffLL) return false;
+    atoms += counts[b];
+    rows += counts[b] * ((int64_t)(2 * d.m[0] + 1) * (2 * d.m[1] + 1) * (2 * d.m[2] + 1));
+    if (atoms >= 0x7fffffffLL || rows >= 0x7fffffffLL) return false;
+  }
+  return atoms == n;
+}
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static inline int img_blocks(int64_t n) { return (int)((n + kImgThreads - 1) / kImgThreads); }
 
@@ -298,6 +395,59 @@ int e3_cell_images_fill(const float* pos_wrapped, int64_t N, const float cell[9]
   if (!pos_wrapped || !offsets || !owner || !shift || !image_pos) return E3_ERR_INVALID_ARG;
   hipLaunchKernelGGL(images_fill_kernel, dim3(img_blocks(N)), dim3(kImgThreads), 0, (hipStream_t)stream, pos_wrapped, N, d,
                      offsets, G, owner, shift, image_pos);
+  E3_HIP_CHECK(hipGetLastError());
+  return E3_OK;
+}
+
+int64_t e3_cell_images_record_bytes(void) { return (int64_t)sizeof(ImgRec); }
+
+int e3_cell_images_plan_batch(const float* cells, const float* origins, int64_t B, float r, int32_t* shells, float* rho,
+                              void* table) {
+  if (B < 0 || B >= 0x7fffffffLL || !cells || !origins || !shells || !rho || !table || !aligned16(table))
+    return E3_ERR_INVALID_ARG;
+  ImgRec* rec = static_cast<ImgRec*>(table);
+  for (int64_t b = 0; b < B; ++b) {
+    ImgDev d;
+    const int st = image_plan(cells + 9 * b, origins + 3 * b, r, &d);
+    if (st != E3_OK) return st;
+    for (int a = 0; a < 3; ++a) shells[3 * b + a] = d.m[a];
+    rho[b] = d.rho;
+    rec[b].d = d;
+  }
+  return E3_OK;
+}
+
+int e3_cell_images_count_batch(const float* pos, const int32_t* structure, int64_t N, const void* table,
+                               const void* table_host, const int64_t* counts, int64_t B, float* pos_wrapped, int32_t* offsets,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!batch_sizes_ok(static_cast<const ImgRec*>(table_host), counts, B, N) || !offsets || !workspace ||
+      (N > 0 && (!pos || !structure || !pos_wrapped || !table || !aligned16(table))))
+    return E3_ERR_INVALID_ARG;
+  if (workspace_bytes < e3_cell_images_workspace_bytes(N)) return E3_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) {
+    E3_HIP_CHECK(hipMemsetAsync(offsets, 0, 4, s));
+    return E3_OK;
+  }
+  int32_t* cnt = static_cast<int32_t*>(workspace);
+  E3_HIP_CHECK(hipMemsetAsync(cnt + N, 0, 4, s));
+  hipLaunchKernelGGL(images_count_batch_kernel, dim3(img_blocks(N)), dim3(kImgThreads), 0, s, pos, structure, N,
+                     static_cast<const ImgRec*>(table), (int)B, pos_wrapped, cnt);
+  E3_HIP_CHECK(hipGetLastError());
+  E3_HIP_CHECK(exclusive_sum(static_cast<char*>(workspace) + img_cnt_bytes(N), scan_temp_bytes(N + 1), cnt, offsets, N + 1, s));
+  return E3_OK;
+}
+
+int e3_cell_images_fill_batch(const float* pos_wrapped, const int32_t* structure, int64_t N, const void* table,
+                              const void* table_host, const int64_t* counts, int64_t B, const int32_t* offsets, int64_t G,
+                              int32_t* owner, int32_t* shift, float* image_pos, void* stream) {
+  if (!batch_sizes_ok(static_cast<const ImgRec*>(table_host), counts, B, N) || G < 0 || N + G >= 0x7fffffffLL)
+    return E3_ERR_INVALID_ARG;
+  if (N == 0 || G == 0) return E3_OK;
+  if (!pos_wrapped || !structure || !table || !aligned16(table) || !offsets || !owner || !shift || !image_pos)
+    return E3_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(images_fill_batch_kernel, dim3(img_blocks(N)), dim3(kImgThreads), 0, (hipStream_t)stream, pos_wrapped,
+                     structure, N, static_cast<const ImgRec*>(table), (int)B, offsets, G, owner, shift, image_pos);
   E3_HIP_CHECK(hipGetLastError());
   return E3_OK;
 }
